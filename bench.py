@@ -11,6 +11,11 @@ sharded by contiguous row blocks over the ranks (total work fixed => strong scal
 `--config 5` runs BASELINE configuration 5 instead (mixture of K = 8 components, N = 5 M): one step = one
 PPCAMix EM iteration = ONE C-ABI call per rank (ppca_mix_em_step_sharded / ppca_mix_em_step).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints that line.  `--full` adds what the headline does not need:
+the CPU baseline (not with --no-cpu) and, on the default run, the secondary legs of configurations 2, 4 and 5 (not
+with --no-secondary).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64);
+the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -246,6 +251,22 @@ def sustained_mfma_from_profiles():
     return None
 
 
+def dump_outputs(out_dir: str, em, llk_last: float, mixture: bool) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (a few hundred KB at most).
+    EM: the next model (sigma, transform, mean) and the log-likelihood of the model that entered the step; mixture: the
+    next mixture (per-component sigmas, transforms, means, log-weights) and the mixture log-likelihood of its input."""
+    os.makedirs(out_dir, exist_ok=True)
+    if mixture:
+        mix = em.mixture()
+        arrays = {"sigma": [m.isotropic_noise for m in mix.models], "transform": [m.transform for m in mix.models],
+                  "mean": [m.mean for m in mix.models], "log_weights": mix.log_weights, "llk": [llk_last]}
+    else:
+        fm = em.model()
+        arrays = {"sigma": [fm.isotropic_noise], "transform": fm.transform, "mean": fm.mean, "llk": [llk_last]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 SECONDARY = {
     # BASELINE.json configurations 2, 4 and 5 as SHORT legs of the default run, so that the driver's clock sees them too (round 5's
     # review: five rounds of config-4 / config-5 numbers were only ever on the builder's clock).  No CPU leg for them.
@@ -376,9 +397,20 @@ def main() -> None:
                          "5: mixture of 8 components, 5M x 256 x 10); 0 = take --n/--d/--k/--mask as given")
     ap.add_argument("--components", type=int, default=8, help="config 5: number of mixture components")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="the default run (one GPU, the headline configuration) also times short legs of BASELINE configurations 2, 4 and "
-                         "5 after the headline region and reports them under \"secondary\"; this switch leaves them out")
+                    help="with --full, the default run (one GPU, the headline configuration) also times short legs of BASELINE configurations "
+                         "2, 4 and 5 after the headline region and reports them under \"secondary\"; this switch leaves them out")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (unless --no-cpu) and, on the default run, "
+                         "the secondary legs (unless --no-secondary); off by default, so that a plain run only sets up, warms up and "
+                         "times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (the next model and the log-likelihood of its input "
+                         "model) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     default_run = args.config in (0, 3) and (args.n, args.d, args.k, args.mask) == (10_000_000, 256, 10, 0.3) and args.outliers == 0 and args.gram == "auto"
     mask_kind, mask_run = 0, 0
     if args.config == 1:
@@ -538,6 +570,8 @@ def main() -> None:
     if args.dump_model and rank == 0 and not mixture:
         fm = em.model()
         np.savez(args.dump_model, sigma=fm.isotropic_noise, transform=fm.transform, mean=fm.mean, llk=llk_last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, em, llk_last, mixture)
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
@@ -728,7 +762,7 @@ def main() -> None:
                           "ms_per_step": ms_per_step, "value": iters_per_s, "unit": unit},
             }
             out["llk_per_sample_trace"] = [v / n for v in llk_trace]
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             if mixture:
                 rows = min(20_000, rows_local)
                 out["cpu_baseline"] = cpu_baseline_mix(shard._slice(0, rows).numpy(), start, n)
@@ -736,7 +770,7 @@ def main() -> None:
                 out["cpu_baseline"] = cpu_baseline(shard, start, n, d, k, min(args.cpu_rows, rows_local))
         else:
             out["cpu_baseline"] = None
-        if world == 1 and default_run and not args.no_secondary:
+        if world == 1 and default_run and args.full and not args.no_secondary:
             # BASELINE configurations 2, 4, 5 on the same clock as the headline: short legs, after the headline's dataset is released
             em.close()
             del em, shard

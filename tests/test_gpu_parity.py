@@ -774,6 +774,45 @@ def test_two_ranks_on_one_gpu_match_single_rank(P, tmp_path):
     assert abs(a["llk"] - b["llk"]) < 1e-10 * abs(a["llk"])
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """bench.py without --full: exactly --steps timed steps, ms_per_step in the line, no CPU baseline and no secondary legs;
+    --dump-outputs writes the last timed step's outputs (float64), the same model --dump-model writes; the mixture's too."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    model, out = str(tmp_path / "model.npz"), tmp_path / "em"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--samples", "200000",
+                        "--dump-model", model, "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] * j["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert j["cpu_baseline"] is None and "secondary" not in j
+    assert j["unit"] == "EM iters/sec" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    m = np.load(model)
+    got = {f: np.load(out / (f + ".npy")) for f in ("sigma", "transform", "mean", "llk")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["transform"].shape == (256, 10) and got["mean"].shape == (256,)
+    for f in got:
+        np.testing.assert_array_equal(got[f].reshape(np.shape(m[f])), m[f])
+    assert abs(got["llk"][0] / 200000 - j["llk_per_sample_last_input_model"]) < 1e-12 * abs(got["llk"][0] / 200000)
+
+    out = tmp_path / "mix"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "5", "--gpus", "1", "--samples", "400000", "--components", "4",
+                        "--steps", "2", "--warmup", "3", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 2 and len(j["llk_per_sample_trace"]) == 5 and j["cpu_baseline"] is None
+    got = {f: np.load(out / (f + ".npy")) for f in ("sigma", "transform", "mean", "log_weights", "llk")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["transform"].shape == (4, 256, 10) and got["mean"].shape == (4, 256) and got["sigma"].shape == (4,)
+    assert np.all(got["sigma"] > 0) and abs(np.log(np.exp(got["log_weights"]).sum())) < 1e-12
+    assert abs(got["llk"][0] / 400000 - j["llk_per_sample_trace"][-1]) < 1e-12 * abs(got["llk"][0] / 400000)
+
+
 @pytest.mark.parametrize("shape", ["small", "cfg5"])
 def test_sharded_mixture_two_ranks_on_one_gpu(shape):
     """BASELINE config 5's multi-GPU path (ShardedMixEM: all-reduce MAX of the component maxima, one all-reduce SUM
