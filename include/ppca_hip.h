@@ -208,6 +208,16 @@ int ppca_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, i
 int ppca_covariance_diagonal(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int32_t mode,
                              ppca_dataset **out);
 
+/* Posterior sampling / multiple imputation (PosteriorSampler, ppca_model.rs:597-626, without the host round trip): for every
+ * row i, with z_i, Sigma_i the posterior of ppca_infer and U_i the upper-triangular factor of Sigma_i = U_i U_i^T,
+ *   mode 0 (sample): x_i = C (z_i + U_i eps_i) + mean + sigma eta_i on every dimension;
+ *   mode 1 (impute): observed entries passed through bit-exactly, masked ones the mode-0 value (one multiple-imputation draw).
+ * eps_i (k) and eta_i (d) are standard normals of a counter-based generator keyed by (seed, stream, row_offset + i, index)
+ * (DESIGN.md 4.9): the draws do not depend on the grid, chunking or path, and a shard with the right row_offset reproduces
+ * the single-device rows.  A new fully observed dataset carrying the input weights. */
+int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int32_t mode, uint64_t seed,
+                          int64_t row_offset, ppca_dataset **out);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration
@@ -299,6 +309,12 @@ int ppca_vector_sum_dev(ppca_ctx *ctx, const double *v_dev, const double *w_dev,
  * fresh samples). */
 int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights,
                          int32_t n_models, int32_t mode, ppca_dataset **out);
+
+/* PosteriorSamplerMix (mix.rs:521-537) on the device: per row a component from its posterior (a uniform of the row's choice
+ * stream against the cumulative posterior in component order), then that component's ppca_posterior_sample draw of the row
+ * (component c takes the first k_c normals of the row's eps stream).  The output carries no weights. */
+int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights,
+                              int32_t n_models, int32_t mode, uint64_t seed, int64_t row_offset, ppca_dataset **out);
 
 /* ------------------------------------------------------------------ debug */
 /* Test hook: cap the number of workgroups of every persistent-grid launch of this context (the fused kernels start

@@ -429,6 +429,24 @@ class PPCAModel:
         """Observed values kept, masked ones replaced by C z + mean (ppca_model.rs:254-261)."""
         return self._recon(dataset, 1, lib().ppca_reconstruct)
 
+    def sample_posterior(self, dataset: Dataset, seed: Optional[int] = None, *, keep_observed: bool = False,
+                         row_offset: int = 0) -> Dataset:
+        """One draw per row from the posterior predictive, on the GPU in one pass: C (z + U eps) + mean + sigma eta with
+        z, Sigma = U U^T the row's posterior (what `infer` returns) and eps, eta standard normals of a counter-based
+        generator keyed by (seed, row_offset + row, index).  keep_observed=True: observed entries are passed through
+        unchanged and only the masked ones are drawn (one draw of multiple imputation).  The result carries the input
+        weights.  The draw of a row does not depend on how the dataset is split: a slice starting at row s with
+        row_offset=s reproduces those rows of the whole.  seed=None draws a fresh seed."""
+        if row_offset < 0:
+            raise ValueError("row_offset must be >= 0")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        ctx = dataset._ctx
+        h = C.c_void_p()
+        check(lib().ppca_posterior_sample(ctx.handle, dataset._h, self._device(ctx).h, int(bool(keep_observed)),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), C.byref(h)))
+        return Dataset._wrap(h, ctx)
+
     def _iterate(self, dataset: Dataset, prior: Optional[Prior], want_llk: bool):
         ctx = dataset._ctx
         if len(dataset) == 0:
@@ -556,12 +574,13 @@ class InferredMasked:
         return self._as_dataset(np.where(np.isfinite(x), 0.0, diag))
 
     def posterior_sampler(self) -> "PosteriorSampler":
-        """ppca_model.rs:581-592"""
+        """ppca_model.rs:581-592 -- host-side, with numpy's generator (its draws for a seed are kept as they are).
+        PPCAModel.sample_posterior draws on the GPU in one pass, without the covariances leaving the device."""
         return PosteriorSampler(self._model, self._states, np.linalg.cholesky(self._covs))
 
 
 class PosteriorSampler:
-    """ppca_model.rs:597-626; src/python_bindings.rs:347-365"""
+    """ppca_model.rs:597-626; src/python_bindings.rs:347-365.  Host-side; see PPCAModel.sample_posterior for the GPU pass."""
 
     def __init__(self, model: PPCAModel, states: np.ndarray, chol: np.ndarray):
         self._model, self._states, self._chol = model, states, chol
@@ -754,6 +773,22 @@ class PPCAMix:
         """mix.rs:254-265, :414-423"""
         return self._mix_recon(dataset, 1)
 
+    def sample_posterior(self, dataset: Dataset, seed: Optional[int] = None, *, keep_observed: bool = False,
+                         row_offset: int = 0) -> Dataset:
+        """One draw per row on the GPU: a component from the row's posterior over the components, then that component's
+        PPCAModel.sample_posterior draw of the row (same generator, same keep_observed / row_offset meaning).  The result
+        carries no weights, like the other mixture outputs.  seed=None draws a fresh seed."""
+        if row_offset < 0:
+            raise ValueError("row_offset must be >= 0")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        ctx = dataset._ctx
+        devs, arr = self._handles(ctx)
+        h = C.c_void_p()
+        check(lib().ppca_mix_posterior_sample(ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), int(bool(keep_observed)),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), C.byref(h)))
+        return Dataset._wrap(h, ctx)
+
     def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None) -> Dataset:
         """mix.rs:124-134: a component per sample from the prior weights, then that component's generative
         process (component blocks are generated on the GPU and interleaved by a random permutation)."""
@@ -901,7 +936,8 @@ class InferredMaskedMix:
 
 class PosteriorSamplerMix:
     """mix.rs:521-537; src/python_bindings.rs:887-905: a component per sample from its posterior, then a draw
-    from that component's state posterior pushed through its model."""
+    from that component's state posterior pushed through its model.  Host-side, with numpy's generator (its draws for a
+    seed are kept as they are); PPCAMix.sample_posterior draws on the GPU in one call."""
 
     def __init__(self, posteriors: np.ndarray, samplers: List["PosteriorSampler"]):
         self._post, self._samplers = posteriors, samplers

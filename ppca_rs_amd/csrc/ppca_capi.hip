@@ -1289,6 +1289,64 @@ extern "C" int ppca_covariance_diagonal(ppca_ctx *ctx, ppca_dataset *ds, const p
     return recon_common(ctx, ds, model, 2 + mode, out);
 }
 
+// ------------------------------------------------------------------ posterior sampling
+// The draw of ppca_sample.hip over the dataset's rows into out (dataset rows x d): the posterior means and covariances of a
+// chunk of rows (the pass of ppca_infer, fused or generic) into scratch, then one draw kernel over the chunk.  Chunks bound the
+// scratch at 1 GiB (N x k x k doubles would not fit at N = 10 M, k = 64); the draw depends on the row alone, not on the chunk.
+static int posterior_sample_rows(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int mode, uint64_t seed,
+                                 int64_t row_offset, double *out, const int *choice, int comp) {
+    const int k = model->k;
+    const int64_t per_row = (int64_t)sizeof(double) * ((int64_t)k * k + k);
+    const int64_t chunk = std::max<int64_t>(1024, std::min<int64_t>(ds->n, ((int64_t)1 << 30) / per_row));
+    const size_t rows = (size_t)std::min(chunk, ds->n);
+    BufRef st, cv;
+    if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
+    double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
+    for (int64_t r0 = 0; r0 < ds->n; r0 += chunk) {
+        ppca_dataset part(*ds);
+        part.n = std::min(chunk, ds->n - r0);
+        part.X = ds->X + r0 * ds->d;
+        part.w = ds->w ? ds->w + r0 : nullptr;
+        if (int rc = run_post(ctx, &part, model, nullptr, states, covs, nullptr, 0, nullptr)) return rc;
+        HIP_TRY(launch_posterior_draw(ds->X, ds->d, ds->d, k, part.n, r0, row_offset, model->p(), states, covs, out, mode, seed,
+                                      choice, comp, ctx->n_cu, ctx->stream));
+    }
+    return PPCA_OK;
+}
+
+static int posterior_out(ppca_ctx *ctx, ppca_dataset *ds, bool carry_weights, std::unique_ptr<ppca_dataset> &nd) {
+    nd = std::make_unique<ppca_dataset>();
+    nd->ctx = ctx;
+    nd->n = ds->n;
+    nd->d = ds->d;
+    if (carry_weights) {
+        nd->wbuf = ds->wbuf;
+        nd->w = ds->w;
+    }
+    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(ds->n, 1) * ds->d, &nd->xbuf)) return rc;
+    nd->X = static_cast<const double *>(nd->xbuf->p);
+    return PPCA_OK;
+}
+
+extern "C" int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int32_t mode, uint64_t seed,
+                                     int64_t row_offset, ppca_dataset **out) {
+    if (!ctx || !out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (mode != 0 && mode != 1) return fail(PPCA_ERR_INVALID, "mode must be 0 (sample) or 1 (impute)");
+    if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
+    if (int rc = check_pair(ds, model)) return rc;
+    USE_CTX(ctx);
+    std::unique_ptr<ppca_dataset> nd;
+    if (int rc = posterior_out(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
+    if (ds->n > 0) {
+        if (int rc = posterior_sample_rows(ctx, ds, model, mode, seed, row_offset, static_cast<double *>(nd->xbuf->p), nullptr, 0))
+            return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    *out = nd.release();
+    return PPCA_OK;
+}
+
 // ------------------------------------------------------------------ mixture
 static int mix_check(ppca_dataset *ds, ppca_model *const *models, int32_t nm) {
     if (!ds || !models || nm < 1) return fail(PPCA_ERR_INVALID, "bad mixture arguments");
@@ -1896,6 +1954,34 @@ extern "C" int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model 
             HIP_TRY(launch_mix_accumulate(o, dg.p->X, val.p->X, mean, logpost, c, nm, n, d, c == 0, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
         }
+    }
+    *out = nd.release();
+    return PPCA_OK;
+}
+
+// A component per row from its posterior (the choice stream), then that component's draw of the row (its own path; component c
+// uses the first k_c normals of the row's eps stream).  One sweep per component, each writing only the rows that chose it.
+extern "C" int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights,
+                                         int32_t n_models, int32_t mode, uint64_t seed, int64_t row_offset, ppca_dataset **out) {
+    if (!ctx || !log_weights || !out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (mode != 0 && mode != 1) return fail(PPCA_ERR_INVALID, "mode must be 0 (sample) or 1 (impute)");
+    if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
+    if (int rc = mix_check(ds, models, n_models)) return rc;
+    USE_CTX(ctx);
+    std::unique_ptr<ppca_dataset> nd;
+    if (int rc = posterior_out(ctx, ds, false, nd)) return rc;  // no weights, like the other mixture outputs
+    const int64_t n = ds->n;
+    if (n > 0) {
+        BufRef llk, u, lse, lp, ch;
+        if (int rc = mix_posteriors(ctx, ds, models, log_weights, n_models, llk, u, lse, &lp)) return rc;
+        if (int rc = dev_alloc(sizeof(int) * (size_t)n, &ch)) return rc;
+        int *choice = static_cast<int *>(ch->p);
+        HIP_TRY(launch_mix_choose(static_cast<const double *>(lp->p), n, n_models, seed, row_offset, choice, ctx->stream));
+        for (int c = 0; c < n_models; ++c)
+            if (int rc = posterior_sample_rows(ctx, ds, models[c], mode, seed, row_offset, static_cast<double *>(nd->xbuf->p),
+                                               choice, c))
+                return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     *out = nd.release();
     return PPCA_OK;

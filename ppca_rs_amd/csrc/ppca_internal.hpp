@@ -238,6 +238,16 @@ hipError_t generic_gram_guard(int d, int k, const double *model, void *ws, hipSt
 hipError_t generic_finalize(int k, int d, const double *stats, const double *model_in, double *model_out, double tau,
                             int has_ig, double alpha, double beta, int n_cu, hipStream_t s);
 
+// posterior sampling (ppca_sample.hip): the draw of DESIGN.md section 4.7 for rows [row0, row0 + n_rows) of a dataset from their
+// posterior means / covariances (states, covs: the chunk's own rows) into out (dataset rows x d); choice (nullable): only rows
+// whose choice[row] == comp are written.  mix_choose: a component per row from the log posteriors (n x nm).
+size_t posterior_draw_lds_bytes(int k);
+hipError_t launch_posterior_draw(const double *X, int64_t ldx, int d, int k, int64_t n_rows, int64_t row0, int64_t row_offset,
+                                 const double *model, const double *states, const double *covs, double *out, int mode,
+                                 uint64_t seed, const int *choice, int comp, int n_cu, hipStream_t s);
+hipError_t launch_mix_choose(const double *logpost, int64_t n, int nm, uint64_t seed, int64_t row_offset, int *choice,
+                             hipStream_t s);
+
 // mixture helpers
 // llk: [n_models][n]; logw: [n_models]; w nullable.  Writes u: [n_models][n] =
 // ln w_i + log posterior_ic (-inf when w_i <= 0) and lse[n] (mixture llk per sample).

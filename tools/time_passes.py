@@ -1,5 +1,6 @@
 """Times the output passes that share the per-sample core with the EM pass (llk, llks, infer, smooth,
-extrapolate, covariance diagonal) through the public API, device-resident inputs (diagnostic)."""
+extrapolate, covariance diagonal, posterior sample / impute) through the public API, device-resident inputs (diagnostic);
+then the host posterior sampler (infer + numpy) on a slice of at most 1 M rows."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -41,6 +42,12 @@ def cdiag(mode):
     _lib.check(L.ppca_covariance_diagonal(ctx.handle, ds._h, md.h, mode, C.byref(o)))
     L.ppca_dataset_free(o)
 timed("smoothed cov diagonal", lambda: cdiag(0), 16 * d)
+def psample(mode):
+    o = C.c_void_p()
+    _lib.check(L.ppca_posterior_sample(ctx.handle, ds._h, md.h, mode, 7, 0, C.byref(o)))
+    L.ppca_dataset_free(o)
+timed("posterior sample", lambda: psample(0), 16 * d)
+timed("posterior impute", lambda: psample(1), 16 * d)
 nn = min(n, 1_000_000)
 sub = ds._slice(0, nn)
 st, cv = np.empty((nn, k)), np.empty((nn, k, k))
@@ -48,3 +55,11 @@ t0 = time.perf_counter(); _lib.check(L.ppca_infer(ctx.handle, sub._h, md.h, _lib
 _lib.check(L.ppca_infer(ctx.handle, sub._h, md.h, _lib.ptr(st), _lib.ptr(cv))); t2 = time.perf_counter()
 print(f"infer states only ({nn} rows, incl. D2H)      {1e3*(t1-t0):8.2f} ms")
 print(f"infer states + covariances (incl. D2H {cv.nbytes/1e6:.0f} MB) {1e3*(t2-t1):8.2f} ms")
+del st, cv
+nh = min(nn, max(1000, (1 << 32) // (8 * k * k * 3)))  # the host sampler holds about three N x k x k arrays: 4 GB at most
+hs = ds._slice(0, nh)
+t3 = time.perf_counter(); m.infer(hs).posterior_sampler().sample(seed=7); t4 = time.perf_counter()
+o = C.c_void_p()
+_lib.check(L.ppca_posterior_sample(ctx.handle, hs._h, md.h, 0, 7, 0, C.byref(o))); t5 = time.perf_counter()
+L.ppca_dataset_free(o)
+print(f"host posterior sampler ({nh} rows: infer + numpy + upload) {1e3*(t4-t3):8.2f} ms   device posterior sample, same rows {1e3*(t5-t4):8.2f} ms")
