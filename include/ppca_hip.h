@@ -218,6 +218,18 @@ int ppca_covariance_diagonal(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *
 int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int32_t mode, uint64_t seed,
                           int64_t row_offset, ppca_dataset **out);
 
+/* Leave-one-out predictive of every entry (an extension with no reference counterpart): for each entry j of row i,
+ * the predictive of x_ij given the row's OTHER observed entries, the model held fixed.  With z, Sigma the row's posterior (ppca_infer),
+ * r_j = x_j - mean_j - c_j^T z, q_j = c_j^T Sigma c_j and s_j = sigma^2 - q_j:
+ *   observed j: mean x_j - sigma^2 r_j / s_j, variance sigma^4 / s_j, log-density l_j = -1/2 (log 2 pi + log(sigma^4 / s_j) + r_j^2 / s_j)
+ *   masked j:   mean mean_j + c_j^T z (ppca_reconstruct mode 1), variance sigma^2 + q_j (ppca_covariance_diagonal mode 1)
+ * An observed entry whose s_j rounding took to sigma^4 / (sigma^2 + |c_j|^2) or below (the exact value is never below) gets the
+ * prior predictive (mean_j, sigma^2 + |c_j|^2).  per_sample_host[i] = sum of l_j over the row's observed entries (0 for a row with
+ * none), total_host = sum_i w_i per_sample_host[i].  mean_out / var_out: new fully observed datasets carrying the input weights.
+ * Every output is nullable, at least one is given; with both dataset outputs null no N x d buffer is allocated or written. */
+int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, ppca_dataset **mean_out, ppca_dataset **var_out,
+                        double *total_host, double *per_sample_host);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration
@@ -315,6 +327,14 @@ int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *mod
  * (component c takes the first k_c normals of the row's eps stream).  The output carries no weights. */
 int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights,
                               int32_t n_models, int32_t mode, uint64_t seed, int64_t row_offset, ppca_dataset **out);
+
+/* The leave-one-out predictive of a mixture (an extension with no reference counterpart).  Component c gives m_cj,
+ * v_cj, l_cj as ppca_loo_predictive does; lp_c is the row's log posterior of c (ppca_mix_llk).  Observed j: a_cj = exp(lp_c - l_cj - L_j)
+ * with L_j = log sum_c exp(lp_c - l_cj) (the posterior of c given the row without j), l_j = -L_j.  Masked j: a_cj = exp(lp_c).  Mean
+ * sum_c a_cj m_cj, variance sum_c a_cj (v_cj + (m_cj - mean_j)^2).  per_sample_host / total_host as ppca_loo_predictive (total: the
+ * sample weights applied, as ppca_mix_llk).  The output datasets carry no weights, like every mixture output. */
+int ppca_mix_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights, int32_t n_models,
+                            ppca_dataset **mean_out, ppca_dataset **var_out, double *total_host, double *per_sample_host);
 
 /* ------------------------------------------------------------------ debug */
 /* Test hook: cap the number of workgroups of every persistent-grid launch of this context (the fused kernels start

@@ -101,6 +101,8 @@ SIGNATURES = {
     "ppca_covariance_diagonal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, c_void_pp]),
     "ppca_posterior_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, c_void_pp]),
     "ppca_mix_posterior_sample": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, c_void_pp]),
+    "ppca_loo_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, c_void_pp, c_double_p, C.c_void_p]),
+    "ppca_mix_loo_predictive": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, c_void_pp, c_void_pp, c_double_p, C.c_void_p]),
     "ppca_mix_em_step": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.POINTER(Prior), c_void_pp, C.c_void_p, c_double_p]),
     "ppca_mix_last_rows_used": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "ppca_mix_llk": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, c_double_p, C.c_void_p, C.c_void_p]),

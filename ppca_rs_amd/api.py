@@ -447,6 +447,26 @@ class PPCAModel:
                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), C.byref(h)))
         return Dataset._wrap(h, ctx)
 
+    def _loo(self, dataset: Dataset, full: bool, per_sample: bool):
+        ctx = dataset._ctx
+        return _loo_call(dataset, full, per_sample, lambda mh, vh, tot, ps: lib().ppca_loo_predictive(
+            ctx.handle, dataset._h, self._device(ctx).h, mh, vh, tot, ps))
+
+    def loo_predictive(self, dataset: Dataset) -> "LooPredictive":
+        """The predictive of every entry given the OTHER observed entries of its row, the model held fixed (one GPU pass; an
+        extension with no reference counterpart).  Observed entries: the leave-one-out mean and variance, and the log-density
+        of the entry under them; masked entries: the `extrapolate` value and the extrapolated covariance diagonal."""
+        return self._loo(dataset, True, True)
+
+    def loo_llks(self, dataset: Dataset) -> np.ndarray:
+        """Per row, the sum over its observed entries of the leave-one-out log-density (0 for a row with none); no N x d output
+        is written."""
+        return self._loo(dataset, False, True)._llks
+
+    def loo_llk(self, dataset: Dataset) -> float:
+        """sum_i w_i loo_llks[i]: the leave-one-out pseudo-log-likelihood, a criterion for the state size that needs no refit."""
+        return self._loo(dataset, False, False)._llk
+
     def _iterate(self, dataset: Dataset, prior: Optional[Prior], want_llk: bool):
         ctx = dataset._ctx
         if len(dataset) == 0:
@@ -577,6 +597,46 @@ class InferredMasked:
         """ppca_model.rs:581-592 -- host-side, with numpy's generator (its draws for a seed are kept as they are).
         PPCAModel.sample_posterior draws on the GPU in one pass, without the covariances leaving the device."""
         return PosteriorSampler(self._model, self._states, np.linalg.cholesky(self._covs))
+
+
+def _loo_call(dataset: Dataset, full: bool, per_sample: bool, fn) -> "LooPredictive":
+    ctx = dataset._ctx
+    mh, vh = C.c_void_p(), C.c_void_p()
+    tot = C.c_double(0.0)
+    llks = np.empty(len(dataset)) if per_sample else None
+    check(fn(C.byref(mh) if full else None, C.byref(vh) if full else None, C.byref(tot), ptr(llks)))
+    mean = Dataset._wrap(mh, ctx) if full else None
+    var = Dataset._wrap(vh, ctx) if full else None
+    return LooPredictive(dataset, mean, var, llks, tot.value)
+
+
+class LooPredictive:
+    """What PPCAModel.loo_predictive / PPCAMix.loo_predictive return: per entry the predictive given the other observed
+    entries of the row (mean(), variance(): device-resident datasets), per row the sum of the observed entries' log-densities
+    (llks()) and its weighted total (llk())."""
+
+    def __init__(self, dataset: Dataset, mean: Optional[Dataset], var: Optional[Dataset], llks: Optional[np.ndarray], llk: float):
+        self._dataset, self._mean, self._var, self._llks, self._llk = dataset, mean, var, llks, llk
+
+    def mean(self) -> Dataset:
+        return self._mean
+
+    def variance(self) -> Dataset:
+        return self._var
+
+    def llks(self) -> np.ndarray:
+        return self._llks.copy()
+
+    def llk(self) -> float:
+        return self._llk
+
+    def zscores(self) -> np.ndarray:
+        """Host-side (x - mean) / sqrt(variance) on observed entries, NaN on masked ones: standard normal under a calibrated
+        model; a large magnitude marks the entry of a row that its other entries do not explain."""
+        x = self._dataset.numpy()
+        z = (x - self._mean.numpy()) / np.sqrt(self._var.numpy())
+        z[~np.isfinite(x)] = np.nan
+        return z
 
 
 class PosteriorSampler:
@@ -788,6 +848,26 @@ class PPCAMix:
         check(lib().ppca_mix_posterior_sample(ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), int(bool(keep_observed)),
                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), C.byref(h)))
         return Dataset._wrap(h, ctx)
+
+    def _loo(self, dataset: Dataset, full: bool, per_sample: bool):
+        ctx = dataset._ctx
+        devs, arr = self._handles(ctx)
+        return _loo_call(dataset, full, per_sample, lambda mh, vh, tot, ps: lib().ppca_mix_loo_predictive(
+            ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), mh, vh, tot, ps))
+
+    def loo_predictive(self, dataset: Dataset) -> "LooPredictive":
+        """PPCAModel.loo_predictive for the mixture: per entry the mixture of the components' leave-one-out predictives, each
+        component weighted by its posterior given the row without that entry (masked entries: by its posterior given the
+        row, as `extrapolate` does).  The datasets carry no weights, like the other mixture outputs."""
+        return self._loo(dataset, True, True)
+
+    def loo_llks(self, dataset: Dataset) -> np.ndarray:
+        """PPCAModel.loo_llks for the mixture (no N x d output is written)."""
+        return self._loo(dataset, False, True)._llks
+
+    def loo_llk(self, dataset: Dataset) -> float:
+        """sum_i w_i loo_llks[i], the sample weights applied as in `llk`."""
+        return self._loo(dataset, False, False)._llk
 
     def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None) -> Dataset:
         """mix.rs:124-134: a component per sample from the prior weights, then that component's generative

@@ -1347,6 +1347,89 @@ extern "C" int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca
     return PPCA_OK;
 }
 
+// ------------------------------------------------------------------ leave-one-out predictive
+// Rows that fit 1 GiB of scratch at once (the posterior covariances, and per_entry doubles per row and dimension): the chunking of
+// posterior_sample_rows.  Every output of the LOO kernels depends on its row alone, not on the chunk.
+static int64_t loo_chunk_rows(int64_t n, int d, int k, int per_entry) {
+    const int64_t per_row = (int64_t)sizeof(double) * ((int64_t)k * k + k + (int64_t)per_entry * d + 1);
+    return std::max<int64_t>(1024, std::min<int64_t>(std::max<int64_t>(n, 1), ((int64_t)1 << 30) / per_row));
+}
+
+// The LOO pass of one model over part (a chunk of rows): the posterior pass of ppca_infer (fused or generic) into states / covs, then
+// loo_kernel.  Outputs are the chunk's own rows.
+static int loo_part(ppca_ctx *ctx, ppca_dataset *part, const ppca_model *model, double *states, double *covs, double *mean,
+                    double *var, double *ell, double *llks) {
+    if (int rc = run_post(ctx, part, model, nullptr, states, covs, nullptr, 0, nullptr)) return rc;
+    HIP_TRY(launch_loo(part->X, part->d, part->d, model->k, part->n, model->p(), states, covs, mean, var, ell, llks, ctx->n_cu,
+                       ctx->stream));
+    return PPCA_OK;
+}
+
+static ppca_dataset loo_slice(const ppca_dataset *ds, int64_t r0, int64_t rows) {
+    ppca_dataset part(*ds);
+    part.n = std::min(rows, ds->n - r0);
+    part.X = ds->X + r0 * ds->d;
+    part.w = ds->w ? ds->w + r0 : nullptr;
+    return part;
+}
+
+// total_host = sum_i w_i llks[i] (the fixed-order reduction of ppca_mix_llk), per_sample_host = llks; n = 0: total 0.
+static int loo_totals(ppca_ctx *ctx, ppca_dataset *ds, const double *llks, double *total_host, double *per_sample_host) {
+    const int64_t n = ds->n;
+    double tot = 0.0;
+    if (n > 0) {
+        if (total_host) {
+            double *work = static_cast<double *>(ctx->work->p);
+            HIP_TRY(launch_reduce_sum(llks, ds->w, n, work + 1024, work, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(&tot, work + 1024, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (per_sample_host)
+            HIP_TRY(hipMemcpyAsync(per_sample_host, llks, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (total_host) *total_host = tot;
+    return PPCA_OK;
+}
+
+extern "C" int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, ppca_dataset **mean_out,
+                                   ppca_dataset **var_out, double *total_host, double *per_sample_host) {
+    if (!ctx) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!mean_out && !var_out && !total_host && !per_sample_host) return fail(PPCA_ERR_INVALID, "no output requested");
+    if (int rc = check_pair(ds, model)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int k = model->k;
+    std::unique_ptr<ppca_dataset> md, vd;  // the input weights carried over, as ppca_reconstruct does
+    if (mean_out)
+        if (int rc = posterior_out(ctx, ds, true, md)) return rc;
+    if (var_out)
+        if (int rc = posterior_out(ctx, ds, true, vd)) return rc;
+    const bool want_l = total_host || per_sample_host;
+    BufRef lb;
+    if (want_l)
+        if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1), &lb)) return rc;
+    double *mean = md ? static_cast<double *>(md->xbuf->p) : nullptr, *var = vd ? static_cast<double *>(vd->xbuf->p) : nullptr;
+    double *llks = want_l ? static_cast<double *>(lb->p) : nullptr;
+    if (n > 0) {
+        const int64_t chunk = loo_chunk_rows(n, ds->d, k, 0);
+        const size_t rows = (size_t)std::min(chunk, n);
+        BufRef st, cv;
+        if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            ppca_dataset part = loo_slice(ds, r0, chunk);
+            if (int rc = loo_part(ctx, &part, model, static_cast<double *>(st->p), static_cast<double *>(cv->p),
+                                  mean ? mean + r0 * ds->d : nullptr, var ? var + r0 * ds->d : nullptr, nullptr,
+                                  llks ? llks + r0 : nullptr))
+                return rc;
+        }
+    }
+    if (int rc = loo_totals(ctx, ds, llks, total_host, per_sample_host)) return rc;
+    if (mean_out) *mean_out = md.release();
+    if (var_out) *var_out = vd.release();
+    return PPCA_OK;
+}
+
 // ------------------------------------------------------------------ mixture
 static int mix_check(ppca_dataset *ds, ppca_model *const *models, int32_t nm) {
     if (!ds || !models || nm < 1) return fail(PPCA_ERR_INVALID, "bad mixture arguments");
@@ -1984,6 +2067,68 @@ extern "C" int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_m
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     *out = nd.release();
+    return PPCA_OK;
+}
+
+// Per chunk of rows: each component's LOO pass folded into per-entry state (launch_mix_loo_fold), the mean and L_j, then -- when the
+// variance is wanted -- each component's pass again for the variance around the mean (as ppca_mix_reconstruct recomputes its
+// components rather than keep nm N x d arrays).
+extern "C" int ppca_mix_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights,
+                                       int32_t n_models, ppca_dataset **mean_out, ppca_dataset **var_out, double *total_host,
+                                       double *per_sample_host) {
+    if (!ctx || !log_weights) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!mean_out && !var_out && !total_host && !per_sample_host) return fail(PPCA_ERR_INVALID, "no output requested");
+    if (int rc = mix_check(ds, models, n_models)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int d = ds->d, nm = n_models;
+    std::unique_ptr<ppca_dataset> md, vd;  // no weights, like the other mixture outputs
+    if (mean_out)
+        if (int rc = posterior_out(ctx, ds, false, md)) return rc;
+    if (var_out)
+        if (int rc = posterior_out(ctx, ds, false, vd)) return rc;
+    const bool want_l = total_host || per_sample_host, want_m = mean_out || var_out;
+    BufRef lb;
+    if (want_l)
+        if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1), &lb)) return rc;
+    double *mean = md ? static_cast<double *>(md->xbuf->p) : nullptr, *var = vd ? static_cast<double *>(vd->xbuf->p) : nullptr;
+    double *llks = want_l ? static_cast<double *>(lb->p) : nullptr;
+    if (n > 0) {
+        BufRef llk, u, lse, lp;
+        if (int rc = mix_posteriors(ctx, ds, models, log_weights, nm, llk, u, lse, &lp)) return rc;
+        const double *logpost = static_cast<const double *>(lp->p);
+        int kmax = 1;
+        for (int c = 0; c < nm; ++c) kmax = std::max(kmax, models[c]->k);
+        // per row and dimension: the component's m, v, l and the state mx, sm, wm
+        const int64_t chunk = loo_chunk_rows(n, d, kmax, 6);
+        const size_t rows = (size_t)std::min(chunk, n), nd = rows * (size_t)d;
+        BufRef st, cv, sc;
+        if (int rc = dev_alloc(sizeof(double) * rows * kmax, &st)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * rows * kmax * kmax, &cv)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * nd * 6, &sc)) return rc;
+        double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
+        double *m = static_cast<double *>(sc->p), *v = m + nd, *ell = v + nd, *mx = ell + nd, *sm = mx + nd, *wm = sm + nd;
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            ppca_dataset part = loo_slice(ds, r0, chunk);
+            const double *lpc = logpost + r0 * nm;
+            for (int c = 0; c < nm; ++c) {
+                if (int rc = loo_part(ctx, &part, models[c], states, covs, want_m ? m : nullptr, nullptr, ell, nullptr)) return rc;
+                HIP_TRY(launch_mix_loo_fold(part.X, d, d, part.n, lpc, c, nm, m, ell, mx, sm, want_m ? wm : nullptr, c == 0,
+                                            ctx->stream));
+            }
+            double *mean_c = mean ? mean + r0 * d : (want_m ? wm : nullptr);
+            HIP_TRY(launch_mix_loo_finish(part.X, d, d, part.n, mx, sm, wm, mean_c, llks ? llks + r0 : nullptr, ctx->n_cu, ctx->stream));
+            if (var)
+                for (int c = 0; c < nm; ++c) {
+                    if (int rc = loo_part(ctx, &part, models[c], states, covs, m, v, ell, nullptr)) return rc;
+                    HIP_TRY(launch_mix_loo_var(part.X, d, d, part.n, lpc, c, nm, m, v, ell, mx, mean_c, var + r0 * d, c == 0,
+                                               ctx->stream));
+                }
+        }
+    }
+    if (int rc = loo_totals(ctx, ds, llks, total_host, per_sample_host)) return rc;
+    if (mean_out) *mean_out = md.release();
+    if (var_out) *var_out = vd.release();
     return PPCA_OK;
 }
 

@@ -248,6 +248,23 @@ hipError_t launch_posterior_draw(const double *X, int64_t ldx, int d, int k, int
 hipError_t launch_mix_choose(const double *logpost, int64_t n, int nm, uint64_t seed, int64_t row_offset, int *choice,
                              hipStream_t s);
 
+// leave-one-out predictive (ppca_loo.hip): for rows [0, n_rows) of a chunk with their posterior means / covariances
+// (states, covs), the predictive of every entry given the row's other observed entries -- mean, var (nullable, n_rows x d), the
+// per-entry log-densities ell (nullable, n_rows x d, 0 on masked entries) and their row sums llks (nullable, n_rows).
+size_t loo_lds_bytes(int k);
+hipError_t launch_loo(const double *X, int64_t ldx, int d, int k, int64_t n_rows, const double *model, const double *states,
+                      const double *covs, double *mean, double *var, double *ell, double *llks, int n_cu, hipStream_t s);
+// The mixture's combination over a chunk (logpost: the chunk's rows of the n x nm log posteriors): fold component c's mean m and ell
+// into mx, sm, wm (wm nullable: no mean wanted); finish: L into mx on observed entries, the mean into mean (nullable, may alias wm),
+// llks (nullable); var: the second sweep, var (+)= a_cj (v_cj + (m_cj - mean_j)^2).
+hipError_t launch_mix_loo_fold(const double *X, int64_t ldx, int d, int64_t n_rows, const double *logpost, int c, int nm,
+                               const double *m, const double *ell, double *mx, double *sm, double *wm, int first, hipStream_t s);
+hipError_t launch_mix_loo_finish(const double *X, int64_t ldx, int d, int64_t n_rows, double *mx, const double *sm, const double *wm,
+                                 double *mean, double *llks, int n_cu, hipStream_t s);
+hipError_t launch_mix_loo_var(const double *X, int64_t ldx, int d, int64_t n_rows, const double *logpost, int c, int nm,
+                              const double *m, const double *v, const double *ell, const double *L, const double *mean, double *var,
+                              int first, hipStream_t s);
+
 // mixture helpers
 // llk: [n_models][n]; logw: [n_models]; w nullable.  Writes u: [n_models][n] =
 // ln w_i + log posterior_ic (-inf when w_i <= 0) and lse[n] (mixture llk per sample).

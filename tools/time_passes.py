@@ -1,6 +1,7 @@
 """Times the output passes that share the per-sample core with the EM pass (llk, llks, infer, smooth,
-extrapolate, covariance diagonal, posterior sample / impute) through the public API, device-resident inputs (diagnostic);
-then the host posterior sampler (infer + numpy) on a slice of at most 1 M rows."""
+extrapolate, covariance diagonal, posterior sample / impute, leave-one-out predictive) through the public API, device-resident inputs (diagnostic);
+then the host posterior sampler (infer + numpy) on a slice of at most 1 M rows.  `--mix NM` adds the mixture's leave-one-out
+predictive over NM components next to its extrapolated covariance diagonal."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -48,6 +49,15 @@ def psample(mode):
     L.ppca_dataset_free(o)
 timed("posterior sample", lambda: psample(0), 16 * d)
 timed("posterior impute", lambda: psample(1), 16 * d)
+def loo(full):
+    mo, vo, tot = C.c_void_p(), C.c_void_p(), C.c_double()
+    _lib.check(L.ppca_loo_predictive(ctx.handle, ds._h, md.h, C.byref(mo) if full else None, C.byref(vo) if full else None,
+                                     C.byref(tot), None))
+    if full:
+        L.ppca_dataset_free(mo)
+        L.ppca_dataset_free(vo)
+timed("loo predictive (2 N x d out)", lambda: loo(True), 24 * d)
+timed("loo llks only", lambda: loo(False), 8 * d)
 nn = min(n, 1_000_000)
 sub = ds._slice(0, nn)
 st, cv = np.empty((nn, k)), np.empty((nn, k, k))
@@ -63,3 +73,23 @@ o = C.c_void_p()
 _lib.check(L.ppca_posterior_sample(ctx.handle, hs._h, md.h, 0, 7, 0, C.byref(o))); t5 = time.perf_counter()
 L.ppca_dataset_free(o)
 print(f"host posterior sampler ({nh} rows: infer + numpy + upload) {1e3*(t4-t3):8.2f} ms   device posterior sample, same rows {1e3*(t5-t4):8.2f} ms")
+if "--mix" in sys.argv:  # the mixture's leave-one-out predictive over nm components of state size k (perturbed copies of m)
+    nm = int(sys.argv[sys.argv.index("--mix") + 1])
+    rng = np.random.default_rng(4)
+    mix = P.PPCAMix([P.PPCAModel(m.isotropic_noise * (1 + 0.1 * c_), m.transform + 0.1 * rng.standard_normal((d, k)), m.mean)
+                     for c_ in range(nm)], np.full(nm, -np.log(nm)))
+    devs, arr = mix._handles(ctx)
+    def mloo(full):
+        mo, vo, tot = C.c_void_p(), C.c_void_p(), C.c_double()
+        _lib.check(L.ppca_mix_loo_predictive(ctx.handle, ds._h, arr, _lib.ptr(mix._lw), nm, C.byref(mo) if full else None,
+                                             C.byref(vo) if full else None, C.byref(tot), None))
+        if full:
+            L.ppca_dataset_free(mo)
+            L.ppca_dataset_free(vo)
+    def mrecon(mode):
+        o = C.c_void_p()
+        _lib.check(L.ppca_mix_reconstruct(ctx.handle, ds._h, arr, _lib.ptr(mix._lw), nm, mode, C.byref(o)))
+        L.ppca_dataset_free(o)
+    timed(f"mix({nm}) extrap cov diagonal", lambda: mrecon(3), 16 * d, reps=2)
+    timed(f"mix({nm}) loo predictive", lambda: mloo(True), 24 * d, reps=2)
+    timed(f"mix({nm}) loo llks only", lambda: mloo(False), 8 * d, reps=2)
