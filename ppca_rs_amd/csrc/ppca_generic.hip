@@ -2838,15 +2838,18 @@ static hipError_t launch_gemm(GemmArgs g, hipStream_t s, int n_cu = 256, double 
 
 static size_t solve_lds(int k) { return sizeof(double) * 2 * (size_t)(2 * k * (k | 1) + 64); }
 
+// hipFuncSetAttribute is per device: each device gets the attribute once, at the size of the largest k (64) this kernel serves.
 static hipError_t set_solve_lds(int k) {
-    static size_t cur = 0;
-    const size_t need = solve_lds(k);
-    if (need > cur) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-        if (e != hipSuccess) return e;
-        cur = need;
-    }
+    if (solve_lds(k) <= 65536) return hipSuccess;
+    static std::atomic<unsigned long long> done{0ull};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)solve_lds(64));
+    if (e != hipSuccess) return e;
+    done.fetch_or(bit, std::memory_order_release);
     return hipSuccess;
 }
 
@@ -3240,12 +3243,18 @@ hipError_t generic_finalize(int k, int d, const double *stats, const double *mod
         hipLaunchKernelGGL(gen_finalize_misc_kernel, dim3(1), dim3(256), 0, s, stats, model_in, model_out, d, k, has_ig, alpha, beta);
         return hipGetLastError();
     }
-    const size_t lds = sizeof(double) * 2 * (size_t)(k * (k | 1) + 64);
-    static size_t cur = 0;
-    if (lds > cur) {
-        GTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&gen_rowsolve_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        cur = lds;
+    const auto rowsolve_lds = [](int kk) { return sizeof(double) * 2 * (size_t)(kk * (kk | 1) + 64); };
+    const size_t lds = rowsolve_lds(k);
+    if (lds > 65536) {  // (k = 64: 67,584 B) per device, as set_solve_lds
+        static std::atomic<unsigned long long> done{0ull};
+        int dev = 0;
+        GTRY(hipGetDevice(&dev));
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (!(done.load(std::memory_order_acquire) & bit)) {
+            GTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&gen_rowsolve_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowsolve_lds(64)));
+            done.fetch_or(bit, std::memory_order_release);
+        }
     }
     int grid = std::min((d + 1) / 2, n_cu * 2);
     hipLaunchKernelGGL(gen_rowsolve_kernel, dim3(grid), dim3(128), lds, s, stats, model_in, model_out, d, k, tau);

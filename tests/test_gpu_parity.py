@@ -1473,7 +1473,8 @@ def test_multi_component_step_equals_component_by_component(oracle, tmp_path):
     HBM once; selection, reduction + verdict, finalisation + next slice tables with blockIdx.y = component).  Against the
     component-by-component form of rounds 2-5 (PPCA_MIX_MULTI=0) in a child process each: the llks are BIT-identical (same per-sample
     arithmetic), and so are the new models (same row lists, weights and partial statistics per component); the log-weights and the
-    llk total differ only by the order of two sums.  The case with a component outside the int8 Gram's dynamic range must take that
+    llk total differ only by the order of two sums -- under a tau + inverse-gamma prior too (k3_prior: finalize_qprep_multi_kernel
+    against finalize_kernel).  The case with a component outside the int8 Gram's dynamic range must take that
     component's llks from the fp64 instantiation (engine 1) and agree with the oracle."""
     import subprocess
     import sys
@@ -1487,7 +1488,7 @@ def test_multi_component_step_equals_component_by_component(oracle, tmp_path):
         assert r.returncode == 0 and "mix multi check written" in r.stdout, (flag, r.stdout[-1500:], r.stderr[-2500:])
         outs.append(np.load(path))
     multi, single = outs
-    for case in ("k8", "k8_grid8", "k3_grid2", "k3_grid16", "k16"):
+    for case in ("k8", "k8_grid8", "k3_grid2", "k3_grid16", "k16", "k3_prior"):
         np.testing.assert_array_equal(multi[case + "_llks"], single[case + "_llks"], err_msg=case)
         np.testing.assert_array_equal(multi[case + "_lp"], single[case + "_lp"], err_msg=case)
         np.testing.assert_array_equal(multi[case + "_c"], single[case + "_c"], err_msg=case)

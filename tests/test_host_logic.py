@@ -45,6 +45,30 @@ def test_finalize_host_with_priors(oracle, hiplib):
     np.testing.assert_allclose(new.isotropic_noise, s1, rtol=1e-10)
     np.testing.assert_allclose(new.transform, c1, rtol=1e-8, atol=1e-12)
     np.testing.assert_allclose(new.mean, m1, rtol=1e-8, atol=1e-12)
+    # each hook alone, at state sizes of every finalisation kernel (fused, generic, beyond 64), against the oracle's step: the host
+    # finalisation is the reference of tests/test_gpu_priors.py.  Dimension 7 is fully masked: with tau = 0 its system is singular
+    # and the old row is kept, with tau > 0 it is tau I and the row becomes exactly 0 (ppca_model.rs:307-321)
+    for k in (1, 10, 16, 64, 100):
+        x, s, c, mu, w = _case(oracle, n=150, d=20, k=k, seed=10 + k)
+        x[:, 7] = np.nan
+        pm, pc = np.linspace(-1, 1, 20), 0.5 * np.eye(20) + 0.1
+        st = oracle.stats(x, s, c, mu, w)
+        for kw in ({}, {"transformation_precision": 0.7}, {"transformation_precision": 1e8},
+                   {"isotropic_noise_alpha": 3.0, "isotropic_noise_beta": 2.0}, {"isotropic_noise_alpha": 0.0, "isotropic_noise_beta": 0.0},
+                   {"mean": pm, "mean_covariance": pc}):
+            prior = Prior().with_transformation_precision(kw.get("transformation_precision", 0.0))
+            if "isotropic_noise_alpha" in kw:
+                prior = prior.with_isotropic_noise_prior(kw["isotropic_noise_alpha"], kw["isotropic_noise_beta"])
+            if "mean" in kw:
+                prior = prior.with_mean_prior(pm, pc)
+            new = finalize_host(PPCAModel(s, c, mu), st, prior)
+            s1, c1, m1 = oracle.iterate(x, s, c, mu, w, oracle.Prior(**kw))
+            np.testing.assert_allclose(new.isotropic_noise, s1, rtol=1e-10, err_msg=str((k, kw)))
+            np.testing.assert_allclose(new.transform, c1, rtol=1e-8, atol=1e-10 * np.abs(c1).max(), err_msg=str((k, kw)))
+            np.testing.assert_allclose(new.mean, m1, rtol=1e-8, atol=1e-12, err_msg=str((k, kw)))
+            row = np.zeros(k) if kw.get("transformation_precision", 0.0) > 0.0 else c[7]
+            np.testing.assert_array_equal(new.transform[7], row, err_msg=str((k, kw)))
+            np.testing.assert_array_equal(c1[7], row, err_msg=str((k, kw)))
 
 
 def test_empty_dimension_keeps_old_row(oracle, hiplib):

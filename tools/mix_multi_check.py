@@ -6,8 +6,10 @@ finalise launches with blockIdx.y = component) against the component-by-componen
 Writes the mixture llks / log posteriors of the start mixture and the models, log-weights and llk trace of a few EM iterations for a
 list of cases; tests/test_gpu_parity.py::test_multi_component_step_equals_component_by_component runs it twice and compares.  Cases:
 K = 8 at d = 256, k = 10 (weighted rows, an all-masked row, a zero weight); K = 3 at d = 40, k = 3 on a grid capped at 2 and at 16
-workgroups (several (component, run) units per workgroup); K = 16 at k = 1; one component whose transform trips the dynamic-range
-guard of the int8 Gram (rows spanning 1e8, the large ones masked in every sample): its llks come from the fp64 instantiation."""
+workgroups (several (component, run) units per workgroup); the same K = 3 with a transformation precision and an inverse-gamma noise
+prior (finalize_qprep_multi_kernel against finalize_kernel under the prior); K = 16 at k = 1; one component whose transform trips the
+dynamic-range guard of the int8 Gram (rows spanning 1e8, the large ones masked in every sample): its llks come from the fp64
+instantiation."""
 import os
 import sys
 
@@ -37,7 +39,7 @@ def make(rng, d, k, nm, n, mask=0.3, weights=True):
     return x, w, start
 
 
-def run(name, x, w, start, steps, out, grid_limit=0):
+def run(name, x, w, start, steps, out, grid_limit=0, prior=None):
     ctx = _lib.default_context()
     ctx.set_grid_limit(grid_limit)
     ds = P.Dataset(x, w) if w is not None else P.Dataset(x)
@@ -45,7 +47,7 @@ def run(name, x, w, start, steps, out, grid_limit=0):
     out[name + "_lp"] = start.infer_cluster(ds)
     mix, trace = start, []
     for _ in range(steps):
-        mix, llk = mix.iterate_with_llk(ds)
+        mix, llk = mix.iterate_with_llk(ds, prior)
         trace.append(llk)
     out[name + "_trace"] = np.array(trace)
     out[name + "_sigma"] = np.array([m.isotropic_noise for m in mix.models])
@@ -64,6 +66,7 @@ def main():
     x, w, start = make(rng, 40, 3, 3, 3001)
     run("k3_grid2", x, w, start, 3, out, grid_limit=2)
     run("k3_grid16", x, w, start, 2, out, grid_limit=16)
+    run("k3_prior", x, w, start, 3, out, prior=P.Prior().with_isotropic_noise_prior(3.0, 2.0).with_transformation_precision(0.7))
     x, w, start = make(rng, 64, 1, 16, 2000, weights=False)
     run("k16", x, w, start, 2, out)
     # one component outside the int8 Gram's dynamic range (test_int8_gram_dynamic_range_guard (a)): rows of C spanning 1e8, the large
