@@ -849,7 +849,7 @@ static int em_accumulate_impl(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model 
     g.d = a.d;
     g.grid = grid;
 #ifdef PPCA_PHASE_TIMING
-    BufRef dbg;  // [grid][16] phase sums of one thread per role, then [grid][8 waves][16] per-wave sums (em8_kernel)
+    BufRef dbg;  // [grid][16] phase sums of one thread per role, then [grid][8 waves][16] per-wave sums (em9_kernel)
     if (int rc = dev_alloc(sizeof(double) * (size_t)grid * 144, &dbg)) return rc;
     HIP_TRY(hipMemsetAsync(dbg->p, 0, sizeof(double) * (size_t)grid * 144, ctx->stream));
     a.dbg = static_cast<double *>(dbg->p);
@@ -898,7 +898,7 @@ static int em_accumulate_impl(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model 
                 double tw[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
                 for (int g = 0; g < grid; ++g)
                     for (int i = 0; i < 16; ++i) tw[i] += h[(size_t)grid * 16 + ((size_t)g * 8 + w) * 16 + i] / grid;
-                fprintf(stderr, "[em8 wave %d cycles/tile]", w);
+                fprintf(stderr, "[em9 wave %d cycles/tile]", w);
                 for (int i = 0; i < (w < 4 ? 16 : 4); ++i) fprintf(stderr, " %s %.0f", w < 4 ? fn[i] : bn[i], tw[i] / tl);
                 fprintf(stderr, "\n");
             }
@@ -915,7 +915,7 @@ static int em_accumulate_impl(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model 
                 (t[4] + t[6]) / tiles, t[7] / tiles, t[3] / tiles, tiles);
         fprintf(stderr, "[ppca P4b int8 cycles/tile] staging %.0f  digitise %.0f  contraction + barriers + stores %.0f\n", t[5] / tiles, t[15] / tiles, t[7] / tiles);
         // (the eight-wave kernel writes slots 8..15; the four-wave kernel's slots 0..7 are then its idle instantiation's)
-        fprintf(stderr, "[em8 cycles/tile] front: P2 compute %.0f  wait back + stores + barrier %.0f  P3 %.0f  wg barrier + P4a + barrier %.0f  staging + barrier %.0f"
+        fprintf(stderr, "[em9 cycles/tile] front: P2 compute %.0f  wait back + stores + barrier %.0f  P3 %.0f  wg barrier + P4a + barrier %.0f  staging + barrier %.0f"
                         " | back: wait at wg barrier %.0f  digitise + barrier %.0f  contraction / flush %.0f\n",
                 t[8] / tiles, t[9] / tiles, t[10] / tiles, t[11] / tiles, t[12] / tiles, t[13] / tiles, t[14] / tiles, t[15] / tiles);
     }
@@ -2203,15 +2203,7 @@ extern "C" int ppca_debug_counters(ppca_ctx *ctx, int64_t *out8, int32_t reset) 
     if (!ctx || !out8) return fail(PPCA_ERR_INVALID, "null argument");
     USE_CTX(ctx);
     unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIP_TRY(em8_debug_counters(c, reset, ctx->stream));
-    {  // (PPCA_EM9=1: the pipelined-solve variant keeps its own; reported in the same slots)
-        unsigned long long c9[4] = {0, 0, 0, 0};
-        HIP_TRY(em9_debug_counters(c9, reset, ctx->stream));
-        c[0] += c9[0];
-        c[1] += c9[1];
-        c[2] = std::max(c[2], c9[2]);
-        c[3] += c9[3];
-    }
+    HIP_TRY(em9_debug_counters(c, reset, ctx->stream));
     HIP_TRY(em16_debug_counters(c + 4, reset, ctx->stream));
     for (int i = 0; i < 8; ++i) out8[i] = (int64_t)c[i];
     return PPCA_OK;

@@ -34,14 +34,10 @@ struct Cfg {
     // once-per-tile values in scratch and reloads them with an exposed vmcnt(0)):
     // sq[NW <= 8 waves][B] | dev[B] | llk[B] | sumw[B] | nonempty[B] | det mantissa[B] | det exponent[B]
     static constexpr int OFF_L = OFF_S + 2 * B;
-    // int8 form of the mask-side statistics contraction (pass_kernel, P4I8): the second K-half of b moves out of the
-    // second [G | b] buffer (which then holds a tile's digit planes) into P1 [B][K + 1]; column exponents of the
-    // group's two tiles (2 x 16 NTM ints) and a flag word follow.  The per-dimension sample masks of a group
-    // (256 x u64) live in the part of the L region that only the 8-wave variant uses.
-    static constexpr int OFF_P1 = OFF_L + 22 * B;  // (sq has two slots per solver sample when the waves pair lanes)
-    static constexpr int OFF_E = OFF_P1 + B * (K + 1);
-    static constexpr int LDS_DOUBLES = OFF_E + 16 * NTM + 2;
-    static constexpr int OFF_MB = OFF_L + 14 * B;  // 4 waves use L[0 .. 14 B); 256 u64 fit in [14 B, 22 B)
+    // L takes [0, 14 B) (sq has two slots per solver sample when the waves pair lanes).  The B (8 + K + 1) + 16 NTM + 2 doubles behind
+    // it were the regions of the four-wave int8 form of the mask-side statistics contraction (removed): no kernel touches them, and
+    // they stay in the size so that every launch asks for exactly the LDS it was measured with.
+    static constexpr int LDS_DOUBLES = OFF_L + 22 * B + B * (K + 1) + 16 * NTM + 2;
     static_assert(K > FUSED_MAX_K || LDS_DOUBLES * 8 <= 160 * 1024, "LDS budget");  // (k > 10: only KP / NTP are used, by qprep_kernel)
 };
 
@@ -178,29 +174,13 @@ constexpr int QB = 8;
 constexpr int QBASE = 1 << QB;
 typedef int i4_t __attribute__((ext_vector_type(4)));
 
-// Seven independent v_mfma_i32_16x16x64_i8 (one A operand, seven B operands, C = 0) with the results in VGPRs: the
-// builtin's results land in accumulation registers, and under this kernel's register pressure all seven shared one
-// quad -- every MFMA waited for the previous result to be copied out.  The trailing s_nops cover the read-after-MFMA
-// wait states of the last result (the compiler does not see inside the statement); the leading s_nop 1 covers a VALU
-// write of an A / B operand register by the instruction just before the statement (hipcc pads nothing across the
-// boundary: seen as plane-0 digit sums of the first block contracted under a half-written mask operand, 1e-10 of S, in
-// ppca_em16.hip's instantiations for k = 11..15).
-__device__ __forceinline__ void mfma_i8_x7(const i4_t &a, const i4_t (&b)[7], i4_t (&d)[7]) {
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_i32_16x16x64_i8 %0, %7, %8, 0\n\t"
-        "v_mfma_i32_16x16x64_i8 %1, %7, %9, 0\n\t"
-        "v_mfma_i32_16x16x64_i8 %2, %7, %10, 0\n\t"
-        "v_mfma_i32_16x16x64_i8 %3, %7, %11, 0\n\t"
-        "v_mfma_i32_16x16x64_i8 %4, %7, %12, 0\n\t"
-        "v_mfma_i32_16x16x64_i8 %5, %7, %13, 0\n\t"
-        "v_mfma_i32_16x16x64_i8 %6, %7, %14, 0\n\t"
-        "s_nop 7"
-        : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6])
-        : "v"(a), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]));
-}
-
-// Three / one independent v_mfma_i32_16x16x64_i8 with a shared A operand (C = 0), results in VGPRs (see mfma_i8_x7).
+// Three / one independent v_mfma_i32_16x16x64_i8 with a shared A operand (C = 0) and the results in VGPRs: the builtin's
+// results land in accumulation registers, and under these kernels' register pressure they all shared one quad -- every MFMA
+// waited for the previous result to be copied out.  The trailing s_nops cover the read-after-MFMA wait states of the last
+// result (the compiler does not see inside the statement); the leading s_nop 1 covers a VALU write of an A / B operand
+// register by the instruction just before the statement (hipcc pads nothing across the boundary: seen as plane-0 digit sums
+// of the first block contracted under a half-written mask operand, 1e-10 of S, in ppca_em16.hip's instantiations for
+// k = 11..15).
 __device__ __forceinline__ void mfma_i8_x3(const i4_t &a, const i4_t &b0, const i4_t &b1, const i4_t &b2, i4_t &d0, i4_t &d1, i4_t &d2) {
     asm volatile(
         "s_nop 1\n\t"

@@ -3,12 +3,12 @@
 //
 //   estep16_kernel<K>   one sweep over X: staging (centring, masks), [G | b] (int8-sliced Gram + fp64-MFMA b = X~ C),
 //                       the per-sample k x k solve, the x~-side statistics cross / sumx, the scalars and the llk --
-//                       the front role of em8_kernel (ppca_em8.hip) as its own four-wave workgroup with the whole
+//                       the front role of em9_kernel (ppca_em9.hip; here every wave solves every sample) as its own four-wave workgroup with the whole
 //                       512-entry register file per wave; from k = 14 the packed Cholesky factor (210+ registers) is split
 //                       over lane pairs and parked in LDS for the substitutions (SplitChol, solve_lds, minv_pair_lds);
 //                       writes each sample's row [wP (k') | wz (k) | w] (fp64) and the tile's per-dimension sample masks
 //   sstat16_kernel<K>   S / U / totals (256 x (k' + k + 1)) += Mask^T [wP | wz | w] on the INT8 MFMA with exact 64-bit
-//                       integer accumulation: the back role of em8_kernel as its own eight-wave workgroup (each wave owns
+//                       integer accumulation: the back role of em9_kernel as its own eight-wave workgroup (each wave owns
 //                       32 dimensions x all columns: 160 accumulator registers at k = 16), rows staged from HBM
 //
 // Why two kernels: at k = 16 the mask-side statistics are 256 x 153 columns -- 320 accumulator registers per wave of a
@@ -18,13 +18,12 @@
 // ppca_generic.hip (ten launches per chunk, X read four times): 14.5 ms per iteration at d = 200, k = 16, N = 2 M;
 // here 6.7 ms (profiles/r03/cliff.md).
 //
-// Fixed-point form, violation handling and flush cadence of the contraction: exactly as in ppca_em8.hip (one exponent
+// Fixed-point form, violation handling and flush cadence of the contraction: exactly as in ppca_em9.hip (one exponent
 // per column and workgroup, set by the first tile + 6 binary orders of head room; a tile that does not fit flushes the
 // integers and raises the exponents).
 //
 // Replaces in the reference: infer (ppca/src/ppca_model.rs:221-227), the cross moment (:281-293), the d second-moment
 // scans (:294-306), the noise 4-tuple (:328-358) and llk (:142-149), for 11 <= k <= 16.
-#include <atomic>
 #include <cstdlib>
 
 #include "ppca_device.hpp"
@@ -60,7 +59,7 @@ struct Cfg16 {
     static constexpr int NCT = (NC + 15) / 16;
     static constexpr int NCOL = 16 * NCT;        // row stride of the hand-over buffer (doubles)
     // ---- estep16_kernel
-    // [G | b] and the [wP | wz | w] rows share ONE buffer (row stride GS), as in em8_kernel:
+    // [G | b] and the [wP | wz | w] rows share ONE buffer (row stride GS), as in em9_kernel:
     //   as [G | b]:  G (16 NTP, K' used) | b partial of dims 0-127 (16) | pad
     //   as W row:    wP (K') | wz (K) | w | ..      (compact: the hand-over buffer's row)
     static constexpr int GS = 16 * NTP + 18;
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 dst[u][kc] = i4_t{(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
             }
     };
-    // ---- P1: as em8_kernel (the finite-test ballots ARE the mask words; each lane shifts its own bit of every ballot
+    // ---- P1: as em9_kernel (the finite-test ballots ARE the mask words; each lane shifts its own bit of every ballot
     // into st_mb: byte = this dimension over the wave's eight samples, row r at bit 7 - r); sumx rides along on the
     // vector unit (four multiply-adds per row: the sixteen columns of the cross product's MFMA tile are all wz at k = 16)
     double mu[4], lim[4];
@@ -688,7 +687,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // lane: a lane-per-sample factorisation ran on register-file copies (9 x the arithmetic).  Here the lane pair
         // (i, i + 32) holds the factor column-cyclically (SplitChol: 72 doubles each) and exchanges the pivot column
         // per step; the finished factor goes to its own LDS buffer, and the substitutions -- z in every wave, the
-        // columns of M^-1 shared by the waves, two per instruction stream as in em8_kernel -- read it from there
+        // columns of M^-1 shared by the waves, two per instruction stream as in em9_kernel -- read it from there
         // (same address in both halves: one broadcast read), writing the W rows over the Gram as they go.
         {
             const double s2 = sm[cfg::OFF_K], inv_s2 = sm[cfg::OFF_K + 1], lnsig = sm[cfg::OFF_K + 2];
@@ -925,7 +924,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // ===================================================================== mask-side statistics
-// Diagnostic counters as in ppca_em8.hip: [0] rescales beyond a workgroup's first, [1] periodic flushes, [2] the largest
+// Diagnostic counters as in ppca_em9.hip: [0] rescales beyond a workgroup's first, [1] periodic flushes, [2] the largest
 // number of tiles one workgroup walked, [3] workgroups whose statistics were recomputed in fp64 (rounding check).
 __device__ unsigned long long e16_counters[4];
 
@@ -1092,8 +1091,8 @@ __global__ __launch_bounds__(512) void sstat16_kernel(S16Args p) {
     auto emit = [&](int lane, bool accumulate, bool clear) {
         asm volatile("" : "+v"(lane));
         const int l15 = lane & 15, l4 = lane >> 4;
-        // The rounding check of this flush window (the guard of the fixed-point form; em8_kernel's is global, behind
-        // wguard_kernel -- here it is per workgroup and window, conservative): a row far above its neighbours lifts the column
+        // The rounding check of this flush window (the guard of the fixed-point form; em9_kernel's is global, behind
+        // reduce_wguard_kernel -- here it is per workgroup and window, conservative): a row far above its neighbours lifts the column
         // exponents, and a dimension masked in that row sums rows cut far below their resolution.  A diagonal column of S
         // (non-negative terms) of a dimension observed in the window must hold at least 2^34 x the rounding bound
         // 4 sqrt(rows) quanta; otherwise the workgroup's statistics are recomputed in fp64 by sstat16_fallback_kernel.
@@ -1143,7 +1142,7 @@ __global__ __launch_bounds__(512) void sstat16_kernel(S16Args p) {
     };
 
     // ---- one contraction: the group in [P0 | P1] (both == false: P0 alone), sample masks of slots slot_first /
-    // slot_second; digit sums folded into the int64 accumulators (as em8_kernel's)
+    // slot_second; digit sums folded into the int64 accumulators
     auto contract = [&](int lane, bool both, int slot_first, int slot_second) {
         asm volatile("" : "+v"(lane));
         const int l15 = lane & 15, l4 = lane >> 4, lh = l4 >> 1;
@@ -1333,18 +1332,6 @@ hipError_t em16_debug_counters(unsigned long long *out4, int reset, hipStream_t 
 }
 
 // ------------------------------------------------------------------ launchers
-template <class Kern>
-static hipError_t set_lds_once(Kern kern, size_t lds, std::atomic<unsigned long long> &done) {
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-    return hipSuccess;
-}
-
 template <int K>
 static hipError_t launch_em16_t(int grid, const Em16Launch &a, hipStream_t s) {
     using cfg = Cfg16<K>;
@@ -1352,18 +1339,17 @@ static hipError_t launch_em16_t(int grid, const Em16Launch &a, hipStream_t s) {
     // the caller's guarded launch, see ppca_generic.hip)
     const Em16Launch &e = a;
     const size_t lds_e = sizeof(double) * cfg::LDS_DOUBLES, lds_s = sizeof(double) * cfg::S_LDS_DOUBLES;
-    static std::atomic<unsigned long long> done_w{0ull}, done_u{0ull}, done_s{0ull};
     if (a.w) {
-        if (hipError_t er = set_lds_once(&estep16_kernel<K, true>, lds_e, done_w); er != hipSuccess) return er;
+        if (hipError_t er = ensure_dynamic_lds<estep16_kernel<K, true>>(lds_e); er != hipSuccess) return er;
         hipLaunchKernelGGL((estep16_kernel<K, true>), dim3(grid), dim3(256), lds_e, s, e);
     } else {
-        if (hipError_t er = set_lds_once(&estep16_kernel<K, false>, lds_e, done_u); er != hipSuccess) return er;
+        if (hipError_t er = ensure_dynamic_lds<estep16_kernel<K, false>>(lds_e); er != hipSuccess) return er;
         hipLaunchKernelGGL((estep16_kernel<K, false>), dim3(grid), dim3(256), lds_e, s, e);
     }
     if (hipError_t er = hipGetLastError(); er != hipSuccess) return er;
     S16Args b{};
     b.Wrows = a.Wrows; b.Mb = a.Mb; b.n = a.n; b.d = a.d; b.part = a.part;
-    if (hipError_t er = set_lds_once(&sstat16_kernel<K>, lds_s, done_s); er != hipSuccess) return er;
+    if (hipError_t er = ensure_dynamic_lds<sstat16_kernel<K>>(lds_s); er != hipSuccess) return er;
     hipLaunchKernelGGL((sstat16_kernel<K>), dim3(grid), dim3(512), lds_s, s, b);
     if (hipError_t er = hipGetLastError(); er != hipSuccess) return er;
     hipLaunchKernelGGL((sstat16_fallback_kernel<K>), dim3(grid), dim3(256), 0, s, b);  // (returns at once unless the check failed)

@@ -1,31 +1,67 @@
-// ppca_em9.hip -- the EM pass of ppca_em8.hip (eight-wave workgroup, two roles: fp64 front, int8 statistics contraction in
-// the back) with the per-sample SOLVE PIPELINED ACROSS TILES (round 4; the default EM kernel, PPCA_EM9=0 selects em8_kernel):
+// ppca_em9.hip -- the EM pass (E-step + every M-step reduction in ONE sweep over X, as pass_kernel) as an EIGHT-wave
+// workgroup, two waves per SIMD, with two roles and the per-sample solve pipelined across tiles (the default EM kernel
+// for d <= 256, k <= 10):
 //
-//   em8_kernel    every front wave factors every sample of the tile and solves for z (260 + 130 vector instructions on each
-//                 of the four waves), then the waves share the columns of M^-1.  The redundancy is free in time -- the waves
-//                 run in lockstep -- but the solve sits on every wave's chain: load, factor, solve, columns, scalars =
-//                 4.7 k of a tile's ~20 k cycles.
-//   em9_kernel    ONE front wave (rotating with the tile) factors tile t, solves for z and writes the factor, z and the
-//                 [wz | w] part of the W rows back into the tile's [G | b] buffer, while the OTHER THREE form the columns
-//                 of M^-1 and the wP part of the W rows of tile t - 1 from the factor its solver left there one tile
-//                 earlier.  The two activities take about the same time (~3 k cycles), so the chain of a tile loses
-//                 ~1.7 k cycles, and three of four waves skip the factorisation (1 400 vector instructions per tile).
-//                 What it needs: the [G | b] / factor / W-row buffer TWICE (tile parity) -- the 21 KB come from the C tile,
-//                 whose B operands of b = X~ C are read from a zero-padded copy of C in global memory instead (measured
-//                 alone: - 2.3 %) --, the back role one tile later (the W rows of tile t - 1 are final after phase beta of
-//                 tile t: the roles meet through LDS counters only, as in em8's E8_DECOUPLED form) and the per-dimension
-//                 sample masks four tiles deep.
+//   front waves 0-3   P1 staging of a tile's rows, P2 [G | b] (int8-sliced Gram + b = X~ C on v_mfma_f64_4x4x4), phase beta:
+//                     the per-sample k x k solve, P4a the x~-side statistics cross / sumx on the fp64 MFMA
+//   back waves 4-7    P4b: S / U / totals (256 x 66) += Mask^T [wP | wz | w] on the INT8 MFMA: rows of [wP | wz | w] cut
+//                     into seven signed bytes of a fixed-point form, 64 samples (two tiles) per v_mfma_i32_16x16x64_i8,
+//                     the group's exact digit sums recombined into 24-bit pieces and added to fp64 accumulators
 //
-// Everything else -- staging, [G | b], the fixed-point form of the back role and its guard, the cross product, the
-// epilogue -- is em8_kernel's, statement for statement; see ppca_em8.hip for the description.
+// Why this split (round 3):  v_mfma_f64 shares the SIMD's vector port with every other vector
+// instruction of every wave (tools/ubench_shadow.hip), and P4b was 8.8 k of a tile's 13.9 k fp64-MFMA cycles.  With
+// one exact operand (the 0/1 mask) P4b does not need the fp64 pipe at all: on the int8 MFMA it is 70 x 16 cycles of
+// the MATRIX pipe per tile plus ~700 integer vector instructions (digit cutting, recombination) -- work that leaves
+// the fp64 port alone and so can run on the second wave of each SIMD in the gaps of the front role's dependent fp64
+// chains (the Cholesky pivots, LDS operand waits).  The round-2 role split failed because its second role WAS fp64
+// MFMAs; the round-2 int8 P4b failed because it ran on the same wave as everything else.  Registers: the back role
+// holds the 160 accumulator registers and nothing of the solver; the front role holds the solver and none of the
+// mask-side accumulators: both fit 256.
 //
-// Round 5 ("layout B", E9_CLDS=1, the default): b = X~ C runs on v_mfma_f64_4x4x4 -- the instruction's four blocks are (two groups
-// of four dimensions) x (two groups of four samples), so one MFMA covers 8 samples x 4 columns x 8 dimensions and K = 10 columns
-// are three groups of four -- with the C^T operands of the first two column groups RESIDENT IN LDS in operand order; the 16 KB
-// for them come from the digit planes packed to their real columns, the second K-half's partial of b in the row's own free
-// slots, a 78-double row stride at k = 10, the mean re-read from L1 / L2 and a register running sum (Cfg9 below).  Measured
-// 103.5 against 100.3 EM it/s at N = 10 M; with nt row loads and the second digit pair requested one phase early 104.2-104.8.
-#include <atomic>
+// The solve, pipelined across tiles (round 4).  ONE front wave (rotating with the tile) factors tile t, solves for z and
+// writes the factor, z and the [wz | w] part of the W rows back into the tile's [G | b] buffer, while the OTHER THREE form
+// the columns of M^-1 and the wP part of the W rows of tile t - 1 from the factor its solver left there one tile earlier.
+// The two activities take about the same time (~3 k cycles).  Before that every front wave factored every sample -- free in
+// time, the waves run in lockstep, but load, factor, solve, columns, scalars were 4.7 k of a tile's ~20 k cycles on every
+// wave's chain; now the chain of a tile is ~1.7 k cycles shorter and three of four waves skip the factorisation (1 400
+// vector instructions per tile).  What it needs: the [G | b] / factor / W-row buffer TWICE (tile parity), the back role one
+// tile later (the W rows of tile t - 1 are final after phase beta of tile t) and the per-dimension sample masks four tiles
+// deep.
+//
+// b = X~ C (round 5, "layout B") runs on v_mfma_f64_4x4x4 -- the instruction's four blocks are (two groups of four
+// dimensions) x (two groups of four samples), so one MFMA covers 8 samples x 4 columns x 8 dimensions and K = 10 columns
+// are three groups of four -- with the C^T operands of the first two column groups RESIDENT IN LDS in operand order (16 KB;
+// the third from L1 / L2 through PassArgs::cpb).  The LDS for them is reclaimed at k = 10 from: digit planes packed to
+// their real columns (6.1 KB), the second K-half's partial of b in the row's own free slots instead of its own array
+// (2.8), the row stride 82 -> 78 (2), the mean re-read from L1 / L2 instead of an LDS copy (2), the per-lane running sum
+// of tr(C Sigma C^T) in a register instead of LDS (2): Cfg9 below.  Measured 103.7 against 100.3 EM it/s at N = 10 M for
+// round 4's layout (b on the 16 x 16 x 4 form, its B operands from a zero-padded copy of C in global memory); with nt row
+// loads and the second digit pair requested one phase early 104.2-104.8.
+//
+// Fixed-point form.  Column c of [wP | wz | w] has ONE exponent E_c per workgroup: I = rint(w 2^(50 - E_c)), |I| < 2^50,
+// cut by one fused multiply-add onto the magic constant 1.5 2^52 + 0x808080808080 (the mantissa then IS the biased
+// integer; xor with the constant's own bits leaves the balanced bytes).  E_c = exponent of the first tile's column
+// maximum + 6.  A later tile whose entry does not fit raises a flag (any exponent field other than 0x433 after the
+// add: too large, infinite or NaN alike); the back waves then contract what is pending under the old exponents,
+// flush the accumulators into the workgroup's partial (x 2^(E_c - 50), fp64), raise the exponents and cut the
+// tile again -- a cold path, taken once at the first tile and whenever a column outgrows its scale (a tile with only a few
+// such rows sends those rows round the form in exact fp64 adds instead: PassArgs::heavy_max).  The digit sums of a
+// group are exact; the roundings are the cut itself (<= 2^-45 of the column's first-tile maximum per entry), one fp64
+// addition per 24-bit piece and one multiplication per flush.  A non-finite column poisons its exponent: NaN reaches the
+// statistics as through fp64.  Accumulators are also flushed every 100 groups.  Whether the cut was fine enough for the
+// data at hand is checked on the REDUCED statistics by reduce_wguard_kernel (ppca_kernels.hip) from the per-column
+// rounding bounds this role reports (p.errb).
+//
+// Hand-off (all in LDS, no workgroup barrier inside the tile loop): the roles meet through monotonic LDS counters only.
+// The front leaves the tile's [wP | wz | w] rows in the buffer of the tile's parity; the back cuts them into digit planes
+// and contracts a group when its second tile is there.  The front waits on the count of tiles the back has cut before it
+// overwrites a buffer (normally long satisfied: the back's ~4 k cycles per tile sit beside ~16 k of front work).  The
+// per-dimension sample masks of the last four tiles are kept (16 bytes per dimension), so the staging of tile t + 1
+// never touches what the contraction of earlier tiles reads.
+//
+// Replaces in the reference: infer (ppca/src/ppca_model.rs:221-227), the cross moment (:281-293), the d second-moment
+// scans (:294-306), the noise 4-tuple (:328-358) and llk (:142-149) -- as pass_kernel, whose per-sample arithmetic,
+// tile order and summation orders the front role keeps (cross, sumx, the scalars and the llk are bit-identical to it).
 #include <cstdlib>
 
 #include "ppca_device.hpp"
@@ -38,65 +74,28 @@ constexpr int E9_HEAD = 6;      // binary orders kept free above the column maxi
 constexpr int E9_POISON = 100000;
 constexpr int E9_EMIN = -900, E9_EMAX = 1000;
 constexpr int E9_FLUSH_GROUPS = 100;
-#ifndef E9_BARRIER_SLEEP
-#define E9_BARRIER_SLEEP __builtin_amdgcn_s_sleep(1);
-#endif
-#ifndef E9_BACK_PRIO
-#define E9_BACK_PRIO 0
-#endif
-#ifndef E9_FRONT_PRIO
-#define E9_FRONT_PRIO 0
-#endif
-#ifndef E9_CLDS
-#define E9_CLDS 1  // 1 (round 5, "layout B"; measured 103.7 against 100.3 EM it/s, gpurun_out/r5ab4; 0: round 4's layout): b = X~ C on the 4 x 4 x 4 form with the first two column groups of C RESIDENT IN LDS (16 KB; the third
-                   // from L1 / L2), the LDS for it reclaimed at k = 10 from: digit planes packed to their real columns (6.1 KB), the second K-half
-                   // partial of b in the row's free slots instead of its own array (2.8), the row stride 82 -> 78 (2), the mean re-read from L1 / L2
-                   // instead of an LDS copy (2), the per-lane running sum of tr(C Sigma C^T) in a register instead of LDS (2)
-#endif
-#ifndef E9_B444
-#define E9_B444 E9_CLDS
-#endif
-#if E9_CLDS && !E9_B444
-#error "E9_CLDS is the 4 x 4 x 4 form of the b product"
-#endif
-// E9_B444 alone (C operands from L1 / L2): b = X~ C on v_mfma_f64_4x4x4 with the dimension and sample groups in the instruction's four blocks (round 5
-                   // experiment, parity-green).  Measured (gpurun_out/r5ab1, r5ab2, r5t1, r5t2; profiles/r05/README.md): 100.0 against
-                   // 100.7 EM it/s for the 16 x 16 x 4 form -- the loop's 96 MFMAs of 17 cycles take 2.84 k cycles per tile against
-                   // 2.70 k for 32 of 64: the 48 loads of C per wave and tile queue behind the Gram's digit-table loads (one in-order
-                   // vmcnt), deeper look-ahead changes nothing (E9_LAC=6: 99.9).  With the C operands from LDS (timing experiment
-                   // E9_EXP_CLDS, results wrong) the loop takes 2.22 k and the launch 104.8 it/s -- but LDS has 1.7 KB free where 20 KB are
-                   // needed: E9_CLDS reclaims 16 for two of the three column groups.
-#ifndef E9_B_EARLYC
-#define E9_B_EARLYC 1  // the first steps of C operands requested before the Gram's digit pairs (their L2 latency under the integer MFMAs)
-#endif
-#ifndef E9_X_AUX
-#define E9_X_AUX 2  // cache policy of the row loads of X: nt (L2-served: the rows are read once and would only push the digit table and the
-                    // third column group of C out of the 32 KB L1).  Measured on layout B, two rounds interleaved: 103.9-104.1 against
-                    // 103.2-103.4 EM it/s (round 4's layout: +0.5 %, inside the spread)
-#endif
-#ifndef E9_Q_AUX
-#define E9_Q_AUX 0  // ... and of the Gram's digit table (128 KB per tile and workgroup).  Measured with 2 (nt): 90.0 against 100.7 it/s
-#endif
-#ifndef E9_LAC
-#define E9_LAC 4
-#endif
-#ifndef E9_QB_EARLY
-#define E9_QB_EARLY 1  // the second digit pair {5,4} requested with {7,6} during the previous tile's P4a.  On round 4's layout it only moved the
-                       // wait (first half of the Gram 2.40 -> 2.12 k cycles per tile, b loop 2.70 -> 2.87 k: 100.7 against 100.8 it/s); on layout
-                       // B, whose b loop waits for 16 instead of 48 loads, + 0.3 % (with nt row loads 104.2-104.4 against 103.2-103.4)
-#endif
-#ifndef E9_HEAVY_BUDGET
-#define E9_HEAVY_BUDGET 8  // tiles per flush window (200 tiles) whose rows above the scale go round the fixed-point form (heavy_add)
-#endif
-#ifndef E9_PLANES_PACKED
-#define E9_PLANES_PACKED 1
-#endif
-#ifndef E9_GS_PAD
-#define E9_GS_PAD 18  // row stride of [G | b] / W rows = 16 NTP + 18 doubles: even, so that the solver's lane-per-sample accesses
-                      // pair up into 16-byte LDS operations that spread over all banks (measured: 17 costs 2 %)
-#endif
+// Choices that were build-time switches while they were being measured, fixed here to what ships:
+//  - b = X~ C on the 4 x 4 x 4 form with C operands from L1 / L2 only measured 100.0 against 100.7 EM it/s for the 16 x 16 x 4 form
+//    (the loop's 96 MFMAs of 17 cycles take 2.84 k cycles per tile against 2.70 k for 32 of 64: the 48 loads of C per wave and tile
+//    queue behind the Gram's digit-table loads -- one in-order vmcnt --, and deeper look-ahead changes nothing: E9_LAC = 6 gave 99.9;
+//    profiles/r05/README.md).  With two of the three column groups resident in LDS (layout B, above) it is 103.7 against 100.3.
+//  - the first E9_LAC steps of the remaining C operands are requested before the Gram's digit pairs (their L2 latency passes under
+//    the integer MFMAs).
+//  - the second digit pair {5,4} is requested with {7,6} during the previous tile's P4a.  On round 4's layout that only moved the
+//    wait (first half of the Gram 2.40 -> 2.12 k cycles per tile, b loop 2.70 -> 2.87 k: 100.7 against 100.8 it/s); on layout B,
+//    whose b loop waits for 16 instead of 48 loads, + 0.3 % (with nt row loads 104.2-104.4 against 103.2-103.4).
+//  - both roles run at the default wave priority, and a wave that polls a role barrier sleeps one s_sleep(1) per look.
+constexpr int E9_X_AUX = 2;  // cache policy of the row loads of X: nt (L2-served: the rows are read once and would only push the digit table and the
+                             // third column group of C out of the 32 KB L1).  Measured on layout B, two rounds interleaved: 103.9-104.1 against
+                             // 103.2-103.4 EM it/s (round 4's layout: +0.5 %, inside the spread)
+constexpr int E9_Q_AUX = 0;  // ... and of the Gram's digit table (128 KB per tile and workgroup).  Measured with 2 (nt): 90.0 against 100.7 it/s
+constexpr int E9_LAC = 4;    // look-ahead of the b loop's C operands, in steps
+constexpr int E9_HEAVY_BUDGET = 8;  // tiles per flush window (200 tiles) whose rows above the scale go round the fixed-point form (heavy_add)
+constexpr int E9_GS_PAD = 18;  // row stride of [G | b] / W rows = 16 NTP + 18 doubles: even, so that the solver's lane-per-sample accesses
+                               // pair up into 16-byte LDS operations that spread over all banks (measured: 17 costs 2 %)
+constexpr int E9_P4A_AHEAD = 1;  // k-steps P4a's LDS operands are requested ahead of their MFMAs (measured: 2 and 3 change nothing -- 95.9 / 95.8 / 95.4 it/s -- and cost registers)
 
-#ifdef PPCA_PHASE_TIMING  // per-wave phase sums into PassArgs::dbg (printed by ppca_capi.hip with em8's column names)
+#ifdef PPCA_PHASE_TIMING  // per-wave phase sums into PassArgs::dbg (printed by ppca_capi.hip)
 #define E9_FINE(i) { __builtin_amdgcn_sched_barrier(0); long long tn = clock64(); tfine[i] += tn - tfl; tfl = tn; __builtin_amdgcn_sched_barrier(0); }
 #else
 #define E9_FINE(i)
@@ -118,40 +117,36 @@ struct Cfg9 {
     //   as [G | b]:      G (16 NTP, K' used)        | b partial of dims 0-127 (16)          | pad (2)
     //   after the solve: L (K')  .. z in free slots | w z (K) | w | z in free slots ..      | z
     //   as W row:        w P (K') ..                | w z (K) | w | ..
-    static constexpr bool CLDS = E9_CLDS != 0;
     static constexpr int NCGB = (K + 3) / 4;                          // column groups of four of b = X~ C (4 x 4 x 4 form)
-    static constexpr int NCL = CLDS ? (NCGB < 2 ? NCGB : 2) : 0;      // ... whose C operands are resident in LDS
-    static constexpr int PADC = (CLDS && K == 10) ? 14 : E9_GS_PAD;   // width of the row's b area + pad (layout B squeezes k = 10)
+    static constexpr int NCL = NCGB < 2 ? NCGB : 2;                   // ... whose C operands are resident in LDS
+    static constexpr int PADC = K == 10 ? 14 : E9_GS_PAD;             // width of the row's b area + pad (k = 10 is squeezed)
     static constexpr int GS = 16 * NTP + PADC;
     static constexpr int WS = GS;
-    static constexpr int BS = CLDS ? 0 : K + 1;  // b partial of dims 128-255 (layout B: in the row's free slots, p1slot below)
     // digit planes of one tile: [plane][16-sample chunk][column][16 B].  (round 5) NCP = the NC real columns, not the NCOL of the 16-column
     // tiles: the lanes of the last column tile that stand for columns >= NC read whatever follows (the next chunk row, or the words
     // behind the region): their digit sums are never emitted (emit: c < NC) -- 14 columns x 14 rows x 16 B x 2 regions = 6.1 KB of LDS.
-    static constexpr int NCP = E9_PLANES_PACKED ? NC : NCOL;
+    static constexpr int NCP = NC;
     static constexpr int PLANE_BYTES = E9_QW * 2 * NCP * 16;
     static constexpr int OFF_X = 0;
     static constexpr int OFF_G = OFF_X + B * XS;          // two buffers: tile parity
     static constexpr int OFF_W = OFF_G;
-    static constexpr int OFF_B1 = OFF_G + 2 * B * GS;
-    static constexpr int OFF_M = OFF_B1 + B * BS;         // mask words, two parities x B x 4 u64
+    static constexpr int OFF_M = OFF_G + 2 * B * GS;      // mask words, two parities x B x 4 u64
     static constexpr int OFF_MB = OFF_M + 2 * B * 4;      // sample masks per dimension: DP x 4 u32 (slot = tile % 4)
     static constexpr int OFF_S = OFF_MB + DP * 2;         // cross-wave scratch
-    static constexpr int OFF_L = OFF_S + 2 * B;           // running scalars: sq[4][2 B] | dev | llk | w | ne | pm | px
-    static constexpr int OFF_P0 = OFF_L + (CLDS ? 6 : 14) * B;  // digit planes of a group's first tile (layout B: sq lives in a register)
+    static constexpr int OFF_L = OFF_S + 2 * B;           // running scalars: dev | llk | w | ne | pm | px (sq lives in a register)
+    static constexpr int OFF_P0 = OFF_L + 6 * B;          // digit planes of a group's first tile
     static constexpr int OFF_P1 = OFF_P0 + PLANE_BYTES / 8;  // ... and of its second
     static constexpr int OFF_E = OFF_P1 + PLANE_BYTES / 8;  // column exponents (NCOL ints), flags
     static constexpr int OFF_BAR = OFF_E + NCOL / 2 + 4;  // counters: front barrier, back barrier, tiles digitised, violation stamp
-    static constexpr int OFF_MU = OFF_BAR + 4;  // the mean (DP doubles, zero past d): re-read by the staging of every tile
-    static constexpr int OFF_K = OFF_MU + (CLDS ? 0 : DP);  // model scalars: sigma^2, 1 / sigma^2, ln sigma (re-read per tile)
+    static constexpr int OFF_K = OFF_BAR + 4;             // model scalars: sigma^2, 1 / sigma^2, ln sigma (re-read per tile)
     static constexpr int OFF_EB = OFF_K + 4;              // rounding bounds of the cut, per column (wguard_kernel)
     static constexpr int OFF_XT = OFF_EB + NCOL;          // by-products of the solve (quad, |z|^2, det M) per sample, two tile parities
-    static constexpr int OFF_CL = OFF_XT + 2 * B * 4;     // (layout B) C^T operands of the first NCL column groups: [K-half][step][group][32]
+    static constexpr int OFF_CL = OFF_XT + 2 * B * 4;     // C^T operands of the first NCL column groups: [K-half][step][group][32]
     static constexpr int LDS_DOUBLES = OFF_CL + 2 * 16 * NCL * 32;
-    // where the second K-half's partial of b[a] waits for the solver (layout B): the row's free slots at that time -- what is left of
+    // where the second K-half's partial of b[a] waits for the solver: the row's free slots at that time -- what is left of
     // the b area behind the K columns of the first half, then the G part's unused packed columns
     static constexpr int p1slot(int a) { return a < PADC - K ? 16 * NTP + K + a : KP + (a - (PADC - K)); }
-    static_assert(!CLDS || K - (PADC - K) <= 16 * NTP - KP, "free slots of a row hold the second partial of b");
+    static_assert(K - (PADC - K) <= 16 * NTP - KP, "free slots of a row hold the second partial of b");
     static_assert(NCOL / 2 <= 64, "one back wave digitises NCOL / 2 (column, chunk) items");
     static_assert(LDS_DOUBLES * 8 <= 160 * 1024, "LDS budget");
 };
@@ -165,14 +160,11 @@ __device__ __forceinline__ void role_barrier(unsigned *ctr, unsigned &target, in
     for (;;) {
         const unsigned seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         if ((int)(seen - target) >= 0) break;
-        E9_BARRIER_SLEEP
+        __builtin_amdgcn_s_sleep(1);
     }
     asm volatile("" ::: "memory");
 }
 __device__ __forceinline__ void wait_counter(const unsigned *ctr, unsigned need) {
-#if defined(E9_ONLY_FRONT) || defined(E9_ONLY_BACK)  // timing experiments with one role absent: nothing to wait for
-    return;
-#endif
     for (;;) {
         const unsigned seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         if ((int)(seen - need) >= 0) break;
@@ -188,12 +180,11 @@ __device__ __forceinline__ void wait_counter(const unsigned *ctr, unsigned need)
 template <int K, bool GATHER, bool WEIGHTED>
 __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     using cfg = Cfg9<K>;
-    constexpr int KP = cfg::KP, NTP = cfg::NTP, B = cfg::B, XS = cfg::XS, CS = cfg::CS, GS = cfg::GS, BS = cfg::BS,
+    constexpr int KP = cfg::KP, NTP = cfg::NTP, B = cfg::B, XS = cfg::XS, CS = cfg::CS, GS = cfg::GS,
                   WS = cfg::WS, NC = cfg::NC, NCT = cfg::NCT, NCOL = cfg::NCOL, NCP = cfg::NCP;
     constexpr int NF = 4;              // waves per role
     constexpr int RPW = B / NF;        // rows staged per front wave
     constexpr int DPS = cfg::DP / 2;   // dims per K-split of b = X~ C
-    constexpr int STEPS = DPS / 4;
     constexpr int RT = 16 / NF;        // 16-dim row tiles per wave in P4
     constexpr int DW = cfg::DP / NF;   // dims owned by a wave in P4
     constexpr int QW = E9_QW;
@@ -202,7 +193,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double *Xs = sm + cfg::OFF_X;
     double *Gs = sm + cfg::OFF_G;
-    double *B1 = sm + cfg::OFF_B1;
     double *Ws = sm + cfg::OFF_W;
     unsigned long long *Ms = reinterpret_cast<unsigned long long *>(sm + cfg::OFF_M);
     unsigned *Mb = reinterpret_cast<unsigned *>(sm + cfg::OFF_MB);
@@ -229,25 +219,16 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     const double s2_k = p.model[1], lnsig_k = p.model[2];
 
     constexpr bool PAIRS = K >= 2;
-    constexpr int SQW = PAIRS ? 2 * B : B;  // sq slots per front wave
-    constexpr bool CLDS = cfg::CLDS;
-    constexpr int L_DEV = CLDS ? 0 : NF * SQW, L_LLK = L_DEV + B, L_W = L_DEV + 2 * B, L_NE = L_DEV + 3 * B, L_PM = L_DEV + 4 * B,
-                  L_PX = L_DEV + 5 * B;
-    static_assert(L_DEV + 6 * B <= (CLDS ? 6 : 14) * B, "scalar slots");
+    constexpr int L_DEV = 0, L_LLK = L_DEV + B, L_W = L_DEV + 2 * B, L_NE = L_DEV + 3 * B, L_PM = L_DEV + 4 * B, L_PX = L_DEV + 5 * B;
     for (int idx = tid; idx < L_DEV + 6 * B; idx += 512) scl[idx] = (idx >= L_PM && idx < L_PX) ? 1.0 : 0.0;
     for (int idx = tid; idx < cfg::DP * 4; idx += 512) Mb[idx] = 0u;
-    if constexpr (!CLDS) {
-        for (int idx = tid; idx < cfg::DP; idx += 512) sm[cfg::OFF_MU + idx] = idx < d ? mMean[idx] : 0.0;
-    } else {  // the resident part of C^T in operand order: [K-half][step][group < NCL][32] of PassArgs::cpb's [..][group < NCGB][32]
+    {  // the resident part of C^T in operand order: [K-half][step][group < NCL][32] of PassArgs::cpb's [..][group < NCGB][32]
         constexpr int NCL = cfg::NCL, NCGB = cfg::NCGB;
         for (int idx = tid; idx < 2 * 16 * NCL * 32; idx += 512) {
             const int e = idx & 31, blk = idx >> 5, c = blk % NCL, hq = blk / NCL;
             sm[cfg::OFF_CL + idx] = p.cpb[(hq * NCGB + c) * 32 + e];
         }
     }
-#ifdef E9_ONLY_BACK
-    for (int idx = tid; idx < 2 * B * GS; idx += 512) Gs[idx] = 1.0;  // (something finite for the back role to cut)
-#endif
     if (tid < 8) ctr[tid] = 0u;
     if (tid < 4) Ex[NCOL + tid] = 0;  // (heavy-row words of the back role's cold path)
     if (tid < NCOL) sm[cfg::OFF_EB + tid] = 0.0;
@@ -266,12 +247,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     long long tfl = clock64();
 #endif
     __syncthreads();
-#ifdef E9_ONLY_FRONT
-    if (!front) return;
-#endif
-#ifdef E9_ONLY_BACK
-    if (front) return;
-#endif
 
     if (!front) {
         // =========================================================== back role: P4b on the int8 MFMA
@@ -285,7 +260,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 for (int q = 0; q < 4; ++q) accM[r][t][q] = (acc_t)0;
         // (measured: the back role at a higher priority than the front costs 5 % -- it is off the front's critical path
         //  and only has to fill the gaps)
-        if (E9_BACK_PRIO) __builtin_amdgcn_s_setprio(E9_BACK_PRIO);
         unsigned bbar_target = 0u;
         unsigned attempt = 0u;   // digitise attempts so far (the violation stamp of the current one)
         int pending = 0;         // 1: the previous tile's planes wait in P0 for their partner
@@ -356,7 +330,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 tr4(whi, &pl[4][g4], &pl[5][g4], &pl[6][g4], nullptr);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (active && (cvalid || NCP == NCOL)) {
+            if (active && cvalid) {
                 unsigned char *wq = smb + dst_bytes;
 #pragma unroll
                 for (int sl = 0; sl < QW; ++sl)
@@ -669,7 +643,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     }
 
     // =============================================================== front role
-    if (E9_FRONT_PRIO) __builtin_amdgcn_s_setprio(E9_FRONT_PRIO);
     unsigned fbar_target = 0u;
     // cross / sumx accumulators of P4a on v_mfma_f64_4x4x4 (four independent 4 x 4 x 4 blocks per instruction: block b = lane bits
     // 2-3; A[i][k] in lane 16 k + 4 b + i, B[k][j] in lane 16 k + 4 b + j, D[i][j] in lane 16 i + 4 b + j -- probed on the part,
@@ -742,10 +715,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     const __amdgpu_buffer_rsrc_t qrsrc = __builtin_amdgcn_make_buffer_rsrc(p.qtab, 0, (int)qtab_bytes<K>(), 0x00020000);
     const bool gram_wave = NTP >= NF || wave < NTP;
     i4_t qbA[2][4];
-#if E9_QB_EARLY
     i4_t qbB[2][4];  // digits {5,4} requested with {7,6} during the previous tile's P4a (round 5): requested at the top of P2 they
                      // were ~600 cycles old when the second digit pair wanted them -- an L2 round trip is longer
-#endif
     auto load_pair = [&](i4_t(&dst)[2][4], int sl0) {
         int qbase = wave * QS * 4 * 1024;
         asm volatile("" : "+s"(qbase));
@@ -766,8 +737,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     int st_wlo = 0, st_whi = 0;
     int st_mb[4] = {0, 0, 0, 0};
     double xx_run = 0.0;  // sum_i w_i |x~_i|^2 of this wave's rows (sigma^2 and the llk are linear in it)
-    double sq_run = 0.0;  // (layout B) this lane's running share of sum_i w_i tr(C_o Sigma_i C_o^T); layout A keeps it in LDS
-    // (layout B) the lane's four means, requested from L1 / L2 with the next tile's rows (no LDS copy of the mean)
+    double sq_run = 0.0;  // this lane's running share of sum_i w_i tr(C_o Sigma_i C_o^T)
+    // the lane's four means, requested from L1 / L2 with the next tile's rows (no LDS copy of the mean)
     double muq[4] = {0.0, 0.0, 0.0, 0.0};
     auto load_mu = [&]() {
         const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(mMean), 0, d * (int)sizeof(double), 0x00020000);
@@ -813,18 +784,11 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     };
     // staging lane map: lane l holds dims 128 h + 2 l + e (element q = 2 h + e) of a row.  The lane's four means and
     // limits (observed <=> |x| < lim: +inf for a real dimension -- the finite test of dataset.rs:19-22 --, -1 for the
-    // padding past d) are rebuilt per tile from the LDS copy of the mean: as loop invariants they sat in 16 registers
+    // padding past d) are rebuilt per tile from the means load_mu requested: as loop invariants they sat in 16 registers
     // across the solver and were what the register allocator spilled.
     auto stage_tile = [&](int64_t t, int lane) {
         {
-            typedef double d2_t __attribute__((ext_vector_type(2)));
-            if constexpr (CLDS) {
-                mu[0] = muq[0]; mu[1] = muq[1]; mu[2] = muq[2]; mu[3] = muq[3];
-            } else {
-                const d2_t m0 = *reinterpret_cast<const d2_t *>(sm + cfg::OFF_MU + 2 * lane);
-                const d2_t m1 = *reinterpret_cast<const d2_t *>(sm + cfg::OFF_MU + 128 + 2 * lane);
-                mu[0] = m0[0]; mu[1] = m0[1]; mu[2] = m1[0]; mu[3] = m1[1];
-            }
+            mu[0] = muq[0]; mu[1] = muq[1]; mu[2] = muq[2]; mu[3] = muq[3];
 #pragma unroll
             for (int q = 0; q < 4; ++q) lim[q] = (128 * (q >> 1) + 2 * lane + (q & 1) < d) ? __builtin_inf() : -1.0;
         }
@@ -846,11 +810,9 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
         if constexpr (GATHER || WEIGHTED) fetch_meta(tile_begin);
 #pragma unroll
         for (int r = 0; r < RPW; ++r) load_row(trs, tile_begin, r);
-        if constexpr (CLDS) load_mu();
+        load_mu();
         load_pair(qbA, 6);
-#if E9_QB_EARLY
         load_pair(qbB, 4);
-#endif
         stage_tile(tile_begin, lane_entry);
         if constexpr (GATHER || WEIGHTED) fetch_meta(tile_begin + 1);
     }
@@ -863,7 +825,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     constexpr int LROWS = LMAJ ? (KP + LPER - 1) / LPER : 0;  // buffer rows the entry-major factor takes
     // z (a, sample i): first the unused columns of the row's b partial and the pad; what does not fit goes behind K' in the row
     // (row-major factor) or entry-major behind the factor's rows (entry-major factor: the G part of every row is taken)
-    constexpr int PADC = cfg::PADC, ZIN = PADC - K - 1;  // z slots behind [w z | w] in the row's b area + pad (layout A: 17 - K)
+    constexpr int PADC = cfg::PADC, ZIN = PADC - K - 1;  // z slots behind [w z | w] in the row's b area + pad
     auto zslot = [](int a, int i) {
         if (a < ZIN) return i * GS + 16 * NTP + K + 1 + a;
         a -= ZIN;
@@ -891,14 +853,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
         // ------------------------------------------------------------ P2: [G | b] of the tile
         if (cur) {
             const int rt = wave & 1, kq = wave >> 1;
-#if E9_B444
             constexpr int NCGB = (K + 3) / 4;  // column groups of four
             double bsum[NCGB];
-#else
-            const int si = 16 * rt + l15;
-            d4_t accb = d4_t{0, 0, 0, 0};
-            const double *xrow = Xs + si * XS + DPS * kq + l4;
-#endif
             // the count of tiles the back role has cut, requested HERE and looked at where [G | b] is stored: by then it is
             // almost always enough, and the poll (an LDS round trip behind everything this wave has queued: ~0.7 k cycles per
             // tile in the phase table) is skipped
@@ -925,7 +881,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                     }
                 }
             };
-#if E9_B444
             // (operand pointers of the b product; its first LAC steps of C are requested before the Gram's digit pairs so that
             //  their L2 latency passes under the integer MFMAs)
                 constexpr int NQ = DPS / 8;  // steps of 8 dimensions (two blocks of four)
@@ -950,7 +905,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 double cb[LAC + 1][NCGB], xb[LAX + 1][2];
                 constexpr int NCLc = cfg::NCL;
                 const double *clp = sm + cfg::OFF_CL + kq * (NQ * NCLc * 32) + (2 * l4 + kb) * 4 + j4;
-                auto cload_lds = [&](auto q_tag) {  // (layout B) the resident column groups, requested with the x~ operands
+                auto cload_lds = [&](auto q_tag) {  // the resident column groups, requested with the x~ operands
                     constexpr int q = decltype(q_tag)::value;
 #pragma unroll
                     for (int c = 0; c < NCLc; ++c) cb[q % (LAC + 1)][c] = clp[(q * NCLc + c) * 32];
@@ -961,10 +916,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                     for (int c = NCLc; c < NCGB; ++c) {
                         typedef unsigned u2_t __attribute__((ext_vector_type(2)));
                         const int off = (q * NCGB + c) * 256;  // (a constant once the loop is unrolled)
-#ifdef E9_EXP_CLDS  // (timing experiment, results wrong: what the loop would cost with its C operands in LDS)
-                        cb[q % (LAC + 1)][c] = Xs[(cvo + off) / 8 + kq * 4096];
-                        continue;
-#endif
                         const u2_t v2 = __builtin_amdgcn_raw_buffer_load_b64(crs, cvo + (off & 4095), cso[off >> 12], 0);
                         cb[q % (LAC + 1)][c] = __longlong_as_double(((long long)v2[1] << 32) | v2[0]);
                     }
@@ -974,11 +925,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
 #pragma unroll
                     for (int g = 0; g < 2; ++g) xb[q % (LAX + 1)][g] = xrow[8 * g * XS + 32 * (q >> 2) + 4 * (q & 3)];
                 };
-#endif
             double qs = 0.0;
-#if !E9_QB_EARLY
-            i4_t qbB[2][4];
-#endif
             {
                 unsigned long long mwd[2][4];
 #pragma unroll
@@ -986,13 +933,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
 #pragma unroll
                     for (int kc = 0; kc < 4; ++kc) mwd[rt2][kc] = Msc[(16 * rt2 + l15) * 4 + kc];
                 __builtin_amdgcn_sched_barrier(0);
-#if !E9_QB_EARLY
-                load_pair(qbB, 4);
-#endif
                 if (gram_wave) qs = p.qscale[16 * wave + l15];
-#if E9_B444 && E9_B_EARLYC
                 static_for<LAC>([&](auto q_tag) { cload(q_tag); });
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 // A = mask bytes: lane (sample 16 rt2 + l15, k-chunk kc, 16 l4 .. +15 of it); 4 bits -> 4 bytes by one
                 // multiply: (x * 0x204081) & 0x01010101 puts bit i of x into byte i
@@ -1011,7 +953,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 load_pair(qbB, 0);
             }
             E9_FINE(15)  // "-": mask bytes + digit pairs {7,6}, {5,4}
-#if E9_B444
             {
                 // b = X~ C on v_mfma_f64_4x4x4 (round 5).  One instruction = four independent 4 x 4 x 4 blocks; block = (kb, sb):
                 // two groups of four DIMENSIONS x two groups of four SAMPLES, so one MFMA covers 8 samples x 4 columns x 8
@@ -1021,9 +962,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 // 258-double row stride).  Per wave and tile 96 MFMAs of 17 cycles where the 16 x 16 x 4 form took 32 of
                 // 105-142 (profiles/r04/mfma_peak.txt), the same 32 LDS reads, 48 instead of 32 loads of C, and the two
                 // dimension-group partials summed across lane bit 3 at the end.
-#if !E9_B_EARLYC
-                static_for<LAC>([&](auto q_tag) { cload(q_tag); });
-#endif
                 static_for<LAX>([&](auto q_tag) {
                     xload(q_tag);
                     cload_lds(q_tag);
@@ -1053,36 +991,6 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                     bsum[c] = kb ? t1 : t0;
                 }
             }
-#else
-            {
-                // the 16 x 16 x 4 form of rounds 3-4 (kept for A/B runs): B operands from the zero-padded copy of C in global
-                // memory (L1 / L2), requested two chunks of four k-steps ahead
-                constexpr int CH = 4, NCH = STEPS / CH;
-                const double *cg = p.cpad + (DPS * kq + l4) * CS + colb;
-                double axb[2][CH], cbb[3][CH];
-#pragma unroll
-                for (int c0 = 0; c0 < 2; ++c0)
-#pragma unroll
-                    for (int u = 0; u < CH; ++u) cbb[c0][u] = cg[4 * (c0 * CH + u) * CS];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) axb[0][u] = xrow[4 * u];
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if (c + 1 < NCH) {
-#pragma unroll
-                        for (int u = 0; u < CH; ++u) axb[(c + 1) & 1][u] = xrow[4 * ((c + 1) * CH + u)];
-                    }
-                    if (c + 2 < NCH) {
-#pragma unroll
-                        for (int u = 0; u < CH; ++u) cbb[(c + 2) % 3][u] = cg[4 * ((c + 2) * CH + u) * CS];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < CH; ++u) accb = mfma(axb[c & 1][u], cbb[c % 3][u], accb);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#endif
             E9_FINE(4)   // "P3-load": the b loop
             group(qbA, false);  // digits {3,2}
             group(qbB, false);  // digits {1,0}
@@ -1096,32 +1004,17 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 for (int rt2 = 0; rt2 < 2; ++rt2)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)  // C/D map of the 16x16 integer MFMA: row = 4 (lane >> 4) + reg
-                        if (!CLDS || 16 * wave + l15 < KP) Gcur[(16 * rt2 + 4 * l4 + r) * GS + 16 * wave + l15] = v[rt2][r] * qs;  // (sample-major: the solver's loads pair up into 16-byte reads; entry-major measured 2 % slower)
+                        if (16 * wave + l15 < KP) Gcur[(16 * rt2 + 4 * l4 + r) * GS + 16 * wave + l15] = v[rt2][r] * qs;  // (sample-major: the solver's loads pair up into 16-byte reads; entry-major measured 2 % slower)
             }
             // the two K-split partials of b are summed by the solver in a fixed order (p0 + p1)
-#if E9_B444
 #pragma unroll
             for (int c = 0; c < NCGB; ++c) {
-                if constexpr (CLDS) {
-                    const int a = 4 * c + l4;
-                    if (a < K) Gcur[(16 * rt + l15) * GS + (kq == 0 ? 16 * NTP + a : cfg::p1slot(a))] = bsum[c];
-                } else {
-                    if (kq == 0) Gcur[(16 * rt + l15) * GS + 16 * NTP + 4 * c + l4] = bsum[c];
-                    else if (4 * c + l4 < K + 1) B1[(16 * rt + l15) * BS + 4 * c + l4] = bsum[c];
-                }
+                const int a = 4 * c + l4;
+                if (a < K) Gcur[(16 * rt + l15) * GS + (kq == 0 ? 16 * NTP + a : cfg::p1slot(a))] = bsum[c];
             }
-#else
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (kq == 0) Gcur[(16 * rt + l4 + 4 * r) * GS + 16 * NTP + l15] = accb[r];
-                else if (l15 < K + 1) B1[(16 * rt + l4 + 4 * r) * BS + l15] = accb[r];
-            }
-#endif
         }
         E9_FINE(2)
-#ifndef E9_EXP_NOB1  // (timing experiment, results wrong: what this barrier costs)
         role_barrier(fbar, fbar_target, lane_entry);
-#endif
         // ------------------------------------------------------------ phase beta: solve tile rel | columns of tile rel - 1
         // ONE front wave (rel mod 4) factors the samples of tile rel (lane = sample, lanes 32-63 mirror 0-31), solves for z,
         // leaves factor, z and [wz | w] in the tile's rows and takes the scalars; the other three form the columns of M^-1 of
@@ -1141,30 +1034,19 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 if (cur) {
                     const int64_t row = tile * B + i;
                     double *g0 = Gcur + i * GS;
-                    const double *b1 = B1 + i * BS;
                     const double wgt = (row < n) ? (WEIGHTED ? p.w[row] : 1.0) : 0.0;
                     const int m = __popcll(Msc[i * 4]) + __popcll(Msc[i * 4 + 1]) + __popcll(Msc[i * 4 + 2]) + __popcll(Msc[i * 4 + 3]);
                     Posterior<K> fac;
                     double pm = 1.0;
                     int pe = 0;
                     double z[K], quad = 0.0, zz = 0.0;
-#ifdef E9_EXP_NOLOAD  // (timing experiments, results wrong: what each part of the solver's trip costs)
-                    fac.load([&](int e) { return (double)(e + 1) * s2; }, s2);
-#pragma unroll
-                    for (int a = 0; a < K; ++a) z[a] = s2 + (double)a;
-#else
                     fac.load([&](int e) { return g0[e]; }, s2);
 #pragma unroll
-                    for (int a = 0; a < K; ++a) z[a] = g0[16 * NTP + a] + (CLDS ? g0[cfg::p1slot(a)] : b1[a]);
-#endif
+                    for (int a = 0; a < K; ++a) z[a] = g0[16 * NTP + a] + g0[cfg::p1slot(a)];
                     E9_FINE(7)   // "solve" column of the table: the solver's loads
-#ifndef E9_EXP_NOFACTOR
                     fac.factor_loaded(pm, pe);
-#endif
                     E9_FINE(9)   // "scalars": its factorisation
-#ifndef E9_EXP_NOSOLVE
                     fac.solve_loaded(z, quad, zz);
-#endif
                     E9_FINE(10)  // "wg-barrier": its substitutions; "factor": its write-back
                     if (hi == 0) {
                         // the factor ENTRY-major over the G part of the tile's buffer (entry e of sample i at row e / 2, column
@@ -1172,12 +1054,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                         // between the lanes, every store and every load of the three column waves ran four-way bank-conflicted
                         // (the solver's trip took 4.7 k cycles).  Safe: every lane of this wave has read its own [G | b] row
                         // before the first store is issued, and nobody else reads this buffer in this phase.
-#ifndef E9_EXP_NOWRITE  // (timing experiment: what the write-back costs)
 #pragma unroll
                         for (int e = 0; e < KP; ++e) Gcur[lslot(e, i)] = fac.L[e];
-#else
-                        Gcur[lslot(0, i)] = fac.L[0] + fac.L[KP - 1];
-#endif
 #pragma unroll
                         for (int a = 0; a < K; ++a) Gcur[zslot(a, i)] = z[a];
                         // W row = [w P (K') | .. | w z (K) | w | ..]: the [w z | w] part now (P4a of this trip reads it)
@@ -1258,14 +1136,11 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                     scl[L_NE + i] = run_ne + sc_ne;
                 }
             }
-            if constexpr (CLDS) sq_run += sc_sq;
-            else scl[wave * SQW + (PAIRS ? lane : i)] += sc_sq;
+            sq_run += sc_sq;
         }
         if (wave == solver) { E9_FINE(6) } else { E9_FINE(8) }  // "factor": the solver's trip; "columns": a column wave's
         // the factor, z and [wz | w] of tile rel and the W rows of tile rel - 1 are final
-#ifndef E9_EXP_NOB2  // (timing experiment, results wrong: what this barrier costs)
         role_barrier(fbar, fbar_target, lane_entry);
-#endif
         E9_FINE(5)
         if (rel > 0 && lane_entry == 0) __hip_atomic_fetch_add(wready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (!cur) break;
@@ -1273,13 +1148,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
         // the only reader of the x~ tile; the next tile's rows are requested one per k-step behind the MFMAs
         {
             load_pair(qbA, 6);  // the next tile's first digit pair (the table does not depend on the tile)
-            if constexpr (CLDS) load_mu();
-#if E9_QB_EARLY
+            load_mu();
             load_pair(qbB, 4);  // ... and its second
-#endif
-#ifndef E9_P4A_AHEAD
-#define E9_P4A_AHEAD 1  // k-steps the LDS operands are requested ahead of their MFMAs (measured: 2 and 3 change nothing -- 95.9 / 95.8 / 95.4 it/s -- and cost registers)
-#endif
             constexpr int AH = E9_P4A_AHEAD, NB3 = AH + 1;
             double bzb[NB3][NCG], axb[NB3][RT];
             const __amdgpu_buffer_rsrc_t trs = tile_rsrc(tile + 1);
@@ -1314,9 +1184,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
             }
         }
         E9_FINE(11)
-#ifndef E9_EXP_NOB3  // (timing experiment, results wrong: what this barrier costs)
         role_barrier(fbar, fbar_target, lane_entry);  // the x~ tile is free
-#endif
         E9_FINE(12)
         // ------------------------------------------------------------ P1 of the next tile
         // (its sample masks go into the slot of tile rel - 3: the back role's iterations up to rel - 2 must be over)
@@ -1324,9 +1192,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
         stage_tile(tile + 1, lane);
         if constexpr (GATHER || WEIGHTED) fetch_meta(tile + 2);  // (consumed one trip from here: P4a's row requests, the staging's weights)
         E9_FINE(13)
-#ifndef E9_EXP_NOB4  // (timing experiment, results wrong: what this barrier costs)
         role_barrier(fbar, fbar_target, lane_entry);
-#endif
         E9_FINE(14)
     }
 #ifdef PPCA_PHASE_TIMING
@@ -1337,7 +1203,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     // ---------------------------------------------------------------- epilogue (front waves)
     {
         const int lane = lane_entry, l15 = lane & 15, l4 = lane >> 4;
-        const double sq_w = CLDS ? wave_sum(sq_run) : wave_sum(lane < SQW ? scl[wave * SQW + lane] : 0.0);
+        const double sq_w = wave_sum(sq_run);
         const double xx_w = wave_sum(xx_run);
         if (lane == 0) {
             xxs[wave] = sq_w;
@@ -1387,16 +1253,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
 template <int K, bool GATHER, bool WEIGHTED>
 static hipError_t launch_em9_t(int grid, const PassArgs &a, hipStream_t s) {
     const size_t lds = sizeof(double) * Cfg9<K>::LDS_DOUBLES;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&em9_kernel<K, GATHER, WEIGHTED>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = ensure_dynamic_lds<em9_kernel<K, GATHER, WEIGHTED>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((em9_kernel<K, GATHER, WEIGHTED>), dim3(grid), dim3(512), lds, s, a);
     return hipGetLastError();
 }
@@ -1424,19 +1281,19 @@ bool em9_covers(int k) {
 
 hipError_t launch_em9(int k, int grid, const PassArgs &a, hipStream_t s) {
     const bool gather = a.rows != nullptr;
-#define PPCA_E8_CASE(KK) \
+#define PPCA_E9_CASE(KK) \
     case KK:             \
         return gather ? launch_em9_t<KK, true, true>(grid, a, s) : (a.w ? launch_em9_t<KK, false, true>(grid, a, s) : launch_em9_t<KK, false, false>(grid, a, s));
     switch (k) {
 #ifdef PPCA_DEV_K10
-        PPCA_E8_CASE(10)
+        PPCA_E9_CASE(10)
 #else
-        PPCA_E8_CASE(1) PPCA_E8_CASE(2) PPCA_E8_CASE(3) PPCA_E8_CASE(4) PPCA_E8_CASE(5) PPCA_E8_CASE(6) PPCA_E8_CASE(7)
-        PPCA_E8_CASE(8) PPCA_E8_CASE(9) PPCA_E8_CASE(10)
+        PPCA_E9_CASE(1) PPCA_E9_CASE(2) PPCA_E9_CASE(3) PPCA_E9_CASE(4) PPCA_E9_CASE(5) PPCA_E9_CASE(6) PPCA_E9_CASE(7)
+        PPCA_E9_CASE(8) PPCA_E9_CASE(9) PPCA_E9_CASE(10)
 #endif
         default: return hipErrorInvalidValue;
     }
-#undef PPCA_E8_CASE
+#undef PPCA_E9_CASE
 }
 
 }  // namespace ppca

@@ -14,7 +14,6 @@
 // GEMM is a plain LDS-staged 64x64 tile kernel on v_mfma_f64_16x16x4_f64.
 #include <algorithm>
 #include <vector>
-#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -1574,9 +1573,7 @@ __global__ __launch_bounds__(256) void solve_big_kernel(SolveArgs a) {
 static size_t solve_big_lds(int k) { return sizeof(double) * ((size_t)k * (k | 1) + 2 * (size_t)k + 256); }
 static hipError_t launch_solve_big(const SolveArgs &a, int n_cu, hipStream_t s) {
     const size_t lds = solve_big_lds(a.k);
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        e != hipSuccess)
-        return e;
+    if (hipError_t e = ensure_dynamic_lds<solve_big_kernel>(lds); e != hipSuccess) return e;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(a.n, (int64_t)n_cu));
     hipLaunchKernelGGL(solve_big_kernel, dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
@@ -2006,16 +2003,7 @@ __global__ __launch_bounds__(256) void solve_bc_kernel(SolveArgs a) {
 template <int KPAD>
 static hipError_t launch_solve_bc(const SolveArgs &a, int grid, hipStream_t s) {
     const size_t lds = sizeof(double) * 4 * KPAD * KPAD;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (lds > 65536 && !(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_bc_kernel<KPAD>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = lds > 65536 ? ensure_dynamic_lds<solve_bc_kernel<KPAD>>(lds) : hipSuccess; e != hipSuccess) return e;
     hipLaunchKernelGGL((solve_bc_kernel<KPAD>), dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }
@@ -2320,20 +2308,11 @@ static hipError_t launch_solve_mfma(const SolveArgs &a, int n_cu, hipStream_t s)
     }();
     int grid = (int)std::min<int64_t>((a.n + W - 1) / W, (int64_t)n_cu * (occ2 ? 2 : 1));
     if (grid < 1) grid = 1;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (lds > 65536 && !(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_mfma_kernel<NB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 65536) {
+        if (hipError_t e = ensure_dynamic_lds<solve_mfma_kernel<NB>>(lds); e != hipSuccess) return e;
         if constexpr (NB <= 4) {
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_mfma_occ2_kernel<NB>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (hipError_t e = ensure_dynamic_lds<solve_mfma_occ2_kernel<NB>>(lds); e != hipSuccess) return e;
         }
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
     }
     if constexpr (NB <= 4) {
         if (occ2) {
@@ -2715,16 +2694,7 @@ template <int TM, bool BUF>
 static hipError_t launch_i8gemm_t(const I8GemmArgs &g, dim3 grid, hipStream_t s) {
     constexpr int nbuf = (BUF && I8_RING != 0) ? (TM == 256 ? 4 : 3) : 2;
     const size_t lds = (size_t)nbuf * (TM + GQS * 32) * 64 + (nbuf >= 3 ? 64 : 0);  // (+ the ring's counters)
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (lds > 65536 && !(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&i8gemm_kernel<64, TM, BUF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = lds > 65536 ? ensure_dynamic_lds<i8gemm_kernel<64, TM, BUF>>(lds) : hipSuccess; e != hipSuccess) return e;
     hipLaunchKernelGGL((i8gemm_kernel<64, TM, BUF>), grid, dim3(2 * TM), lds, s, g);
     return hipGetLastError();
 }
@@ -2838,19 +2808,10 @@ static hipError_t launch_gemm(GemmArgs g, hipStream_t s, int n_cu = 256, double 
 
 static size_t solve_lds(int k) { return sizeof(double) * 2 * (size_t)(2 * k * (k | 1) + 64); }
 
-// hipFuncSetAttribute is per device: each device gets the attribute once, at the size of the largest k (64) this kernel serves.
+// each device gets the attribute once, at the size of the largest k (64) this kernel serves
 static hipError_t set_solve_lds(int k) {
     if (solve_lds(k) <= 65536) return hipSuccess;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)solve_lds(64));
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-    return hipSuccess;
+    return ensure_dynamic_lds<solve_kernel>(solve_lds(64));
 }
 
 #define GTRY(expr)                        \
@@ -2985,15 +2946,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
             if (k <= 16) hipLaunchKernelGGL((gen_prep_kernel<1>), pg, dim3(256), prep_lds(1), s, Xc, ldx, nc, d, W.dpad, W.npad, model, k, W.A, W.AT, W.xx, W.mc, W.Bz, i8 ? 1 : 0);
             else if (k <= 32) hipLaunchKernelGGL((gen_prep_kernel<2>), pg, dim3(256), prep_lds(2), s, Xc, ldx, nc, d, W.dpad, W.npad, model, k, W.A, W.AT, W.xx, W.mc, W.Bz, i8 ? 1 : 0);
             else {
-                static std::atomic<unsigned long long> prep_done{0ull};  // (per device, as the other kernels above 64 KB of LDS)
-                int dev = 0;
-                GTRY(hipGetDevice(&dev));
-                const unsigned long long bit = 1ull << (dev & 63);
-                if (!(prep_done.load(std::memory_order_acquire) & bit)) {
-                    GTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&gen_prep_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)prep_lds(4)));
-                    prep_done.fetch_or(bit, std::memory_order_release);
-                }
+                GTRY(ensure_dynamic_lds<gen_prep_kernel<4>>(prep_lds(4)));
                 hipLaunchKernelGGL((gen_prep_kernel<4>), pg, dim3(256), prep_lds(4), s, Xc, ldx, nc, d, W.dpad, W.npad, model, k, W.A, W.AT, W.xx, W.mc, W.Bz, i8 ? 1 : 0);
             }
             GTRY(hipGetLastError());
@@ -3237,7 +3190,7 @@ hipError_t generic_finalize(int k, int d, const double *stats, const double *mod
                             int has_ig, double alpha, double beta, int n_cu, hipStream_t s) {
     if (k > 64) {  // one workgroup per dimension (solve_big_kernel's tools)
         const size_t lds = solve_big_lds(k);
-        GTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&gen_rowsolve_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        GTRY(ensure_dynamic_lds<gen_rowsolve_big_kernel>(lds));
         hipLaunchKernelGGL(gen_rowsolve_big_kernel, dim3((unsigned)std::min(d, 4 * n_cu)), dim3(256), lds, s, stats, model_in, model_out, d, k, tau);
         GTRY(hipGetLastError());
         hipLaunchKernelGGL(gen_finalize_misc_kernel, dim3(1), dim3(256), 0, s, stats, model_in, model_out, d, k, has_ig, alpha, beta);
@@ -3245,17 +3198,7 @@ hipError_t generic_finalize(int k, int d, const double *stats, const double *mod
     }
     const auto rowsolve_lds = [](int kk) { return sizeof(double) * 2 * (size_t)(kk * (kk | 1) + 64); };
     const size_t lds = rowsolve_lds(k);
-    if (lds > 65536) {  // (k = 64: 67,584 B) per device, as set_solve_lds
-        static std::atomic<unsigned long long> done{0ull};
-        int dev = 0;
-        GTRY(hipGetDevice(&dev));
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(done.load(std::memory_order_acquire) & bit)) {
-            GTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&gen_rowsolve_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowsolve_lds(64)));
-            done.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    if (lds > 65536) GTRY(ensure_dynamic_lds<gen_rowsolve_kernel>(rowsolve_lds(64)));  // (k = 64: 67,584 B), as set_solve_lds
     int grid = std::min((d + 1) / 2, n_cu * 2);
     hipLaunchKernelGGL(gen_rowsolve_kernel, dim3(grid), dim3(128), lds, s, stats, model_in, model_out, d, k, tau);
     GTRY(hipGetLastError());

@@ -5,7 +5,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
+#include <mutex>
 
 #include "ppca_small.hpp"
 
@@ -48,8 +50,8 @@ struct PassArgs {
     double *dbg;          // diagnostic builds (-DPPCA_PHASE_TIMING): [grid][4] phase cycle sums
     // EM mode, the guard of the int8 form of the mask-side statistics (launch_em_wguard):
     double *errb;         // [grid][W_GUARD_NCOL]: per workgroup and column of [wP | wz | w], a bound of the rounding the fixed-point
-                          // cut added to any sum of that column (written by em8_kernel; nullptr: not collected)
-    const double *cpad;   // zero-padded copy of C, [256][k + 1], written by qprep_kernel (em8's -DE8_C_GLOBAL experiment)
+                          // cut added to any sum of that column (written by em9_kernel; nullptr: not collected)
+    const double *cpad;   // zero-padded copy of C, [256][k + 1], written by qprep_kernel (read by no kernel since em9_kernel's b product moved to cpb)
     const double *cpb;    // C as the A operands of em9_kernel's b = X~ C on v_mfma_f64_4x4x4, in operand order (CPB_DOUBLES, written
                           // by qprep_kernel: see cpb_index)
     const int *runflag;   // nullable: second stage of a guarded EM pass (launch_em_fallback): the fp64 instantiation of pass_kernel
@@ -124,6 +126,28 @@ constexpr int CPB_GROUPS = 3;  // column groups of 4 at k = FUSED_MAX_K = 10
 constexpr int CPB_DOUBLES = 2 * 16 * CPB_GROUPS * 32;
 constexpr int W_GUARD_NCOL = 80;  // 16 x ceil((k' + k + 1) / 16) at k = 10
 
+// Raises hipFuncAttributeMaxDynamicSharedMemorySize of `Kernel` on the current device to at least `bytes`; a no-op when this device
+// already has that much for this kernel.  The attribute is per device and per kernel: one table per kernel holds, per device, the
+// largest size set so far (read without the lock by every launch; written under it, so that two callers with different sizes cannot
+// leave the attribute below what the table says).  A device id beyond the table sets the attribute uncached.
+template <auto Kernel>
+hipError_t ensure_dynamic_lds(size_t bytes) {
+    constexpr int TABLE = 64;
+    static std::atomic<size_t> have[TABLE] = {};
+    static std::mutex mu;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    const bool cached = dev >= 0 && dev < TABLE;
+    if (cached && have[dev].load(std::memory_order_acquire) >= bytes) return hipSuccess;
+    std::lock_guard<std::mutex> lock(mu);
+    if (cached && have[dev].load(std::memory_order_relaxed) >= bytes) return hipSuccess;
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        e != hipSuccess)
+        return e;
+    if (cached) have[dev].store(bytes, std::memory_order_release);
+    return hipSuccess;
+}
+
 // Number of workgroups the fused pass wants for n rows on a device with n_cu CUs.
 int fused_grid(int64_t n, int n_cu);
 size_t fused_lds_bytes(int k);
@@ -136,11 +160,8 @@ int fused_gram_tiles(int k);  // number of qflag entries the guard writes for st
 // Launchers.  Return hipSuccess or the launch error.
 hipError_t launch_pass_em(int k, int grid, const PassArgs &a, hipStream_t s);
 hipError_t launch_pass_post(int k, int grid, const PassArgs &a, hipStream_t s);
-// The EM pass as an eight-wave workgroup, two roles (ppca_em8.hip): front waves stage / [G | b] / solve / cross, back
-// waves contract the mask-side statistics on the int8 MFMA.  Honours a.qflag like the int8 instantiation of pass_kernel.
-bool em8_covers(int k);
-hipError_t launch_em8(int k, int grid, const PassArgs &a, hipStream_t s);
-// The same with the per-sample solve pipelined across tiles (ppca_em9.hip; PPCA_EM9=1).
+// The EM pass as an eight-wave workgroup, two roles (ppca_em9.hip): front waves stage / [G | b] / solve (pipelined across tiles) /
+// cross, back waves contract the mask-side statistics on the int8 MFMA.  Honours a.qflag like the int8 instantiation of pass_kernel.
 bool em9_covers(int k);
 hipError_t launch_em9(int k, int grid, const PassArgs &a, hipStream_t s);
 hipError_t em9_debug_counters(unsigned long long *out4, int reset, hipStream_t s);
@@ -164,8 +185,7 @@ struct Em16Launch {
     int no_llk;
     double *dbg;
 };
-// diagnostic counters of the int8 statistics contraction (see ppca_em8.hip): read (and optionally reset) on the current device
-hipError_t em8_debug_counters(unsigned long long *out4, int reset, hipStream_t s);
+// diagnostic counters of the int8 statistics contraction (see ppca_em9.hip): read (and optionally reset) on the current device
 hipError_t em16_debug_counters(unsigned long long *out4, int reset, hipStream_t s);
 bool em16_covers(int d, int k);
 int em16_ncol(int k);

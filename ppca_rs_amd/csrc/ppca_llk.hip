@@ -25,7 +25,6 @@
 // Per-sample arithmetic is that of pass_kernel except for the ORDER of the |x~|^2 sum (same int8-sliced Gram behind
 // the same guard, same Cholesky), so the llks agree with it to rounding.  The guard's fallback is
 // pass_kernel<K, false, 4, false>.
-#include <atomic>
 #include <cstdlib>
 
 #include "ppca_device.hpp"
@@ -105,11 +104,7 @@ __global__ __launch_bounds__(256) void llk2_kernel(PassArgs p) {
     // One descriptor per tile (base = its first row, extent = its real rows): the row is a scalar offset, the lane
     // a constant VGPR, the half an immediate.  Rows past n read as zeros ("observed", but no lane's sample).
     auto load_tile = [&](int64_t tile) {
-#ifdef LLK2_DIAG_RESIDENT  // measurement only: every tile re-reads the workgroup's first one (L2-resident: the sweep without HBM)
-        const int rel0 = 0;
-#else
         const int rel0 = (int)(tile - tile_begin) * B;
-#endif
         int cnt = nrel - rel0;
         cnt = __builtin_amdgcn_readfirstlane(cnt < 0 ? 0 : (cnt > B ? B : cnt));  // (keeps the descriptor scalar)
         const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -656,8 +651,8 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
     // Round r: [its first tile was staged during round r - 1's solver step] contract A, stage B, contract B, then the solver step of
     // the round's 64 samples on wave 0 WHILE the other seven waves stage the first tile of round r + 1 (wave 0 stages its four rows
     // behind its solver step).  Until round 6 the other waves stood at the barrier during the solver step (a sixth of the round by
-    // ablation, LLK8_EXP_NOSOLVE: 2.36 -> 1.97 ms at N = 4 M) and everybody staged the first tile afterwards (another sixth,
-    // LLK8_EXP_NOSTAGE0: 1.98 ms).
+    // ablation, a build without the step's arithmetic: 2.36 -> 1.97 ms at N = 4 M) and everybody staged the first tile afterwards
+    // (another sixth, a build without that staging: 1.98 ms).
 #ifdef LLK8_TIMING  // (diagnostic build: per-phase cycle sums of wave 0 -- and the overlapped staging of wave 1 -- into the scalars)
     long long tq[6] = {0, 0, 0, 0, 0, 0}, tl = clock64();
 #define L8_STAMP(i) { __builtin_amdgcn_sched_barrier(0); const long long tn = clock64(); tq[i] += tn - tl; tl = tn; __builtin_amdgcn_sched_barrier(0); }
@@ -707,11 +702,6 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
                 if (lane == 0) __hip_atomic_fetch_add(hand, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 load_tile(tile + 3);
             }
-#ifdef LLK8_EXP_NOSOLVE  // (timing experiment, results wrong: the round without the arithmetic of its one-wave solver step)
-          if (p.d < 0) {
-#else
-          {
-#endif
             const int slot = lane >> 5, i = lane & (B - 1);
             const int mrs = slot == 1 ? B : (par ? 2 * B : 0);
             const int64_t t = tile + slot;
@@ -745,9 +735,7 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
                 (void)xx; (void)m; (void)wgt; (void)pm; (void)pe;
                 if constexpr (ROLES) kill_table();
             }
-          }
         }
-#ifndef LLK8_EXP_NOSTAGE0  // (timing experiment, results wrong: the rounds without the staging of their first tile)
         if (more) {  // the first tile of the next round (its rows have been in registers since this round's second staging)
             ++handed;
             if (wave != SOLVER) {
@@ -769,7 +757,6 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
                 }
             }
         }
-#endif
         L8_STAMP(2)
         if constexpr (OUT != 0) {
             __syncthreads();
@@ -996,16 +983,7 @@ static bool llk8_enabled() {  // PPCA_LLK8=0: the four-wave llk2_kernel (A/B run
 template <int K>
 static hipError_t launch_llk8_t(int grid, const PassArgs &a, hipStream_t s) {
     const size_t lds = sizeof(double) * CfgL8<K>::LDS_DOUBLES;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&llk8_kernel<K>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = ensure_dynamic_lds<llk8_kernel<K>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((llk8_kernel<K>), dim3(grid), dim3(512), lds, s, a);
     return hipGetLastError();
 }
@@ -1014,16 +992,7 @@ template <int K>
 static hipError_t launch_llk2_t(int grid, const PassArgs &a, hipStream_t s) {
     if (llk8_enabled()) return launch_llk8_t<K>(grid, a, s);
     const size_t lds = sizeof(double) * CfgL<K>::LDS_DOUBLES;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&llk2_kernel<K>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = ensure_dynamic_lds<llk2_kernel<K>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((llk2_kernel<K>), dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }
@@ -1031,16 +1000,7 @@ static hipError_t launch_llk2_t(int grid, const PassArgs &a, hipStream_t s) {
 template <int K>
 static hipError_t launch_mix_llk8_t(int grid, const MixLlkArgs &a, hipStream_t s) {
     const size_t lds = sizeof(double) * CfgL8<K>::LDS_DOUBLES;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mix_llk8_kernel<K>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = ensure_dynamic_lds<mix_llk8_kernel<K>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((mix_llk8_kernel<K>), dim3(grid), dim3(512), lds, s, a);
     return hipGetLastError();
 }
@@ -1048,16 +1008,7 @@ static hipError_t launch_mix_llk8_t(int grid, const MixLlkArgs &a, hipStream_t s
 template <int K, int OUT>
 static hipError_t launch_recon8_t(int grid, const PassArgs &a, hipStream_t s) {
     const size_t lds = sizeof(double) * CfgL8<K>::LDS_DOUBLES;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&recon8_kernel<K, OUT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = ensure_dynamic_lds<recon8_kernel<K, OUT>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((recon8_kernel<K, OUT>), dim3(grid), dim3(512), lds, s, a);
     return hipGetLastError();
 }

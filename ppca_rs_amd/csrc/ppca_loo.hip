@@ -210,11 +210,7 @@ hipError_t launch_loo(const double *X, int64_t ldx, int d, int k, int64_t n_rows
     const size_t lds = loo_lds_bytes(k);
     LooArgs a{X, ldx, d, k, n_rows, model, states, covs, mean, var, ell, llks};
     const int64_t grid = std::min<int64_t>(n_rows, (int64_t)std::max(n_cu, 1) * 8);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&loo_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds > 64 * 1024 ? ensure_dynamic_lds<loo_kernel>(lds) : hipSuccess; e != hipSuccess) return e;
     hipLaunchKernelGGL(loo_kernel, dim3((unsigned)grid), dim3(LOO_THREADS), lds, s, a);
     return hipGetLastError();
 }

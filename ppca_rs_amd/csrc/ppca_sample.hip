@@ -156,11 +156,7 @@ hipError_t launch_posterior_draw(const double *X, int64_t ldx, int d, int k, int
                                  uint64_t seed, const int *choice, int comp, int n_cu, hipStream_t s) {
     if (n_rows <= 0) return hipSuccess;
     const size_t lds = posterior_draw_lds_bytes(k);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&posterior_draw_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds > 64 * 1024 ? ensure_dynamic_lds<posterior_draw_kernel>(lds) : hipSuccess; e != hipSuccess) return e;
     const int64_t grid = std::min<int64_t>(n_rows, (int64_t)std::max(n_cu, 1) * 32);
     DrawArgs a{X, ldx, d, k, n_rows, row0, row_offset, model, states, covs, out, mode, seed, choice, comp};
     hipLaunchKernelGGL(posterior_draw_kernel, dim3((unsigned)grid), dim3(64), lds, s, a);

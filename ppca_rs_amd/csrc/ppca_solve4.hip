@@ -20,7 +20,6 @@
 //   * the packed index -> (LDS offset, row, column) map is a table built once per workgroup.
 // The padding (k < n) is re-initialised for every group of samples (a non-finite entry must not leak into the next group).
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -550,15 +549,7 @@ hipError_t launch_solve4_t(const SolveArgs &a, int n_cu, hipStream_t s) {
     const int64_t groups = (a.n + NS - 1) / NS;
     int grid = (int)std::min<int64_t>((groups + W - 1) / W, (int64_t)n_cu);
     if (grid < 1) grid = 1;
-    static std::atomic<unsigned long long> done{0ull};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&solve4_kernel<NB, EM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = ensure_dynamic_lds<solve4_kernel<NB, EM>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((solve4_kernel<NB, EM>), dim3(grid), dim3(64 * W), lds, s, a);
     return hipGetLastError();
 }

@@ -1,8 +1,8 @@
 """The STEADY STATE of the fused kernels under the oracle.
 
 The fused kernels start min(tiles, CUs) persistent workgroups, so at the sizes the CPU oracle affords (N <= 20 000) a
-workgroup of the 256-CU part walks at most three 32-sample tiles -- what only exists from tile 2-4 onwards (em8's
-three-tile mask ring and its two-blocks-deep pipelined contraction, the periodic flush of the int64 accumulators every
+workgroup of the 256-CU part walks at most three 32-sample tiles -- what only exists from tile 2-4 onwards (em9's
+four-tile mask ring and its two-blocks-deep pipelined contraction, the periodic flush of the int64 accumulators every
 100 groups, a raise of the fixed-point exponents with a contraction pending; em16's next-tile prefetch, LDS-parked factor
 and hand-over ring; the two-tile rounds of the llk sweep) would only ever be compared with itself.  Here:
 
@@ -70,7 +70,7 @@ def _assert_stats(got, want, d, k, tol, tag):
 
 def _gathered_stats(P, ctx, ds, m, u):
     """One component pass of the mixture (ppca_mix_component_stats): weights exp(u - max u), rows of negligible weight
-    dropped and the others GATHERED -- em8_kernel<K, true, true>."""
+    dropped and the others GATHERED -- em9_kernel<K, true, true>."""
     import torch
     from ppca_rs_amd import _lib
 
@@ -86,7 +86,7 @@ def _gathered_stats(P, ctx, ds, m, u):
 
 @pytest.mark.parametrize("k,d", [(1, 64), (4, 200), (7, 255), (10, 256)])
 def test_eight_wave_em_pass_steady_state(P, oracle, ctx, k, d):
-    """em8_kernel (weighted, un-weighted and gathered instantiations) with ~300 tiles per workgroup: the three-tile mask
+    """em9_kernel (weighted, un-weighted and gathered instantiations) with ~300 tiles per workgroup: the mask
     ring, the pipelined contraction, the tiles-cut counter and (beyond 200 tiles) the periodic int64 flush all fire; the
     whole statistics buffer against the literal oracle."""
     n = 20_000
@@ -187,7 +187,7 @@ def test_fixed_point_form_rescales_inside_one_workgroup(P, oracle, ctx, k, d):
     few tiles -- contract what is pending under the old exponents, flush the int64 accumulators into the partial, raise
     the exponents, cut the tile again --, asserted through the rescale counter; descending, the exponents stay where the
     first tile put them and the later rows are cut far below it (precision relative to the LARGEST terms, as in any fp64
-    sum).  em8_kernel's back role (k <= 10) and sstat16_kernel (k >= 11), against the oracle."""
+    sum).  em9_kernel's back role (k <= 10) and sstat16_kernel (k >= 11), against the oracle."""
     n = 6_000
     rng = np.random.default_rng(800 + k)
     x, _, _ = oracle.synth(n, d, k, 0.3, 7300 + k)
@@ -541,16 +541,14 @@ def test_heavy_tailed_fuzz_of_the_fixed_point_statistics():
     assert r.returncode == 0 and "fuzz2 ok" in r.stdout, (r.stdout[-800:], r.stderr[-1500:])
 
 
-@pytest.mark.parametrize("em9", ["0", "1"])
-def test_both_eight_wave_kernels_against_the_oracle(em9):
-    """tools/em9_check.py in a child process (the switch is read once per process): em9_kernel (the default: the solve
-    pipelined across tiles) and em8_kernel (PPCA_EM9=0, round 3's) at N = 20 000 on the full grid and on 2 / 1 workgroups,
-    weighted and not, and on ragged shapes down to one row -- every block of the statistics within 1e-9 of the oracle."""
+def test_eight_wave_em_kernel_against_the_oracle():
+    """tools/em9_check.py in a child process: em9_kernel (the eight-wave EM pass, the solve pipelined across tiles) at
+    N = 20 000 on the full grid and on 2 / 1 workgroups, weighted and not, and on ragged shapes down to one row -- every
+    block of the statistics within 1e-9 of the oracle."""
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PPCA_EM9=em9)
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "em9_check.py")], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "em9_check.py")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "em9 check ok" in r.stdout, (r.stdout[-800:], r.stderr[-1500:])

@@ -1,0 +1,94 @@
+"""Are the kernels of two trees the same machine code?  For a refactor that must not change code generation.
+
+    python tools/compare_kernels.py --build TREE OUT     device code of TREE's ppca_rs_amd/csrc/*.hip -> OUT/<name>.elf (gfx950,
+                                                         the flags of ppca_rs_amd/build.py; needs no GPU)
+    python tools/compare_kernels.py OLD NEW              compares two such directories
+
+Per kernel symbol: the bytes of its function in .text with the disassembly's own addresses left out (a function that moved is
+still the same function), and .vgpr_count / .sgpr_count / .group_segment_fixed_size / .private_segment_fixed_size of its metadata
+note.  Prints one line per file and every kernel that differs, appeared or disappeared; exits 1 when a kernel present on both
+sides differs or one appeared (kernels that disappeared are listed: whether they were meant to go is the reader's call).
+Whole files are not compared: two builds of identical code differ in a few bytes outside the sections.
+"""
+import os
+import re
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+LLVM = os.path.join(ROCM, "lib", "llvm", "bin")
+META = (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size")
+
+
+def build(tree, out):
+    csrc = os.path.join(tree, "ppca_rs_amd", "csrc")
+    os.makedirs(out, exist_ok=True)
+
+    def one(src):
+        base = os.path.join(out, src[:-4])
+        subprocess.check_call([os.path.join(ROCM, "bin", "hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only",
+                               "-c", os.path.join(csrc, src), "-o", base + ".co"])
+        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + base + ".co",
+                               "--targets=hip-amdgcn-amd-amdhsa--gfx950", "--output=" + base + ".elf"])
+        os.remove(base + ".co")
+
+    srcs = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and f not in ("ppca_capi.hip", "ppca_comm.hip"))  # (host only)
+    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as ex:
+        list(ex.map(one, srcs))
+
+
+def kernels(elf):
+    """{kernel symbol: (code without addresses, metadata tuple)}"""
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", elf], check=True, capture_output=True, text=True).stdout
+    meta = {}
+    for blk in re.split(r"\n\s*- \.agpr_count:|\n\s*- \.args:", notes)[1:]:
+        sym = re.search(r"\.symbol:\s+'?([^\s']+?)\.kd'?\s", blk)
+        if sym:
+            meta[sym.group(1)] = tuple(int(re.search(re.escape(k) + r":\s+(\d+)", blk).group(1)) for k in META)
+    dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-leading-addr", elf], check=True, capture_output=True, text=True).stdout
+    code, cur = {}, None
+    for ln in dis.split("\n"):
+        m = re.match(r"<(\S+)>:$", ln)
+        if m:
+            cur = m.group(1)
+            code[cur] = []
+        elif cur is not None and ln.strip():
+            code[cur].append(re.sub(r"\s*//\s*[0-9A-Fa-f]+:", " //", ln))  # the trailing "// address: encoding" keeps the encoding
+    return {k: ("\n".join(code.get(k, [])), v) for k, v in meta.items()}
+
+
+def main(old, new):
+    bad = 0
+    for f in sorted(set(os.listdir(old)) | set(os.listdir(new))):
+        if not f.endswith(".elf"):
+            continue
+        if not os.path.exists(os.path.join(new, f)):
+            print("%-22s only in OLD (%d kernels)" % (f, len(kernels(os.path.join(old, f)))))
+            continue
+        if not os.path.exists(os.path.join(old, f)):
+            print("%-22s only in NEW" % f)
+            bad += 1
+            continue
+        a, b = kernels(os.path.join(old, f)), kernels(os.path.join(new, f))
+        both = sorted(set(a) & set(b))
+        diff = [k for k in both if a[k] != b[k]]
+        gone, came = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+        print("%-22s old %3d  new %3d  identical %3d  differ %d  gone %d  new-only %d" % (f, len(a), len(b), len(both) - len(diff), len(diff), len(gone), len(came)))
+        for k in diff:
+            print("   DIFFERS  %s  %s meta %s -> %s" % (k, "code" if a[k][0] != b[k][0] else "", a[k][1], b[k][1]))
+        for k in gone:
+            print("   gone     %s" % k)
+        for k in came:
+            print("   NEW      %s" % k)
+        bad += len(diff) + len(came)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--build":
+        build(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) == 3:
+        sys.exit(main(sys.argv[1], sys.argv[2]))
+    else:
+        sys.exit(__doc__)

@@ -13,6 +13,6 @@ name = name[0] if name else "gen"
 obj = "/tmp/ppca_generic.%s.o" % name
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *flags, "-c", os.path.join(C, "ppca_generic.hip"), "-o", obj])
 out = os.path.join(ROOT, "ppca_rs_amd", "libppca_hip_%s.so" % name)
-objs = [obj] + [os.path.join(C, f) for f in ("ppca_kernels.o", "ppca_em8.o", "ppca_em9.o", "ppca_em16.o", "ppca_llk.o", "ppca_solve4.o", "ppca_comm.o", "ppca_capi.o")]
+objs = [obj] + [os.path.join(C, f) for f in ("ppca_kernels.o", "ppca_em9.o", "ppca_em16.o", "ppca_llk.o", "ppca_solve4.o", "ppca_comm.o", "ppca_capi.o")]
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs)
 print(out)

@@ -1,4 +1,4 @@
-"""Parity of the pipelined-solve variant (PPCA_EM9=1) against the oracle: N = 20 000 on the full grid and on 2 / 1 workgroups,
+"""Parity of em9_kernel (the eight-wave EM pass with the solve pipelined across tiles) against the oracle: N = 20 000 on the full grid and on 2 / 1 workgroups,
 weighted and not, plus ragged shapes (diagnostic; tools/devbuild.py libraries hold k = 10 only)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,4 +31,4 @@ for (n, d, k) in ((20000, 256, 10), (97, 256, 10), (33, 200, 10), (4001, 255, 10
                 e = rel(got[lo:hi], want[lo:hi]); worst = max(worst, e)
                 assert e < 1e-9, (n, d, cap, ww is None, name, e)
 ctx.set_grid_limit(0)
-print("em9 check ok (PPCA_EM9=%s): worst block-relative deviation %.2e" % (os.environ.get("PPCA_EM9"), worst))
+print("em9 check ok: worst block-relative deviation %.2e" % worst)

@@ -1,6 +1,6 @@
-"""Instruction mix of one kernel of an ISA listing (hipcc -S), split at '; E8_MARK n' / '; PPCA_MARK n' comments.
+"""Instruction mix of one kernel of an ISA listing (hipcc -S), split at '; PPCA_MARK n' / '; E16_MARK n' comments.
 
-    python tools/isa_mix.py /tmp/em8.s 'em8_kernelILi10ELb0ELb0'
+    python tools/isa_mix.py /tmp/em9.s 'em9_kernelILi10ELb0ELb0'
 Classes: valu (v_* except MFMA), mfma64 (v_mfma_f64*), mfma8 (v_mfma_i32*), lds (ds_*), vmem (buffer_/global_/scratch_),
 salu (s_* except waitcnt/nop/barrier/branch), wait (s_waitcnt/s_nop/s_barrier/s_sleep), branch."""
 import re, sys, collections
@@ -34,7 +34,7 @@ def main(path, sym):
             break
         if t.startswith(".Lfunc_end"):
             break
-        m = re.match(r";\s*(E8_MARK|PPCA_MARK|E16_MARK)\s+(\S+)", t)
+        m = re.match(r";\s*(PPCA_MARK|E16_MARK)\s+(\S+)", t)
         if m:
             seg = "after mark " + m.group(2) + " #%d" % len(counts)
             continue

@@ -1,6 +1,6 @@
 """Code-object metadata of the kernels in an object / shared library built by hipcc: registers, spills, scratch, LDS.
 
-    python tools/kernel_meta.py ppca_rs_amd/csrc/ppca_em8.o [name-filter]
+    python tools/kernel_meta.py ppca_rs_amd/csrc/ppca_em9.o [name-filter]
 """
 import os, re, subprocess, sys, tempfile
 

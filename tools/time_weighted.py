@@ -1,4 +1,4 @@
-"""EM pass of the fused shapes on an unweighted dataset, a weighted one (em8_kernel<K, false, true>) and through the
+"""EM pass of the fused shapes on an unweighted dataset, a weighted one (em9_kernel<K, false, true>) and through the
 mixture's gathered form is not reachable from here: times ppca_em_accumulate per call (diagnostic)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
