@@ -356,6 +356,48 @@ int ppca_ctx_set_heavy_rows(ppca_ctx *ctx, int32_t max_rows);
  * accumulators, [2] the largest number of tiles one workgroup walked, [3] launches.  Synchronises. */
 int ppca_debug_counters(ppca_ctx *ctx, int64_t *out8, int32_t reset);
 
+/* Test hook: what the HOST side of the split pipeline (ppca_generic.hip + ppca_solve4.hip: every shape with d > 256 or k > 16, and the
+ * output passes of k = 11..16) decided in the most recent pass of this context that went through it -- which kernel variant, tile,
+ * addressing form, K-split and grid each of its size-gated branches took, accumulated over the pass's chunks.  Host integers written
+ * where the launches are made: no device work, no synchronisation, nothing about a launch changes.  With ppca_ctx_set_grid_limit a test
+ * puts an oracle-sized dataset on the large-N side of a threshold and ASSERTS through this record that the branch ran.  Launch lists
+ * keep the first PPCA_TRACE_LAUNCHES entries (the counts go on).  The fused paths (d <= 256, k <= 10; the EM pass of k = 11..16) leave it
+ * alone, except that the latter marks `fused16`. */
+#define PPCA_TRACE_LAUNCHES 32
+typedef struct ppca_generic_trace {
+    int32_t valid;    /* 0 until a pass of this context has gone through the split pipeline */
+    int32_t em;       /* 1 = EM statistics pass, 0 = output pass (llk, states, covariances, reconstructions) */
+    int32_t fused16;  /* 1 = an EM pass handed on to the two-kernel pass of k = 11..16, d <= 256: nothing below is filled */
+    int32_t int8;     /* 1 = the int8-sliced contractions (0: PPCA_GENERIC_FP64=1 or its like pinned the fp64 products) */
+    int32_t d, k, n_cu, chunks;
+    int64_t n, chunk_rows; /* rows of the pass; rows of a full chunk */
+    /* int8 GEMM launches, in launch order.  role: 0 = Gram, 1 = statistics product as ONE launch (nsplit > 1: cut along the samples),
+     * 2 / 3 = the statistics product as a pair: the column blocks that fill the chip, then the last ones cut along the samples */
+    int32_t n_i8gemm;
+    int32_t i8_role[PPCA_TRACE_LAUNCHES], i8_tile_rows[PPCA_TRACE_LAUNCHES], i8_xcd_map[PPCA_TRACE_LAUNCHES];
+    int32_t i8_buffer[PPCA_TRACE_LAUNCHES]; /* 1 = buffer addressing, 0 = pointer arithmetic */
+    int32_t i8_nsplit[PPCA_TRACE_LAUNCHES]; /* slices along the samples (1 = none) */
+    int32_t stats_whole, stats_sliced, stats_pair; /* chunks whose statistics product took each arm */
+    /* fp64 GEMM launches, in launch order.  amode: 0 Gram, 1 b = X~ C, 2 mask^T . B, 3 X~^T . B; guarded: 1 = behind a device-side
+     * guard flag (runs only when the int8 form's guard tripped; the host cannot know) */
+    int32_t n_gemm;
+    int32_t gemm_amode[PPCA_TRACE_LAUNCHES], gemm_kslices[PPCA_TRACE_LAUNCHES], gemm_guarded[PPCA_TRACE_LAUNCHES];
+    /* the one-pass form of the two skinny statistics products: launches, and of the FIRST chunk its column tiles (nt), slices along the
+     * samples, blocks along the dimensions and rows per slice */
+    int32_t skinny_launches, skinny_nt, skinny_slices, skinny_gy;
+    int64_t skinny_rps;
+    /* per-sample solver of the FIRST chunk (the largest).  solver: 1 lane, 2 lane (one wave per SIMD, k >= 13), 3 batched blocked
+     * (solve4), 4 one sample per wave on the MFMA, 5 workgroup per matrix, 6 LDS broadcast, 7 register broadcast, 8 LDS resident;
+     * solver_nb: 16 x 16 blocks per side (3, 4) or k (1, 2); a workgroup takes solver_batch samples per iteration of its loop */
+    int32_t solver, solver_nb, solver_launches;
+    int64_t solver_grid, solver_batch, solver_rows;
+    int32_t scal_launches, scal_blocks_max, scal_accumulated; /* scalar reduction: launches, most blocks, launches ADDING to a previous chunk's */
+    int32_t wdigits_first, wdigits_predicted, wdigits_y_capped; /* chunks cut after / with their column statistics; ... whose re-cut grid was capped */
+    int32_t recon_kind, recon_rpb; /* of the FIRST chunk: 0 none, 1 thread per element, 2 row-block kernel and its rows per block */
+    int64_t recon_grid_x, recon_grid_y;
+} ppca_generic_trace;
+int ppca_generic_last_trace(ppca_ctx *ctx, ppca_generic_trace *out);
+
 /* Which Gram engine the fused passes use for this model: 0 = int8-sliced MFMA with exact integer accumulation,
  * 1 = fp64 MFMA.  Decided on the device per model by a dynamic-range guard (the int8 form keeps 62 bits below each
  * column maximum of vech(c c^T); a model whose rows of C span many orders of magnitude, or whose sigma^2 lies

@@ -55,6 +55,48 @@ class SynthSpec(C.Structure):
     ]
 
 
+TRACE_LAUNCHES = 32  # PPCA_TRACE_LAUNCHES
+
+
+class GenericTrace(C.Structure):
+    """ppca_generic_trace (include/ppca_hip.h): the host-side decisions of the last pass through the split pipeline."""
+
+    _fields_ = [
+        ("valid", C.c_int32), ("em", C.c_int32), ("fused16", C.c_int32), ("int8", C.c_int32),
+        ("d", C.c_int32), ("k", C.c_int32), ("n_cu", C.c_int32), ("chunks", C.c_int32),
+        ("n", C.c_int64), ("chunk_rows", C.c_int64),
+        ("n_i8gemm", C.c_int32),
+        ("i8_role", C.c_int32 * TRACE_LAUNCHES), ("i8_tile_rows", C.c_int32 * TRACE_LAUNCHES), ("i8_xcd_map", C.c_int32 * TRACE_LAUNCHES),
+        ("i8_buffer", C.c_int32 * TRACE_LAUNCHES), ("i8_nsplit", C.c_int32 * TRACE_LAUNCHES),
+        ("stats_whole", C.c_int32), ("stats_sliced", C.c_int32), ("stats_pair", C.c_int32),
+        ("n_gemm", C.c_int32),
+        ("gemm_amode", C.c_int32 * TRACE_LAUNCHES), ("gemm_kslices", C.c_int32 * TRACE_LAUNCHES), ("gemm_guarded", C.c_int32 * TRACE_LAUNCHES),
+        ("skinny_launches", C.c_int32), ("skinny_nt", C.c_int32), ("skinny_slices", C.c_int32), ("skinny_gy", C.c_int32),
+        ("skinny_rps", C.c_int64),
+        ("solver", C.c_int32), ("solver_nb", C.c_int32), ("solver_launches", C.c_int32),
+        ("solver_grid", C.c_int64), ("solver_batch", C.c_int64), ("solver_rows", C.c_int64),
+        ("scal_launches", C.c_int32), ("scal_blocks_max", C.c_int32), ("scal_accumulated", C.c_int32),
+        ("wdigits_first", C.c_int32), ("wdigits_predicted", C.c_int32), ("wdigits_y_capped", C.c_int32),
+        ("recon_kind", C.c_int32), ("recon_rpb", C.c_int32),
+        ("recon_grid_x", C.c_int64), ("recon_grid_y", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain Python values; the launch lists cut to the launches recorded, as lists of dicts (`i8gemm`, `gemm`)."""
+        out = {}
+        for name, typ in self._fields_:
+            v = getattr(self, name)
+            out[name] = int(v) if not isinstance(v, C.Array) else [int(e) for e in v]
+        ni, ng = min(out["n_i8gemm"], TRACE_LAUNCHES), min(out["n_gemm"], TRACE_LAUNCHES)
+        out["i8gemm"] = [{"role": out["i8_role"][i], "tile_rows": out["i8_tile_rows"][i], "xcd_map": out["i8_xcd_map"][i],
+                          "buffer": out["i8_buffer"][i], "nsplit": out["i8_nsplit"][i]} for i in range(ni)]
+        out["gemm"] = [{"amode": out["gemm_amode"][i], "kslices": out["gemm_kslices"][i], "guarded": out["gemm_guarded"][i]}
+                       for i in range(ng)]
+        for name in ("i8_role", "i8_tile_rows", "i8_xcd_map", "i8_buffer", "i8_nsplit", "gemm_amode", "gemm_kslices", "gemm_guarded"):
+            del out[name]
+        return out
+
+
 # name -> (restype, argtypes); every symbol include/ppca_hip.h declares
 SIGNATURES = {
     "ppca_last_error": (C.c_char_p, []),
@@ -126,6 +168,7 @@ SIGNATURES = {
     "ppca_ctx_set_grid_limit": (C.c_int, [C.c_void_p, C.c_int32]),
     "ppca_ctx_set_heavy_rows": (C.c_int, [C.c_void_p, C.c_int32]),
     "ppca_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "ppca_generic_last_trace": (C.c_int, [C.c_void_p, C.POINTER(GenericTrace)]),
     "ppca_em_last_guard": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),
     "ppca_dataset_scale_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_double]),
     "ppca_em_last_fallback": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, C.POINTER(C.c_int64), c_double_p]),
@@ -233,6 +276,13 @@ class Context:
         out = (C.c_int64 * 8)()
         check(lib().ppca_debug_counters(self.handle, out, int(reset)))
         return [int(v) for v in out]
+
+    def generic_trace(self) -> dict:
+        """Test hook (ppca_generic_last_trace): what the host side of the split pipeline decided in this context's last pass through
+        it (GenericTrace.as_dict)."""
+        t = GenericTrace()
+        check(lib().ppca_generic_last_trace(self.handle, C.byref(t)))
+        return t.as_dict()
 
     def last_guard(self):
         """ppca_em_last_guard: (gram_unsafe, stats_unsafe) of the most recent fused EM pass on this context."""

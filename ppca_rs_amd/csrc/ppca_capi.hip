@@ -812,7 +812,7 @@ static int em_accumulate_impl(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model 
             HIP_TRY(hipEventRecord(g0, ctx->stream));
         }
         HIP_TRY(generic_em_accumulate(ds->X, ds->d, ds->w, ds->n, ds->d, model->k, model->p(), stats_dev, ctx->gws->p,
-                                      ctx->n_cu, ctx->stream));
+                                      ctx->n_cu, ctx->stream, &ctx->gen_trace));
         if (ctx->timing) {
             HIP_TRY(hipEventRecord(g1, ctx->stream));
             ctx->events.emplace_back(g0, g1);
@@ -1155,7 +1155,7 @@ static int run_post(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, do
         if (int rc = ensure(ctx->gws, ctx->gws_cap, generic_workspace_bytes(model->d, model->k, ds->n))) return rc;
         double *scal8 = static_cast<double *>(ctx->scal->p);
         HIP_TRY(generic_post(ds->X, ds->d, ds->w, ds->n, ds->d, model->k, model->p(), scal8, llks_dev, states_dev,
-                             covs_dev, recon_dev, recon_mode, ctx->gws->p, ctx->n_cu, ctx->stream));
+                             covs_dev, recon_dev, recon_mode, ctx->gws->p, ctx->n_cu, ctx->stream, &ctx->gen_trace));
         if (scal_out) *scal_out = scal8;
         return PPCA_OK;
     }
@@ -2206,6 +2206,13 @@ extern "C" int ppca_debug_counters(ppca_ctx *ctx, int64_t *out8, int32_t reset) 
     HIP_TRY(em9_debug_counters(c, reset, ctx->stream));
     HIP_TRY(em16_debug_counters(c + 4, reset, ctx->stream));
     for (int i = 0; i < 8; ++i) out8[i] = (int64_t)c[i];
+    return PPCA_OK;
+}
+
+extern "C" int ppca_generic_last_trace(ppca_ctx *ctx, ppca_generic_trace *out) {
+    if (!ctx || !out) return fail(PPCA_ERR_INVALID, "null argument");
+    USE_CTX(ctx);  // (the passes write the record under the same lock)
+    *out = ctx->gen_trace;
     return PPCA_OK;
 }
 

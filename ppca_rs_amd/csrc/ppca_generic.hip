@@ -25,6 +25,23 @@ namespace ppca {
 
 typedef double d4g_t __attribute__((ext_vector_type(4)));
 
+// ------------------------------------------------------------------ dispatch trace (test hook: ppca_generic_last_trace)
+// generic_run points this at its caller's record for the length of the call; per thread, as concurrent passes are.
+static thread_local ppca_generic_trace *t_trace = nullptr;
+ppca_generic_trace *generic_trace_sink() { return t_trace; }
+namespace {
+struct TraceScope {
+    ppca_generic_trace *prev;
+    explicit TraceScope(ppca_generic_trace *t) : prev(t_trace) { t_trace = t; }
+    ~TraceScope() { t_trace = prev; }
+};
+void trace_solver(int kind, int nb, int64_t grid, int64_t batch, int64_t rows) {
+    ppca_generic_trace *t = t_trace;
+    if (!t || t->solver_launches++ != 0) return;
+    t->solver = kind; t->solver_nb = nb; t->solver_grid = grid; t->solver_batch = batch; t->solver_rows = rows;
+}
+}  // namespace
+
 template <class F, int... I>
 __device__ __forceinline__ void static_for_g_impl(F &&f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -333,6 +350,9 @@ static bool launch_skinny_xt(const double *X, int64_t ldx, int64_t n, int d, int
     const int64_t rps = ((n + slices - 1) / slices + 3) / 4 * 4;
     slices = (n + rps - 1) / rps;
     dim3 grid((unsigned)slices, (unsigned)gy);
+    if (ppca_generic_trace *t = t_trace; t && t->skinny_launches++ == 0) {
+        t->skinny_nt = nt; t->skinny_slices = (int)slices; t->skinny_gy = gy; t->skinny_rps = rps;
+    }
     switch (nt) {
         case 1: hipLaunchKernelGGL((skinny_xt_kernel<1, 4>), grid, dim3(256), 0, s, X, ldx, n, d, mean, Bz, ncols, rps, part_ws); break;
         case 2: hipLaunchKernelGGL((skinny_xt_kernel<2, 4>), grid, dim3(256), 0, s, X, ldx, n, d, mean, Bz, ncols, rps, part_ws); break;
@@ -1575,6 +1595,7 @@ static hipError_t launch_solve_big(const SolveArgs &a, int n_cu, hipStream_t s) 
     const size_t lds = solve_big_lds(a.k);
     if (hipError_t e = ensure_dynamic_lds<solve_big_kernel>(lds); e != hipSuccess) return e;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(a.n, (int64_t)n_cu));
+    trace_solver(5, a.k, grid, 1, a.n);
     hipLaunchKernelGGL(solve_big_kernel, dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }
@@ -1678,6 +1699,7 @@ static hipError_t launch_solve_lane(const SolveArgs &a, int n_cu, hipStream_t s)
     int64_t blocks = (a.n + 255) / 256;
     if (blocks > 8 * (int64_t)n_cu) blocks = 8 * (int64_t)n_cu;
     if (blocks < 1) blocks = 1;
+    trace_solver(K >= 13 ? 2 : 1, K, blocks, 256, a.n);
     if constexpr (K >= 13) {
         if (a.em) hipLaunchKernelGGL((solve_lane_wide_kernel<K, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((solve_lane_wide_kernel<K, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
@@ -2004,6 +2026,7 @@ template <int KPAD>
 static hipError_t launch_solve_bc(const SolveArgs &a, int grid, hipStream_t s) {
     const size_t lds = sizeof(double) * 4 * KPAD * KPAD;
     if (hipError_t e = lds > 65536 ? ensure_dynamic_lds<solve_bc_kernel<KPAD>>(lds) : hipSuccess; e != hipSuccess) return e;
+    trace_solver(6, KPAD / 16, grid, 4, a.n);
     hipLaunchKernelGGL((solve_bc_kernel<KPAD>), dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }
@@ -2308,6 +2331,7 @@ static hipError_t launch_solve_mfma(const SolveArgs &a, int n_cu, hipStream_t s)
     }();
     int grid = (int)std::min<int64_t>((a.n + W - 1) / W, (int64_t)n_cu * (occ2 ? 2 : 1));
     if (grid < 1) grid = 1;
+    trace_solver(4, NB, grid, W, a.n);
     if (lds > 65536) {
         if (hipError_t e = ensure_dynamic_lds<solve_mfma_kernel<NB>>(lds); e != hipSuccess) return e;
         if constexpr (NB <= 4) {
@@ -2376,6 +2400,7 @@ static hipError_t launch_solve(const SolveArgs &a, int n_cu, hipStream_t s) {
         if (a.k <= 32) return launch_solve_bc<32>(a, grid, s);
         return launch_solve_bc<64>(a, grid, s);
     }
+    trace_solver(7, (a.k + 15) / 16, grid, 4, a.n);
     if (a.k <= 16) hipLaunchKernelGGL((solve_reg_kernel<16>), dim3(grid), dim3(256), 0, s, a);
     else if (a.k <= 32) hipLaunchKernelGGL((solve_reg_kernel<32>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((solve_reg_kernel<64>), dim3(grid), dim3(256), 0, s, a);
@@ -2709,7 +2734,8 @@ static bool i8gemm_s256() {
     }();
     return v;
 }
-static hipError_t launch_i8gemm(const I8GemmArgs &g, hipStream_t s) {
+// role: what the product is, for the dispatch trace only (ppca_generic_trace::i8_role)
+static hipError_t launch_i8gemm(const I8GemmArgs &g, hipStream_t s, int role) {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     static const int tm = [] {  // PPCA_I8GEMM_TM=128: the 4-wave tile everywhere (A/B runs)
         const char *e = getenv("PPCA_I8GEMM_TM");
@@ -2744,6 +2770,11 @@ static hipError_t launch_i8gemm(const I8GemmArgs &g, hipStream_t s) {
     h.xcd_map = (xcd && h.ncb >= 16) ? 1 : 0;
     dim3 grid((unsigned)h.ncb, (unsigned)h.nrb, (unsigned)nz);
     if (h.xcd_map) grid = dim3((unsigned)(8 * ((h.ncb + 7) / 8) * h.nrb * nz), 1u, 1u);
+    if (ppca_generic_trace *t = t_trace) {
+        if (const int i = t->n_i8gemm++; i < PPCA_TRACE_LAUNCHES) {
+            t->i8_role[i] = role; t->i8_tile_rows[i] = tmr; t->i8_xcd_map[i] = h.xcd_map; t->i8_buffer[i] = buf ? 1 : 0; t->i8_nsplit[i] = nz;
+        }
+    }
     if (tall) e = buf ? launch_i8gemm_t<256, true>(h, grid, s) : launch_i8gemm_t<256, false>(h, grid, s);
     else e = buf ? launch_i8gemm_t<128, true>(h, grid, s) : launch_i8gemm_t<128, false>(h, grid, s);
     if (e != hipSuccess) return e;
@@ -2788,7 +2819,15 @@ static hipError_t launch_gemm(GemmArgs g, hipStream_t s, int n_cu = 256, double 
         ksplit = std::min<int64_t>(ksplit, part_cap / std::max<int64_t>(1, g.M * g.N));
         if (ksplit > 64) ksplit = 64;
     }
+    const auto trace = [&](int nslices) {
+        ppca_generic_trace *t = t_trace;
+        if (!t) return;
+        if (const int i = t->n_gemm++; i < PPCA_TRACE_LAUNCHES) {
+            t->gemm_amode[i] = AMODE; t->gemm_guarded[i] = g.guard ? 1 : 0; t->gemm_kslices[i] = nslices;
+        }
+    };
     if (ksplit <= 1) {
+        trace(1);
         g.part = nullptr;
         dim3 grid((unsigned)((g.N + T - 1) / T), (unsigned)((g.M + T - 1) / T));
         hipLaunchKernelGGL((gemm_kernel<AMODE>), grid, dim3(256), 0, s, g);
@@ -2797,6 +2836,7 @@ static hipError_t launch_gemm(GemmArgs g, hipStream_t s, int n_cu = 256, double 
     g.part = part_ws;
     g.kslice = ((g.K + ksplit - 1) / ksplit + 15) / 16 * 16;
     const int nsl = (int)((g.K + g.kslice - 1) / g.kslice);
+    trace(nsl);
     dim3 grid((unsigned)((g.N + T - 1) / T), (unsigned)((g.M + T - 1) / T), (unsigned)nsl);
     hipLaunchKernelGGL((gemm_kernel<AMODE>), grid, dim3(256), 0, s, g);
     hipError_t e = hipGetLastError();
@@ -2906,10 +2946,16 @@ static hipError_t run_em16(const double *X, int64_t ldx, const double *w, int64_
 static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k,
                               const double *model, bool em, double *stats,
                               double *scal8, double *llks, double *states, double *covs, double *recon, int recon_mode,
-                              void *ws, int n_cu, hipStream_t s) {
+                              void *ws, int n_cu, hipStream_t s, ppca_generic_trace *trace) {
     const int64_t kp = (int64_t)k * (k + 1) / 2;
     const StatsLayout L(d, k);
     GenWs W = carve(ws, d, k, n);
+    const TraceScope trace_scope(trace);
+    if (trace) {
+        *trace = ppca_generic_trace{};
+        trace->valid = 1; trace->em = em ? 1 : 0; trace->d = d; trace->k = k; trace->n_cu = n_cu; trace->n = n;
+        trace->chunk_rows = W.chunk; trace->chunks = (int)((n + W.chunk - 1) / W.chunk);
+    }
     const double *mean = model + MODEL_HDR + (int64_t)d * k;
     const double *Cm = model + MODEL_HDR;
     // (round 6) k = 65 .. 128 run the int8-sliced contractions too (their tables, guards and the int8 GEMM are not bound in k; only the
@@ -2919,7 +2965,11 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
         return e && atoi(e) == 1;
     }();
     const bool i8 = generic_i8() && (k <= 64 || !big_fp64);
-    if (em && i8 && em16_enabled() && em16_covers(d, k)) return run_em16(X, ldx, w, n, d, k, model, stats, W, n_cu, s);
+    if (trace) trace->int8 = i8 ? 1 : 0;
+    if (em && i8 && em16_enabled() && em16_covers(d, k)) {
+        if (trace) trace->fused16 = 1;
+        return run_em16(X, ldx, w, n, d, k, model, stats, W, n_cu, s);
+    }
     {
         const int64_t tot = (int64_t)d * kp;
         hipLaunchKernelGGL(qtab_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, model, d, k, W.Q);
@@ -2971,7 +3021,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
             q.tile_rows = gram_tile;
             q.M = nc; q.N = kp; q.K = W.dpad; q.scale = W.scaleQ; q.out = W.G; q.ldo = kp; q.accumulate = 0;
             q.guard = W.flags;
-            GTRY(launch_i8gemm(q, s));
+            GTRY(launch_i8gemm(q, s, 0));
         }
         // G = Mask . Q (fp64 MFMA; with the int8 form enabled: only when its guard tripped)
         g.B = W.Q; g.ldb = kp; g.M = nc; g.N = kp; g.K = d;
@@ -2994,6 +3044,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
         if (getenv("PPCA_GENERIC_LDS_SOLVE")) {  // the LDS-resident variant, kept for A/B runs
             int sgrid = (int)std::min<int64_t>((nc + 1) / 2, (int64_t)n_cu);
             if (sgrid < 1) sgrid = 1;
+            trace_solver(8, (k + 15) / 16, sgrid, 2, nc);
             hipLaunchKernelGGL(solve_kernel, dim3(sgrid), dim3(128), solve_lds(k), s, a);
             GTRY(hipGetLastError());
         } else {
@@ -3002,6 +3053,11 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
         double *scal = em ? stats + L.scalars : scal8;
         {
             const int sb = (int)((nc + SCAL_ROWS - 1) / SCAL_ROWS);
+            if (ppca_generic_trace *t = t_trace) {
+                ++t->scal_launches;
+                t->scal_blocks_max = std::max(t->scal_blocks_max, sb);
+                if (r0 > 0) ++t->scal_accumulated;
+            }
             hipLaunchKernelGGL(scal_reduce_kernel, dim3((unsigned)sb), dim3(256), 0, s, W.sc, wc, nc, W.spart);
             hipLaunchKernelGGL(scal_final_kernel, dim3(1), dim3(256), 0, s, W.spart, sb, scal, (em || r0 > 0) ? 1 : 0);
             GTRY(hipGetLastError());
@@ -3019,6 +3075,10 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                 const int nb = (int)((nc + 255) / 256);
                 dim3 dg((unsigned)((kp + 63) / 64), (unsigned)(ncpad / 64));
                 const dim3 lg((unsigned)((kp + 31) / 32), (unsigned)nb);
+                if (ppca_generic_trace *t = t_trace) {
+                    ++((wpred && r0 > 0) ? t->wdigits_predicted : t->wdigits_first);
+                    if (wpred && r0 > 0 && dg.y > 256u) ++t->wdigits_y_capped;
+                }
                 if (wpred && r0 > 0) {
                     hipLaunchKernelGGL(gen_wdigits_lines_kernel, lg, dim3(256), 0, s, W.G, nc, ncpad, (int)kp, W.npad, W.predW,
                                        W.BtW, W.colpart, W.flags, 1);
@@ -3058,7 +3118,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                         // tile times.  Both launches go through the same kernel; the slices are added in slice order.
                         I8GemmArgs q1 = q;
                         q1.N = (ncb - rest) * 32;
-                        GTRY(launch_i8gemm(q1, s));
+                        GTRY(launch_i8gemm(q1, s, 2));
                         I8GemmArgs q2 = q;
                         const int64_t c0 = q1.N;
                         q2.Bt = q.Bt + c0 * q.ldb;
@@ -3074,8 +3134,9 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                             q2.nsplit = (int)((ncpad + q2.ksplit - 1) / q2.ksplit);
                             q2.out2 = W.part;
                         }
-                        GTRY(launch_i8gemm(q2, s));
+                        GTRY(launch_i8gemm(q2, s, 3));
                         launched = true;
+                        if (t_trace) ++t_trace->stats_pair;
                     } else if (tiles < slots) {
                         // ... and a grid far below it leaves the chip idle: cut the samples into enough slices to fill it
                         int64_t ns = (slots + tiles - 1) / tiles;
@@ -3089,7 +3150,10 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                         }
                     }
                 }
-                if (!launched)                 GTRY(launch_i8gemm(q, s));
+                if (!launched) {
+                    GTRY(launch_i8gemm(q, s, 1));
+                    if (t_trace) ++(q.ksplit > 0 ? t_trace->stats_sliced : t_trace->stats_whole);
+                }
             }
             // S += Mask^T . wP (fp64 MFMA; with the int8 form enabled: only when the chunk's guard tripped)
             g.B = W.G; g.ldb = kp; g.M = d; g.N = kp; g.K = nc;
@@ -3115,6 +3179,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                 return e && e[0] == 'n';
             }();
             if (naive || k > 64) {
+                if (t_trace && r0 == 0) t_trace->recon_kind = 1;
                 const int64_t tot = nc * d;
                 hipLaunchKernelGGL(recon_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, Xc, ldx, nc, d, k,
                                    model, W.Bz, W.G, recon_mode, recon + r0 * d);
@@ -3122,6 +3187,9 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                 // rows per block: enough blocks to fill the chip a few times over, at least 16 rows to amortise the row of C
                 int rpb = (int)std::max<int64_t>(16, std::min<int64_t>(256, nc / (8 * (int64_t)n_cu) + 1));
                 const dim3 rg((unsigned)((nc + rpb - 1) / rpb), (unsigned)((d + 255) / 256));
+                if (ppca_generic_trace *t = t_trace; t && r0 == 0) {
+                    t->recon_kind = 2; t->recon_rpb = rpb; t->recon_grid_x = rg.x; t->recon_grid_y = rg.y;
+                }
                 if (k <= 16) hipLaunchKernelGGL((recon2_kernel<16>), rg, dim3(256), 0, s, Xc, ldx, nc, d, k, model, W.Bz, W.G, recon_mode, recon + r0 * d, rpb);
                 else if (k <= 32) hipLaunchKernelGGL((recon2_kernel<32>), rg, dim3(256), 0, s, Xc, ldx, nc, d, k, model, W.Bz, W.G, recon_mode, recon + r0 * d, rpb);
                 else hipLaunchKernelGGL((recon2_kernel<64>), rg, dim3(256), 0, s, Xc, ldx, nc, d, k, model, W.Bz, W.G, recon_mode, recon + r0 * d, rpb);
@@ -3173,17 +3241,17 @@ hipError_t generic_gram_guard(int d, int k, const double *model, void *ws, hipSt
 }
 
 hipError_t generic_em_accumulate(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k,
-                                 const double *model, double *stats, void *ws, int n_cu, hipStream_t s) {
+                                 const double *model, double *stats, void *ws, int n_cu, hipStream_t s, ppca_generic_trace *trace) {
     return generic_run(X, ldx, w, n, d, k, model, true, stats, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                       ws, n_cu, s);
+                       ws, n_cu, s, trace);
 }
 
 hipError_t generic_post(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k, const double *model,
                         double *scal8, double *llks, double *states, double *covs,
-                        double *recon, int recon_mode, void *ws, int n_cu, hipStream_t s) {
+                        double *recon, int recon_mode, void *ws, int n_cu, hipStream_t s, ppca_generic_trace *trace) {
     if (n == 0) return hipMemsetAsync(scal8, 0, sizeof(double) * 8, s);
     return generic_run(X, ldx, w, n, d, k, model, false, nullptr, scal8, llks, states, covs, recon,
-                       recon_mode, ws, n_cu, s);
+                       recon_mode, ws, n_cu, s, trace);
 }
 
 hipError_t generic_finalize(int k, int d, const double *stats, const double *model_in, double *model_out, double tau,

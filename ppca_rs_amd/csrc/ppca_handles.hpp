@@ -82,6 +82,7 @@ struct ppca_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events2;  // (timing) the second stage of the guarded EM passes: fallback + reduction
     BufRef gws;   // workspace of the generic split pipeline
     size_t gws_cap = 0;
+    ppca_generic_trace gen_trace{};  // host-side decisions of the last pass through the split pipeline (ppca_generic_last_trace)
     // mixture scratch, kept across iterations (hipMalloc / hipFree of hundreds of MB per component cost more than
     // the kernels): 0 llk, 1 u, 2 lse, 3 log posteriors, 4 component weights, 5 row list, 6 block counts
     BufRef mix[7];

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <mutex>
 
+#include "../../include/ppca_hip.h"
 #include "ppca_small.hpp"
 
 namespace ppca {
@@ -247,13 +248,15 @@ hipError_t launch_mfma_probe(const double *a16x4, const double *b4x16, double *o
 
 // generic split pipeline (ppca_generic.hip): any d, k <= GENERIC_MAX_K (k <= 64 on the tuned kernels; 65..128 on fp64 contractions and a
 // workgroup-per-matrix solver whose k x k matrix is what 160 KB of LDS hold: correct, no performance claim)
+// trace (nullable): the record of the pass's host-side decisions, overwritten (test hook: ppca_generic_last_trace)
 constexpr int GENERIC_MAX_K = 128;
 size_t generic_workspace_bytes(int d, int k, int64_t n);
 hipError_t generic_em_accumulate(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k,
-                                 const double *model, double *stats, void *ws, int n_cu, hipStream_t s);
+                                 const double *model, double *stats, void *ws, int n_cu, hipStream_t s,
+                                 ppca_generic_trace *trace);
 hipError_t generic_post(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k, const double *model,
                         double *scal8, double *llks, double *states, double *covs, double *recon, int recon_mode,
-                        void *ws, int n_cu, hipStream_t s);
+                        void *ws, int n_cu, hipStream_t s, ppca_generic_trace *trace);
 hipError_t generic_gram_guard(int d, int k, const double *model, void *ws, hipStream_t s, const int **flag_dev, int *forced);
 hipError_t generic_finalize(int k, int d, const double *stats, const double *model_in, double *model_out, double tau,
                             int has_ig, double alpha, double beta, int n_cu, hipStream_t s);

@@ -6,7 +6,13 @@
 
 #include <cstdint>
 
+#include "../../include/ppca_hip.h"
+
 namespace ppca {
+
+// The dispatch record of the split-pipeline pass running on this thread (ppca_generic_last_trace), or nullptr when its caller keeps
+// none: the launchers note what they decided, host integers only.
+ppca_generic_trace *generic_trace_sink();
 
 struct SolveArgs {
     double *G;        // [n][kp] in: packed Gram; out (EM): w P packed

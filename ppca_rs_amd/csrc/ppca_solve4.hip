@@ -549,6 +549,9 @@ hipError_t launch_solve4_t(const SolveArgs &a, int n_cu, hipStream_t s) {
     const int64_t groups = (a.n + NS - 1) / NS;
     int grid = (int)std::min<int64_t>((groups + W - 1) / W, (int64_t)n_cu);
     if (grid < 1) grid = 1;
+    if (ppca_generic_trace *t = generic_trace_sink(); t && t->solver_launches++ == 0) {
+        t->solver = 3; t->solver_nb = NB; t->solver_grid = grid; t->solver_batch = W * NS; t->solver_rows = a.n;
+    }
     if (hipError_t e = ensure_dynamic_lds<solve4_kernel<NB, EM>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((solve4_kernel<NB, EM>), dim3(grid), dim3(64 * W), lds, s, a);
     return hipGetLastError();

@@ -26,6 +26,26 @@ def test_header_symbols_exported(hiplib):
     assert hiplib.ppca_abi_version() == 6
 
 
+def test_generic_trace_layout_matches_the_header(tmp_path):
+    """ppca_generic_trace as ctypes declares it (_lib.GenericTrace) against the C compiler's layout of include/ppca_hip.h: size and the
+    offset of every field."""
+    import ctypes
+    import subprocess
+
+    from ppca_rs_amd import _lib
+
+    names = [n for n, _ in _lib.GenericTrace._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppca_hip.h"\nint main(void) {\n'
+                   '    printf("%zu %d\\n", sizeof(ppca_generic_trace), PPCA_TRACE_LAUNCHES);\n'
+                   + "".join('    printf("%%zu\\n", offsetof(ppca_generic_trace, %s));\n' % n for n in names) + "    return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
+    assert [int(out[0]), int(out[1])] == [ctypes.sizeof(_lib.GenericTrace), _lib.TRACE_LAUNCHES]
+    assert [int(v) for v in out[2:]] == [getattr(_lib.GenericTrace, n).offset for n in names]
+
+
 def test_path_kind_and_stats_len(hiplib):
     assert hiplib.ppca_path_kind(256, 10) == 1
     assert hiplib.ppca_path_kind(32, 4) == 1
