@@ -230,6 +230,44 @@ int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *mod
 int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, ppca_dataset **mean_out, ppca_dataset **var_out,
                         double *total_host, double *per_sample_host);
 
+/* ------------------------------------- factor analysis: per-column noise */
+/* An extension with no reference counterpart: x = C z + mean + eps with eps_j ~ N(0, psi_j^2), one noise level per column.  Dividing
+ * column j by s_j = psi_j turns it into the isotropic model: with A = diag(1/s) C, mean~ = mean / s and Y = X diag(1/s) (masked
+ * entries stay masked), PPCAModel(1, A, mean~) on Y has the posterior (z_i, Sigma_i) of the FA model on X, and
+ * llks_FA(x_i) = llks_PPCA(y_i) - sum_{j observed in i} ln s_j.  An FA model is three host arrays: noise (d), transform (d x k), mean (d).
+ *
+ * ppca_dataset_scale_columns: one streaming pass over the dataset with per-column host vectors a, b, l (d each; b, l nullable = 0):
+ *   out     (nullable) a new dataset carrying the input weights: x_ij a_j (one fp64 multiply) on observed entries, NaN on masked
+ *           ones; with out == NULL no N x d buffer is allocated or written
+ *   col_sums_host (nullable, 3 d): tot_j = sum_i w_i m_ij | sum_j = sum_i w_i m_ij (x_ij a_j - b_j) | sq_j = sum_i w_i m_ij (x_ij a_j - b_j)^2
+ *   row_sums (nullable, n; host or device, as ppca_llk's per-sample output): sum_j m_ij l_j
+ * Column sums go through per-workgroup partials added in a fixed order (no float atomics): bit-reproducible for a given grid; out
+ * and row_sums do not depend on the grid at all.  At least one output is given.  Synchronises. */
+int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const double *a_host, const double *b_host, const double *l_host,
+                               ppca_dataset **out, double *col_sums_host, double *row_sums);
+/* out_ij = x_ij, bit-exact, where ds is observed; fill_ij a_j elsewhere (fill: a dataset of the same shape; a_host: d).  A new
+ * dataset carrying the weights of ds: the last step of the FA model's extrapolate.  Synchronises. */
+int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *fill, const double *a_host, ppca_dataset **out);
+/* The FA M-step on host buffers (no GPU needed, like ppca_em_finalize_host).  stats: the packed statistics of the EM pass of
+ * PPCAModel(1, A, mean~) on Y; sq_j = sum_i w_i m_ij (y_ij - mean~_j)^2 (ppca_dataset_scale_columns with a = 1 / s, b = mean / s);
+ * min_noise (d, nullable = 0).  Per column j, tot = totals_j -- an ECM step, each block maximised given the blocks already
+ * updated, so the log-likelihood cannot decrease:
+ *   1. a_j = solution of S_j a = cross_j by the Cholesky row solve; a pivot <= 0 keeps the old row c_j / s_j; no prior term
+ *   2. delta_j = (sumx_j - a_j . U_j) / tot with the NEW a_j (0 if tot = 0); mean~_j += delta_j
+ *   3. psi~_j^2 = (sq_j - 2 a_j . cross_j + a_j^T S_j a_j - delta_j^2 tot) / tot with the new a_j, delta_j; psi~_j = 1 if tot = 0 or the
+ *      value is non-finite or <= 0
+ *   4. c_j = s_j a_j, mean_j = s_j mean~_j, psi_j = max(s_j psi~_j, min_noise_j)
+ * Outputs may not alias inputs. */
+int ppca_fa_finalize_host(int32_t d, int32_t k, const double *noise, const double *transform, const double *mean, const double *stats,
+                          const double *sq, const double *min_noise, double *noise_out, double *transform_out, double *mean_out);
+/* One FA EM iteration on a single GPU: whiten + sq (ppca_dataset_scale_columns), ppca_em_accumulate on the whitened dataset, the
+ * statistics to the host, ppca_fa_finalize_host; the whitened dataset is released before returning (peak device memory: twice the
+ * dataset).  llk_in (nullable): log-likelihood of the INPUT FA model, the pass's by-product minus sum_j totals_j ln s_j.  One
+ * synchronisation per call. */
+int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, const double *noise, const double *transform,
+                    const double *mean, const double *min_noise, double *noise_out, double *transform_out, double *mean_out,
+                    double *llk_in);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration

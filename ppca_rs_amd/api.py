@@ -117,6 +117,38 @@ class Dataset:
         check(lib().ppca_dataset_empty_dimensions(self._h, flags))
         return [j for j in range(self._d) if flags[j]]
 
+    def _scale_columns(self, a, b=None, l=None, *, out: bool = True, col_sums: bool = False, row_sums: bool = False):
+        """ppca_dataset_scale_columns: (x * a as a new Dataset or None, (tot, sum, sq) of x * a - b or None, row sums of l over
+        the observed entries or None) from one streaming pass."""
+        d = self._d
+        a, b, l = f64(a, (d,)), (f64(b, (d,)) if b is not None else None), (f64(l, (d,)) if l is not None else None)
+        h = C.c_void_p()
+        sums = np.empty((3, d)) if col_sums else None
+        rows = np.empty(len(self)) if row_sums else None
+        check(lib().ppca_dataset_scale_columns(self._ctx.handle, self._h, ptr(a), ptr(b), ptr(l), C.byref(h) if out else None,
+                                               ptr(sums), ptr(rows)))
+        return (Dataset._wrap(h, self._ctx) if out else None), sums, rows
+
+    def _fill_masked(self, fill: "Dataset", a) -> "Dataset":
+        """ppca_dataset_fill_masked: this dataset's observed entries as they are, fill * a elsewhere."""
+        h = C.c_void_p()
+        check(lib().ppca_dataset_fill_masked(self._ctx.handle, self._h, fill._h, ptr(f64(a, (self._d,))), C.byref(h)))
+        return Dataset._wrap(h, self._ctx)
+
+    def column_stats(self):
+        """(totals, means, variances) of every column over its observed entries, weighted: totals_j = sum_i w_i m_ij, the
+        weighted mean, and the weighted mean of the squared deviations from it (0 for a column with no observed entry).  Two
+        sums-only sweeps on the GPU (the second centred on the means of the first, so that the variance does not cancel)."""
+        d = self._d
+        one = np.ones(d)
+        _, s1, _ = self._scale_columns(one, out=False, col_sums=True)
+        tot = s1[0]
+        safe = np.where(tot > 0.0, tot, 1.0)
+        mean = np.where(tot > 0.0, s1[1] / safe, 0.0)
+        _, s2, _ = self._scale_columns(one, mean, out=False, col_sums=True)
+        var = np.where(tot > 0.0, s2[2] / safe - (s2[1] / safe) ** 2, 0.0)
+        return tot, mean, np.maximum(var, 0.0)
+
     def chunks(self, chunks: int) -> "DatasetChunks":
         """Iterator over ceil(N / chunks)-row slices (src/python_bindings.rs:110-118)."""
         return DatasetChunks(self, chunks)
@@ -689,6 +721,204 @@ class PPCATrainer:
                 model = new_model
             else:
                 model = model.iterate_with_prior(self.dataset, prior) if prior is not None else model.iterate(self.dataset)
+        return model.to_canonical()
+
+
+# --------------------------------------------------------------------------- factor analysis (per-column noise)
+class InferredFA:
+    """What FAModel.infer returns: the per-sample posterior means and covariances of the latent state."""
+
+    def __init__(self, states: np.ndarray, covs: np.ndarray):
+        self._states, self._covs = states, covs
+
+    def states(self) -> np.ndarray:
+        if self._states.shape[0] == 0:
+            return np.zeros((0, 0))
+        return self._states.copy()
+
+    def covariances(self) -> List[np.ndarray]:
+        return [c.copy() for c in self._covs]
+
+
+class FAModel:
+    """Masked factor analysis: y = C x + mean + noise, x ~ N(0, I), noise_j ~ N(0, noise[j]^2) -- PPCAModel with one noise level
+    per column (an extension with no reference counterpart; include/ppca_hip.h).
+
+    Every pass runs the PPCA kernels on the dataset with column j divided by noise[j] (`whitened()` is the model of that
+    dataset); the whitened copy is made on the GPU for the call and released with it: at most one is alive at a time.
+    """
+
+    def __init__(self, noise, transform, mean, *, ctx=None):
+        base = PPCAModel(1.0, transform, mean, ctx=ctx)  # (the checks of transform and mean are PPCAModel's)
+        n = np.array(noise, dtype=np.float64)
+        if n.ndim != 1 or n.shape[0] != base.output_size:
+            raise ValueError(f"noise must have shape ({base.output_size},): one level per column")
+        if not (np.all(np.isfinite(n)) and np.all(n > 0.0)):
+            raise ValueError("every entry of noise must be a positive finite number")
+        self._noise, self._c, self._mean, self._ctx = n, base._c, base._mean, ctx
+        self._noise.setflags(write=False)
+
+    # -- getters ----------------------------------------------------------------
+    @property
+    def noise(self) -> np.ndarray:
+        return self._noise.copy()
+
+    @property
+    def transform(self) -> np.ndarray:
+        return self._c.copy()
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self._mean.copy()
+
+    @property
+    def output_size(self) -> int:
+        return int(self._c.shape[0])
+
+    @property
+    def state_size(self) -> int:
+        return int(self._c.shape[1])
+
+    @property
+    def n_parameters(self) -> int:
+        return 2 * self.output_size + self.output_size * self.state_size
+
+    def __repr__(self) -> str:
+        return f"FAModel(noise=array({self._noise}), transform=array({self._c}), mean=array({self._mean}))"
+
+    # -- construction -------------------------------------------------------------
+    @staticmethod
+    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None) -> "FAModel":
+        """The transform of PPCAModel.init (same seed, same draw), noise = 1, mean = 0."""
+        m = PPCAModel.init(state_size, dataset, seed=seed)
+        return FAModel(np.ones(m.output_size), m._c, m._mean)
+
+    @staticmethod
+    def from_ppca(model: PPCAModel) -> "FAModel":
+        """The FA model equal to an isotropic one: noise = sigma on every column."""
+        return FAModel(np.full(model.output_size, model.isotropic_noise), model._c, model._mean)
+
+    def whitened(self) -> PPCAModel:
+        """PPCAModel(1, diag(1 / noise) C, mean / noise): the model of the dataset whose column j is divided by noise[j]."""
+        return PPCAModel(1.0, self._c / self._noise[:, None], self._mean / self._noise, ctx=self._ctx)
+
+    def to_canonical(self) -> "FAModel":
+        """The rotation of PPCAModel.to_canonical on C; noise and mean are untouched."""
+        return FAModel(self._noise, PPCAModel(1.0, self._c, self._mean).to_canonical()._c, self._mean)
+
+    def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None, *, ctx=None) -> Dataset:
+        """The whitened model's `sample` (generated on the GPU) with column j multiplied by noise[j]."""
+        white = self.whitened().sample(dataset_size, mask_prob, seed, ctx=ctx or self._ctx)
+        return white._scale_columns(self._noise)[0]
+
+    # -- passes ---------------------------------------------------------------------
+    def _whiten(self, dataset: Dataset, **kw):
+        if dataset._d != self.output_size:
+            raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {self.output_size}")
+        return dataset._scale_columns(1.0 / self._noise, **kw)
+
+    def llks(self, dataset: Dataset) -> np.ndarray:
+        """Per-sample log-likelihood: the whitened model's on the whitened rows minus the sum of ln noise[j] over the row's
+        observed entries."""
+        y, _, jac = self._whiten(dataset, l=np.log(self._noise), row_sums=True)
+        return self.whitened().llks(y) - jac
+
+    def llk(self, dataset: Dataset) -> float:
+        """Weighted log-likelihood."""
+        y, sums, _ = self._whiten(dataset, col_sums=True)
+        return self.whitened().llk(y) - float(np.dot(sums[0], np.log(self._noise)))
+
+    def infer(self, dataset: Dataset) -> InferredFA:
+        """Posterior of the latent state of every sample (that of the whitened model on the whitened rows)."""
+        inf = self.whitened().infer(self._whiten(dataset)[0])
+        return InferredFA(inf._states, inf._covs)
+
+    def smooth(self, dataset: Dataset) -> Dataset:
+        """C z + mean for every dimension."""
+        sm = self.whitened().smooth(self._whiten(dataset)[0])  # (the whitened copy is released here)
+        return sm._scale_columns(self._noise)[0]
+
+    def extrapolate(self, dataset: Dataset) -> Dataset:
+        """Observed values kept bit for bit, masked ones replaced by C z + mean."""
+        sm = self.whitened().smooth(self._whiten(dataset)[0])
+        return dataset._fill_masked(sm, self._noise)
+
+    def _iterate(self, dataset: Dataset, min_noise, want_llk: bool):
+        ctx = dataset._ctx
+        if len(dataset) == 0:
+            raise ValueError("dataset is empty")
+        d, k = self.output_size, self.state_size
+        if dataset._d != d:
+            raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {d}")
+        floor = None
+        if min_noise is not None:
+            floor = np.ascontiguousarray(np.broadcast_to(np.asarray(min_noise, dtype=np.float64), (d,)))
+        n_out, c_out, m_out = np.empty(d), np.empty((d, k)), np.empty(d)
+        llk = C.c_double(0.0)
+        check(lib().ppca_fa_em_step(ctx.handle, dataset._h, d, k, ptr(self._noise), ptr(self._c), ptr(self._mean), ptr(floor),
+                                    ptr(n_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
+        return FAModel(n_out, c_out, m_out, ctx=self._ctx), (llk.value if want_llk else None)
+
+    def iterate(self, dataset: Dataset, min_noise=None) -> "FAModel":
+        """One ECM iteration (transform, then mean, then noise, each given the ones before it: the log-likelihood cannot
+        decrease).  min_noise: a floor for the new noise, a number or one per column."""
+        return self._iterate(dataset, min_noise, False)[0]
+
+    def iterate_with_llk(self, dataset: Dataset, min_noise=None):
+        """(next model, llk of THIS model) from the same pass."""
+        return self._iterate(dataset, min_noise, True)
+
+    # -- serialisation (own npz container) ----------------------------------------------
+    def dump(self) -> bytes:
+        buf = io.BytesIO()
+        np.savez(buf, kind="ppca_rs_amd.FAModel", noise=self._noise, transform=self._c, mean=self._mean)
+        return buf.getvalue()
+
+    @staticmethod
+    def load(data: bytes) -> "FAModel":
+        try:
+            z = np.load(io.BytesIO(data), allow_pickle=False)
+            if str(z["kind"]) != "ppca_rs_amd.FAModel":
+                raise ValueError(f"not an FAModel container: {z['kind']}")
+            return FAModel(z["noise"], z["transform"], z["mean"])
+        except Exception as err:
+            raise Exception(str(err))
+
+    def __getstate__(self):
+        return self.dump()
+
+    def __setstate__(self, state):
+        o = FAModel.load(state)
+        self.__dict__.update(o.__dict__)
+
+    def __getnewargs__(self):
+        return (self.noise, self.transform, self.mean)
+
+
+@dataclass
+class FATrainer:
+    """EM driver of FAModel: the loop and metrics of PPCATrainer."""
+
+    dataset: Dataset
+
+    def train(self, *, state_size: int, n_iters: int = 10, start: Optional[FAModel] = None,
+              metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False, seed: Optional[int] = None,
+              min_noise_ratio: float = 1e-3) -> FAModel:
+        """min_noise_ratio: the new noise of column j is kept at or above ratio x the column's observed standard deviation -- a guard
+        against a noise level collapsing to 0 (a Heywood case), not a tuned number: at 1e-3 it bounds the share of a column's
+        variance the latent state may explain at 1 - 1e-6."""
+        model = start or FAModel.init(state_size, self.dataset, seed=seed)
+        n = len(self.dataset)
+        floor = min_noise_ratio * np.sqrt(self.dataset.column_stats()[2])
+        for idx in range(n_iters):
+            if not quiet:
+                # the llk of the current model is a by-product of the EM pass: no second sweep
+                new_model, llk = model.iterate_with_llk(self.dataset, floor)
+                metrics = _metrics(llk, model.n_parameters, n)
+                print(f"Masked FA iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
+                model = new_model
+            else:
+                model = model.iterate(self.dataset, floor)
         return model.to_canonical()
 
 

@@ -2285,3 +2285,180 @@ extern "C" int ppca_debug_mfma_i8_probe(ppca_ctx *ctx, const int8_t *a_regs, con
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PPCA_OK;
 }
+
+// ------------------------------------------------------------------ factor analysis (per-column noise)
+// The per-column vectors [a | b | l] of a scale pass on the device (b, l nullable = 0).
+static int upload_abl(ppca_ctx *ctx, int d, const double *a, const double *b, const double *l, BufRef *out) {
+    std::vector<double> h((size_t)3 * d, 0.0);
+    std::memcpy(h.data(), a, sizeof(double) * d);
+    if (b) std::memcpy(h.data() + d, b, sizeof(double) * d);
+    if (l) std::memcpy(h.data() + (size_t)2 * d, l, sizeof(double) * d);
+    if (int rc = dev_alloc(sizeof(double) * h.size(), out)) return rc;
+    HIP_TRY(hipMemcpyAsync((*out)->p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (h leaves scope)
+    return PPCA_OK;
+}
+
+extern "C" int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const double *a_host, const double *b_host,
+                                          const double *l_host, ppca_dataset **out, double *col_sums_host, double *row_sums) {
+    if (!ctx || !ds || !a_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!out && !col_sums_host && !row_sums) return fail(PPCA_ERR_INVALID, "no output requested");
+    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int d = ds->d;
+    std::unique_ptr<ppca_dataset> nd;
+    if (out) {
+        nd = std::make_unique<ppca_dataset>();
+        nd->ctx = ctx;
+        nd->n = n;
+        nd->d = d;
+        nd->wbuf = ds->wbuf;  // the input weights carried over, as ppca_reconstruct does
+        nd->w = ds->w;
+        if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1) * d, &nd->xbuf)) return rc;
+        nd->X = static_cast<const double *>(nd->xbuf->p);
+    }
+    std::vector<double> sums((size_t)3 * d, 0.0);
+    if (n > 0) {
+        BufRef abl, part, rs;
+        if (int rc = upload_abl(ctx, d, a_host, b_host, l_host, &abl)) return rc;
+        const int grid = scale_grid(n, d, ctx->n_cu);
+        if (int rc = dev_alloc(sizeof(double) * ((size_t)grid + 1) * 3 * d, &part)) return rc;
+        if (row_sums)
+            if (int rc = dev_alloc(sizeof(double) * (size_t)n, &rs)) return rc;
+        double *p = static_cast<double *>(part->p), *red = p + (size_t)grid * 3 * d;
+        HIP_TRY(launch_scale_columns(ds->X, ds->d, ds->w, n, d, static_cast<const double *>(abl->p),
+                                     nd ? static_cast<double *>(nd->xbuf->p) : nullptr, p, grid, rs ? static_cast<double *>(rs->p) : nullptr,
+                                     ctx->stream));
+        if (col_sums_host) {
+            HIP_TRY(launch_reduce_partials(p, grid, (int64_t)3 * d, red, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(sums.data(), red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (row_sums)  // (host or device destination, as ppca_llk's per-sample output)
+            HIP_TRY(hipMemcpyAsync(row_sums, rs->p, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (col_sums_host) std::memcpy(col_sums_host, sums.data(), sizeof(double) * sums.size());
+    if (out) *out = nd.release();
+    return PPCA_OK;
+}
+
+extern "C" int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *fill, const double *a_host, ppca_dataset **out) {
+    if (!ctx || !ds || !fill || !a_host || !out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (ds->n != fill->n || ds->d != fill->d) return fail(PPCA_ERR_INVALID, "the two datasets differ in shape");
+    if (ds->ctx->device != ctx->device || fill->ctx->device != ctx->device)
+        return fail(PPCA_ERR_INVALID, "datasets and context live on different devices");
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int d = ds->d;
+    auto nd = std::make_unique<ppca_dataset>();
+    nd->ctx = ctx;
+    nd->n = n;
+    nd->d = d;
+    nd->wbuf = ds->wbuf;
+    nd->w = ds->w;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1) * d, &nd->xbuf)) return rc;
+    nd->X = static_cast<const double *>(nd->xbuf->p);
+    if (n > 0) {
+        BufRef abl;
+        if (int rc = upload_abl(ctx, d, a_host, nullptr, nullptr, &abl)) return rc;
+        HIP_TRY(launch_fill_masked(ds->X, ds->d, fill->X, fill->d, n, d, static_cast<const double *>(abl->p),
+                                   static_cast<double *>(nd->xbuf->p), ctx->n_cu, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    *out = nd.release();
+    return PPCA_OK;
+}
+
+extern "C" int ppca_fa_finalize_host(int32_t d, int32_t k, const double *noise, const double *transform, const double *mean,
+                                     const double *stats, const double *sq, const double *min_noise, double *noise_out,
+                                     double *transform_out, double *mean_out) {
+    if (d < 1 || k < 0 || !noise || !mean || !stats || !sq || !noise_out || !mean_out || (k > 0 && (!transform || !transform_out)))
+        return fail(PPCA_ERR_INVALID, "null argument");
+    if (k == 0) {  // state size 0 = one zero column, as ppca_em_finalize_host
+        std::vector<double> c0((size_t)d, 0.0), c1((size_t)d, 0.0);
+        return ppca_fa_finalize_host(d, 1, noise, c0.data(), mean, stats, sq, min_noise, noise_out, c1.data(), mean_out);
+    }
+    const StatsLayout L(d, k);
+    std::vector<double> S((size_t)L.kp), a((size_t)k);
+    for (int j = 0; j < d; ++j) {
+        const double s = noise[j];
+        if (!(s > 0.0) || !std::isfinite(s)) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+        const double *Sj = stats + L.S + (int64_t)j * L.kp, *cr = stats + L.cross + (int64_t)j * k, *Uj = stats + L.U + (int64_t)j * k;
+        const double tot = stats[L.totals + j];
+        // 1. the whitened row: S_j a = cross_j; a pivot <= 0 keeps the old row c_j / s_j
+        for (int e = 0; e < L.kp; ++e) S[e] = Sj[e];
+        for (int b = 0; b < k; ++b) a[b] = cr[b];
+        const bool solved = chol_packed(S.data(), k);
+        if (solved)
+            chol_solve_packed(S.data(), k, a.data());
+        else
+            for (int b = 0; b < k; ++b) a[b] = transform[(int64_t)j * k + b] / s;
+        // 2. the whitened mean moves by delta, with the NEW row
+        double au = 0.0, ac = 0.0, asa = 0.0;
+        for (int b = 0; b < k; ++b) {
+            au += a[b] * Uj[b];
+            ac += a[b] * cr[b];
+            double row = 0.0;
+            for (int c = 0; c < k; ++c) row += Sj[c <= b ? tri(b, c) : tri(c, b)] * a[c];
+            asa += a[b] * row;
+        }
+        const double delta = tot > 0.0 ? (stats[L.sumx + j] - au) / tot : 0.0;
+        // 3. the whitened noise, full form (the row may have been kept)
+        double v = tot > 0.0 ? (sq[j] - 2.0 * ac + asa - delta * delta * tot) / tot : 0.0;
+        const double pt = (tot > 0.0 && std::isfinite(v) && v > 0.0) ? std::sqrt(v) : 1.0;
+        // 4. back to the columns' units (a kept row and an unmoved mean are copied, not rescaled twice)
+        for (int b = 0; b < k; ++b) transform_out[(int64_t)j * k + b] = solved ? s * a[b] : transform[(int64_t)j * k + b];
+        mean_out[j] = delta == 0.0 ? mean[j] : s * (mean[j] / s + delta);
+        const double floor_j = min_noise ? min_noise[j] : 0.0;
+        noise_out[j] = std::max(s * pt, floor_j);
+    }
+    return PPCA_OK;
+}
+
+extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, const double *noise, const double *transform,
+                               const double *mean, const double *min_noise, double *noise_out, double *transform_out,
+                               double *mean_out, double *llk_in) {
+    if (!ctx || !ds || !noise || !mean || !noise_out || !mean_out || d < 1 || k < 0 || (k > 0 && (!transform || !transform_out)))
+        return fail(PPCA_ERR_INVALID, "null argument");
+    if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
+    if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
+    if (int rc = check_path(d, k == 0 ? 1 : k)) return rc;
+    for (int j = 0; j < d; ++j)
+        if (!(noise[j] > 0.0) || !std::isfinite(noise[j])) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+    USE_CTX(ctx);
+    // the whitened model PPCAModel(1, A, mean~) and the whitening vectors a = 1 / s, b = mean / s
+    std::vector<double> inv((size_t)d), mw((size_t)d), A((size_t)d * k), sums((size_t)3 * d);
+    for (int j = 0; j < d; ++j) {
+        inv[j] = 1.0 / noise[j];
+        mw[j] = mean[j] / noise[j];
+        for (int b = 0; b < k; ++b) A[(int64_t)j * k + b] = transform[(int64_t)j * k + b] / noise[j];
+    }
+    struct Held {  // released on every return path; the whitened copy goes back to the context's block cache
+        ppca_dataset *y = nullptr;
+        ppca_model *m = nullptr;
+        ~Held() {
+            ppca_dataset_free(y);
+            ppca_model_free(m);
+        }
+    } held;
+    if (int rc = ppca_dataset_scale_columns(ctx, ds, inv.data(), mw.data(), nullptr, &held.y, sums.data(), nullptr)) return rc;
+    if (int rc = ppca_model_create(ctx, d, k, 1.0, A.data(), mw.data(), &held.m)) return rc;
+    const StatsLayout L(d, held.m->k);
+    if (int rc = ensure(ctx->stats, ctx->stats_cap, sizeof(double) * (size_t)L.len)) return rc;
+    double *stats = static_cast<double *>(ctx->stats->p);
+    ctx->stats_llk_at = -1;  // (the llk in the buffer is the whitened model's: ppca_em_last_llk does not apply)
+    if (int rc = ppca_em_accumulate(ctx, held.y, held.m, stats)) return rc;
+    std::vector<double> h((size_t)L.len);
+    HIP_TRY(hipMemcpyAsync(h.data(), stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (int rc = ppca_fa_finalize_host(d, k, noise, transform, mean, h.data(), sums.data() + (size_t)2 * d, min_noise, noise_out,
+                                       transform_out, mean_out))
+        return rc;
+    if (llk_in) {
+        double jac = 0.0;
+        for (int j = 0; j < d; ++j) jac += h[L.totals + j] * std::log(noise[j]);
+        *llk_in = h[L.scalars + SC_LLK] - jac;
+    }
+    return PPCA_OK;
+}

@@ -288,6 +288,16 @@ hipError_t launch_mix_loo_var(const double *X, int64_t ldx, int d, int64_t n_row
                               const double *m, const double *v, const double *ell, const double *L, const double *mean, double *var,
                               int first, hipStream_t s);
 
+// per-column streaming passes of factor analysis (ppca_scale.hip).  launch_scale_columns: out (nullable, n x d)
+// = x a_j on observed entries, NaN elsewhere; part[grid][3 d] the workgroups' column sums tot / sum / sq of w m, w m (x a - b),
+// w m (x a - b)^2 (reduce with launch_reduce_partials); rowsum (nullable, n) = sum_j m_ij l_j; abl_dev = [a | b | l], 3 d doubles;
+// grid = scale_grid(n, d, n_cu).  launch_fill_masked: out = x where observed (bit-exact), fill a_j elsewhere.
+int scale_grid(int64_t n, int d, int n_cu);
+hipError_t launch_scale_columns(const double *X, int64_t ldx, const double *w, int64_t n, int d, const double *abl_dev, double *out,
+                                double *part, int grid, double *rowsum, hipStream_t s);
+hipError_t launch_fill_masked(const double *X, int64_t ldx, const double *F, int64_t ldf, int64_t n, int d, const double *a_dev,
+                              double *out, int n_cu, hipStream_t s);
+
 // mixture helpers
 // llk: [n_models][n]; logw: [n_models]; w nullable.  Writes u: [n_models][n] =
 // ln w_i + log posterior_ic (-inf when w_i <= 0) and lse[n] (mixture llk per sample).

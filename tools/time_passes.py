@@ -1,7 +1,9 @@
 """Times the output passes that share the per-sample core with the EM pass (llk, llks, infer, smooth,
 extrapolate, covariance diagonal, posterior sample / impute, leave-one-out predictive) through the public API, device-resident inputs (diagnostic);
 then the host posterior sampler (infer + numpy) on a slice of at most 1 M rows.  `--mix NM` adds the mixture's leave-one-out
-predictive over NM components next to its extrapolated covariance diagonal."""
+predictive over NM components next to its extrapolated covariance diagonal.  `--fa` runs ONLY the legs of the factor-analysis
+pass: the column-scale pass with and without output against a device-to-device hipMemcpy of the same N x d array
+in the same process, and one FA iteration against one PPCA iteration; every repetition timed on its own (median, min, max)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -19,6 +21,74 @@ ds = P.Dataset._wrap(h, ctx)
 m = P.PPCAModel.init(k, ds, seed=3).iterate(ds).iterate(ds)
 L = _lib.lib()
 md = m._device(ctx)
+
+def fa_legs(reps=12):
+    hip = C.CDLL(_lib.LIB_PATH)  # (dlsym on the library's handle reaches the HIP runtime it is bound to)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipDeviceSynchronize.argtypes = []
+
+    def series(fn):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts, nbytes):
+        med = float(np.median(ts))
+        print(f"{name:44s} median {med:8.3f} ms  min {ts.min():8.3f}  max {ts.max():8.3f}  max/median {ts.max()/med:5.3f}  "
+              f"{nbytes/med/1e6:8.1f} GB/s  ({reps} repetitions)", flush=True)
+        return med
+
+    rng = np.random.default_rng(5)
+    a, b = rng.uniform(0.5, 2.0, d), rng.standard_normal(d)
+    sums = np.empty((3, d))
+    nd_bytes = 8.0 * n * d
+    dst = C.c_void_p()
+    _lib.check(L.ppca_dataset_scale_columns(ctx.handle, ds._h, _lib.ptr(a), None, None, C.byref(dst), None, None))
+    src_p, dst_p = L.ppca_dataset_device_x(ds._h), L.ppca_dataset_device_x(dst)
+    def copy():
+        assert hip.hipMemcpy(dst_p, src_p, C.c_size_t(int(nd_bytes)), 3) == 0  # hipMemcpyDeviceToDevice
+        assert hip.hipDeviceSynchronize() == 0
+    def scale(with_out):
+        o = C.c_void_p()
+        _lib.check(L.ppca_dataset_scale_columns(ctx.handle, ds._h, _lib.ptr(a), _lib.ptr(b), None, C.byref(o) if with_out else None,
+                                                _lib.ptr(sums), None))
+        if with_out:
+            L.ppca_dataset_free(o)
+    # the copy and the pass alternate, so that both see the same machine
+    t_copy, t_scale = [], []
+    for _ in range(2):
+        t_copy.append(series(copy)); t_scale.append(series(lambda: scale(True)))
+    t_copy, t_scale = np.concatenate(t_copy), np.concatenate(t_scale)
+    reps *= 2
+    c = report("hipMemcpy device to device (N x d)", t_copy, 2 * nd_bytes)
+    s1 = report("scale pass with output (+ column sums)", t_scale, 2 * nd_bytes + 8.0 * n)
+    print(f"  scale pass / copy = {s1 / c:.3f}   (the copy's own spread, max / median: {t_copy.max() / c:.3f})")
+    reps //= 2
+    s0 = report("scale pass, sums only (no N x d output)", series(lambda: scale(False)), nd_bytes)
+    print(f"  sums only / read half of the copy = {s0 / (c / 2):.3f}")
+    L.ppca_dataset_free(dst)
+    # one FA iteration against one PPCA iteration (ppca_em_step), both from the model m
+    out = C.c_void_p()
+    _lib.check(L.ppca_model_alloc(ctx.handle, d, k, C.byref(out)))
+    llk = C.c_double()
+    t_pp = series(lambda: _lib.check(L.ppca_em_step(ctx.handle, ds._h, md.h, None, out, C.byref(llk))))
+    L.ppca_model_free(out)
+    fa = P.FAModel.from_ppca(m)
+    no, co, mo = np.empty(d), np.empty((d, k)), np.empty(d)
+    t_fa = series(lambda: _lib.check(L.ppca_fa_em_step(ctx.handle, ds._h, d, k, _lib.ptr(fa._noise), _lib.ptr(fa._c), _lib.ptr(fa._mean), None,
+                                                       _lib.ptr(no), _lib.ptr(co), _lib.ptr(mo), C.byref(llk))))
+    pp = report("PPCA iteration (ppca_em_step, llk read)", t_pp, nd_bytes)
+    ff = report("FA iteration (ppca_fa_em_step, llk read)", t_fa, 3 * nd_bytes)
+    print(f"  FA / PPCA = {ff / pp:.3f}   (FA - PPCA = {ff - pp:.3f} ms; the scale pass alone: {s1:.3f} ms)")
+
+if "--fa" in sys.argv:
+    fa_legs()
+    sys.exit(0)
 
 def timed(name, fn, bytes_per_sample, reps=5):
     fn(); ctx.synchronize()
