@@ -268,6 +268,51 @@ int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, const
                     const double *mean, const double *min_noise, double *noise_out, double *transform_out, double *mean_out,
                     double *llk_in);
 
+/* ------------------------------------- mixture of factor analysers with shared column noise */
+/* An extension with no reference counterpart (Ghahramani & Hinton's mixture of factor analysers): x | c = C_c z + mean_c + eps with
+ * eps_j ~ N(0, psi_j^2) and P(c) = pi_c: ONE noise vector psi (d) for all components, per component a transform (d x k), a mean (d) and
+ * a log-weight; all components have the same k.  With s = psi, Y = X diag(1/s), A_c = diag(1/s) C_c and mean~_c = mean_c / s the
+ * mixture of PPCAModel(1, A_c, mean~_c) on Y has the component posteriors of the FA mixture on X, and
+ * llks_FAMix(x_i) = logsumexp_c(log pi_c + llks_PPCA_c(y_i)) - sum_{j observed in i} ln s_j.  A model is four host arrays: noise (d),
+ * transforms (n_comp x d x k), means (n_comp x d), log_weights (n_comp).
+ *
+ * ppca_dataset_column_moments_multi: one streaming pass over the dataset for n_comp (1 .. 16) row-weight vectors at once.  e (n_comp x n,
+ * component-major; exactly one of e_host / e_dev is given, as ppca_dataset_with_weights) is used INSTEAD of the dataset's weights; a
+ * non-finite weight counts as 0; a_host (d, nullable = 1); b_host (n_comp x d, nullable = 0).  sums_host [n_comp][3][d]:
+ *   tot_cj = sum_i e_ci m_ij | sum_cj = sum_i e_ci m_ij (x_ij a_j - b_cj) | sq_cj = sum_i e_ci m_ij (x_ij a_j - b_cj)^2
+ * each element centred on its own component's b_cj before it is squared.  a and b must be finite: the mask enters as a factor 0 on the
+ * weight, so a masked entry adds exactly nothing only while its b_cj is finite (a non-finite offset turns the column's sums into NaN
+ * even where every entry is masked, where ppca_dataset_scale_columns would give 0).  Up to 8 components the dataset is read once; 9 .. 16 take
+ * the components in two blocks of 8, each over the rows again.  Per-workgroup partials added in a fixed order (no float atomics):
+ * bit-reproducible for a given grid.  An empty dataset gives zeros.  Synchronises. */
+int ppca_dataset_column_moments_multi(ppca_ctx *ctx, ppca_dataset *ds, const double *e_host, const double *e_dev, int32_t n_comp,
+                                      const double *a_host, const double *b_host, double *sums_host);
+/* The M-step of the FA mixture on host buffers (no GPU needed).  stats: n_comp packed buffers of ppca_stats_len(d, k), component c's the
+ * statistics of the EM pass of PPCAModel(1, A_c, mean~_c) on Y under the row weights w_i r_ic; sq (n_comp x d): sq_cj = sum_i w_i r_ic m_ij
+ * (y_ij - mean~_cj)^2; scale (n_comp, nullable = 1): a factor >= 0 on component c's statistics and sq before the components are pooled
+ * (the component passes weight their rows by exp(u_ic - shift_c) with a shift per component: scale_c = exp(shift_c - max shift));
+ * min_noise (d, nullable = 0).  An ECM step in ppca_fa_finalize_host's block order -- the log-likelihood cannot decrease.  Per column j:
+ *   1. per component a_cj = solution of S_cj a = cross_cj by the Cholesky row solve; a pivot <= 0 keeps the old row; no prior term
+ *   2. delta_cj = (sumx_cj - a_cj . U_cj) / totals_cj with the NEW a_cj (0 if totals_cj = 0); mean~_cj += delta_cj
+ *   3. psi~_j^2 = sum_c scale_c (sq_cj - 2 a_cj . cross_cj + a_cj^T S_cj a_cj - delta_cj^2 totals_cj) / sum_c scale_c totals_cj;
+ *      psi~_j = 1 if the denominator is 0 or the value is non-finite or <= 0
+ *   4. C_cj = s_j a_cj, mean_cj = s_j mean~_cj, psi_j = max(s_j psi~_j, min_noise_j)
+ * Outputs may not alias inputs. */
+int ppca_famix_finalize_host(int32_t d, int32_t k, int32_t n_comp, const double *noise, const double *transforms, const double *means,
+                             const double *stats, const double *sq, const double *scale, const double *min_noise, double *noise_out,
+                             double *transforms_out, double *means_out);
+/* One iteration of the FA mixture on a single GPU (n_comp <= 16), composed from existing passes and the sweep above: whiten + the
+ * weighted column totals (ppca_dataset_scale_columns); the responsibilities of the whitened components on Y; per component the shift,
+ * the gathered weighted EM pass of ppca_mix_em_step's component-by-component form and its weights exp(u_ic - shift_c) into a K x n
+ * buffer; ppca_dataset_column_moments_multi's sweep on Y with a = 1, b_c = mean~_c; statistics to the host;
+ * ppca_famix_finalize_host; log_weights_out = log_softmax_c(ln sum_i w_i r_ic).  Rows with w_i <= 0 contribute nothing.  llk_in
+ * (nullable): log-likelihood of the INPUT model, sum_i w_i lse_i - sum_j tot_j ln s_j.  The whitened copy is released to the block
+ * cache before returning (peak device memory: twice the dataset + 3 n_comp n doubles).  Three synchronisations per call: two inside
+ * ppca_dataset_scale_columns, one for the results. */
+int ppca_famix_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, int32_t n_comp, const double *noise, const double *transforms,
+                       const double *means, const double *log_weights, const double *min_noise, double *noise_out,
+                       double *transforms_out, double *means_out, double *log_weights_out, double *llk_in);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration

@@ -135,6 +135,21 @@ class Dataset:
         check(lib().ppca_dataset_fill_masked(self._ctx.handle, self._h, fill._h, ptr(f64(a, (self._d,))), C.byref(h)))
         return Dataset._wrap(h, self._ctx)
 
+    def _column_moments_multi(self, e, a=None, b=None) -> np.ndarray:
+        """ppca_dataset_column_moments_multi: for K row-weight vectors e (K, N) used INSTEAD of the dataset's weights, a per-column
+        factor a (d, default 1) and per-component offsets b (K, d, default 0), the (K, 3, d) sums tot / sum / sq of e m,
+        e m (x a - b_c), e m (x a - b_c)^2 from one streaming pass over the dataset."""
+        d, n = self._d, len(self)
+        e = f64(e)
+        if e.ndim != 2 or e.shape[1] != n or e.shape[0] < 1:
+            raise ValueError(f"e must have shape (K, {n})")
+        nc = e.shape[0]
+        a = f64(a, (d,)) if a is not None else None
+        b = f64(b, (nc, d)) if b is not None else None
+        sums = np.empty((nc, 3, d))
+        check(lib().ppca_dataset_column_moments_multi(self._ctx.handle, self._h, ptr(e), None, nc, ptr(a), ptr(b), ptr(sums)))
+        return sums
+
     def column_stats(self):
         """(totals, means, variances) of every column over its observed entries, weighted: totals_j = sum_i w_i m_ij, the
         weighted mean, and the weighted mean of the squared deviations from it (0 for a column with no observed entry).  Two
@@ -1280,4 +1295,229 @@ class PPCAMixTrainer:
                 model = new_model
             else:
                 model = model.iterate_with_prior(self.dataset, prior) if prior is not None else model.iterate(self.dataset)
+        return model.to_canonical()
+
+
+# --------------------------------------------------------------------------- mixture of factor analysers (shared column noise)
+class FAMix:
+    """Mixture of factor analysers with ONE noise level per column shared by all components (Ghahramani & Hinton):
+    y | c = C_c x + mean_c + noise, x ~ N(0, I), noise_j ~ N(0, noise[j]^2), P(c) = weights[c] -- FAModel's per-column noise met with
+    PPCAMix's mixture of subspaces (an extension with no reference counterpart; include/ppca_hip.h).  All components
+    have the same state size.
+
+    Every pass runs the PPCAMix kernels on the dataset with column j divided by noise[j] (`whitened()` is the mixture of that
+    dataset): one whitened copy serves every component; it is made on the GPU for the call and released with it.
+    """
+
+    def __init__(self, noise, transforms, means, log_weights, *, ctx=None):
+        t = np.array(transforms, dtype=np.float64, order="C")
+        if t.ndim != 3 or t.shape[0] < 1:
+            raise TypeError("transforms must be a 3-D float64 array (n_models, d, k)")
+        m = np.array(means, dtype=np.float64, order="C")
+        if m.ndim != 2:
+            raise TypeError("means must be a 2-D float64 array (n_models, d)")
+        if m.shape[0] != t.shape[0]:
+            raise ValueError("transforms and means differ in the number of components")
+        lw = f64(log_weights).ravel()
+        if lw.shape[0] != t.shape[0]:
+            raise ValueError("components and log_weights differ in length")
+        first = FAModel(noise, t[0], m[0], ctx=ctx)  # (the checks of noise, transform and mean are FAModel's)
+        self._noise, self._c, self._mean, self._ctx = first._noise, t, m, ctx
+        self._lw = _log_softmax(lw)
+        self._c.setflags(write=False)
+        self._mean.setflags(write=False)
+
+    # -- getters ----------------------------------------------------------------
+    @property
+    def noise(self) -> np.ndarray:
+        return self._noise.copy()
+
+    @property
+    def transforms(self) -> np.ndarray:
+        return self._c.copy()
+
+    @property
+    def means(self) -> np.ndarray:
+        return self._mean.copy()
+
+    @property
+    def log_weights(self) -> np.ndarray:
+        return self._lw.copy()
+
+    @property
+    def weights(self) -> np.ndarray:
+        return np.exp(self._lw)
+
+    @property
+    def output_size(self) -> int:
+        return int(self._c.shape[1])
+
+    @property
+    def state_size(self) -> int:
+        return int(self._c.shape[2])
+
+    @property
+    def n_models(self) -> int:
+        return int(self._c.shape[0])
+
+    @property
+    def n_parameters(self) -> int:
+        """The shared noise, per component a transform and a mean, and the free weights."""
+        d, k, nm = self.output_size, self.state_size, self.n_models
+        return d + nm * (d * k + d) + nm - 1
+
+    def __repr__(self) -> str:
+        return f"FAMix(n_models={self.n_models}, output_size={self.output_size}, state_size={self.state_size}, noise=array({self._noise}))"
+
+    # -- construction -------------------------------------------------------------
+    @staticmethod
+    def init(n_models: int, state_size: int, dataset: Dataset, seed: Optional[int] = None) -> "FAMix":
+        """The components of PPCAMix.init (same seed, same draws), noise = 1, equal weights."""
+        mix = PPCAMix.init(n_models, state_size, dataset, seed=seed)
+        return FAMix(np.ones(mix.output_size), np.stack([m._c for m in mix._models]), np.stack([m._mean for m in mix._models]),
+                     mix._lw)
+
+    @staticmethod
+    def from_ppca_mix(mix: PPCAMix) -> "FAMix":
+        """The FA mixture equal to an isotropic one whose components share their noise level and state size."""
+        if len({m.isotropic_noise for m in mix._models}) != 1 or len(set(mix.state_sizes)) != 1:
+            raise ValueError("the components must share their isotropic noise and state size: the noise of an FAMix is shared")
+        m0 = mix._models[0]
+        return FAMix(np.full(m0.output_size, m0.isotropic_noise), np.stack([m._c for m in mix._models]),
+                     np.stack([m._mean for m in mix._models]), mix._lw)
+
+    @staticmethod
+    def from_fa(models: Sequence[FAModel], log_weights) -> "FAMix":
+        """From FA models that share their noise vector and state size."""
+        models = list(models)
+        if not models:
+            raise ValueError("need at least one model")
+        if any(m._c.shape != models[0]._c.shape or not np.array_equal(m._noise, models[0]._noise) for m in models):
+            raise ValueError("the models must share their noise vector and shape: the noise of an FAMix is shared")
+        return FAMix(models[0]._noise, np.stack([m._c for m in models]), np.stack([m._mean for m in models]), log_weights)
+
+    def whitened(self) -> PPCAMix:
+        """PPCAMix of PPCAModel(1, diag(1 / noise) C_c, mean_c / noise): the mixture of the dataset whose column j is divided by
+        noise[j]."""
+        return PPCAMix([PPCAModel(1.0, c / self._noise[:, None], m / self._noise, ctx=self._ctx) for c, m in zip(self._c, self._mean)],
+                       self._lw)
+
+    def components(self) -> List[FAModel]:
+        return [FAModel(self._noise, c, m, ctx=self._ctx) for c, m in zip(self._c, self._mean)]
+
+    def to_canonical(self) -> "FAMix":
+        """The rotation of PPCAModel.to_canonical on every C_c; noise, means and weights are untouched."""
+        return FAMix(self._noise, np.stack([PPCAModel(1.0, c, m).to_canonical()._c for c, m in zip(self._c, self._mean)]), self._mean,
+                     self._lw)
+
+    def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None) -> Dataset:
+        """The whitened mixture's `sample` with column j multiplied by noise[j]."""
+        return self.whitened().sample(dataset_size, mask_prob, seed)._scale_columns(self._noise)[0]
+
+    # -- passes ---------------------------------------------------------------------
+    def _whiten(self, dataset: Dataset, **kw):
+        if dataset._d != self.output_size:
+            raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {self.output_size}")
+        return dataset._scale_columns(1.0 / self._noise, **kw)
+
+    def llks(self, dataset: Dataset) -> np.ndarray:
+        """Per-sample log-likelihood: the whitened mixture's on the whitened rows minus the sum of ln noise[j] over the row's
+        observed entries."""
+        y, _, jac = self._whiten(dataset, l=np.log(self._noise), row_sums=True)
+        return self.whitened().llks(y) - jac
+
+    def llk(self, dataset: Dataset) -> float:
+        """Weighted log-likelihood."""
+        y, sums, _ = self._whiten(dataset, col_sums=True)
+        return self.whitened().llk(y) - float(np.dot(sums[0], np.log(self._noise)))
+
+    def infer_cluster(self, dataset: Dataset) -> np.ndarray:
+        """Log posteriors over the components (N, n_models): those of the whitened mixture on the whitened rows."""
+        return self.whitened().infer_cluster(self._whiten(dataset)[0])
+
+    def smooth(self, dataset: Dataset) -> Dataset:
+        """Posterior-weighted sum of the components' C_c z + mean_c for every dimension."""
+        sm = self.whitened().smooth(self._whiten(dataset)[0])  # (the whitened copy is released here)
+        return sm._scale_columns(self._noise)[0]
+
+    def extrapolate(self, dataset: Dataset) -> Dataset:
+        """Observed values kept bit for bit, masked ones replaced by the smoothed value."""
+        sm = self.whitened().smooth(self._whiten(dataset)[0])
+        return dataset._fill_masked(sm, self._noise)
+
+    def _iterate(self, dataset: Dataset, min_noise, want_llk: bool):
+        ctx = dataset._ctx
+        if len(dataset) == 0:
+            raise ValueError("dataset is empty")
+        d, k, nm = self.output_size, self.state_size, self.n_models
+        if dataset._d != d:
+            raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {d}")
+        floor = None
+        if min_noise is not None:
+            floor = np.ascontiguousarray(np.broadcast_to(np.asarray(min_noise, dtype=np.float64), (d,)))
+        n_out, c_out, m_out, lw_out = np.empty(d), np.empty((nm, d, k)), np.empty((nm, d)), np.empty(nm)
+        llk = C.c_double(0.0)
+        check(lib().ppca_famix_em_step(ctx.handle, dataset._h, d, k, nm, ptr(self._noise), ptr(self._c), ptr(self._mean), ptr(self._lw),
+                                       ptr(floor), ptr(n_out), ptr(c_out), ptr(m_out), ptr(lw_out), C.byref(llk) if want_llk else None))
+        return FAMix(n_out, c_out, m_out, lw_out, ctx=self._ctx), (llk.value if want_llk else None)
+
+    def iterate(self, dataset: Dataset, min_noise=None) -> "FAMix":
+        """One ECM iteration: responsibilities from this model; per component the transform, then the mean; then the shared noise
+        from all components' residuals pooled; new weights.  The log-likelihood cannot decrease.  min_noise: a floor for the new
+        noise, a number or one per column."""
+        return self._iterate(dataset, min_noise, False)[0]
+
+    def iterate_with_llk(self, dataset: Dataset, min_noise=None):
+        """(next model, llk of THIS model) from the same pass."""
+        return self._iterate(dataset, min_noise, True)
+
+    # -- serialisation (own npz container) ----------------------------------------------
+    def dump(self) -> bytes:
+        buf = io.BytesIO()
+        np.savez(buf, kind="ppca_rs_amd.FAMix", noise=self._noise, transforms=self._c, means=self._mean, log_weights=self._lw)
+        return buf.getvalue()
+
+    @staticmethod
+    def load(data: bytes) -> "FAMix":
+        try:
+            z = np.load(io.BytesIO(data), allow_pickle=False)
+            if str(z["kind"]) != "ppca_rs_amd.FAMix":
+                raise ValueError(f"not an FAMix container: {z['kind']}")
+            return FAMix(z["noise"], z["transforms"], z["means"], z["log_weights"])
+        except Exception as err:
+            raise Exception(str(err))
+
+    def __getstate__(self):
+        return self.dump()
+
+    def __setstate__(self, state):
+        o = FAMix.load(state)
+        self.__dict__.update(o.__dict__)
+
+    def __getnewargs__(self):
+        return (self.noise, self.transforms, self.means, self.log_weights)
+
+
+@dataclass
+class FAMixTrainer:
+    """EM driver of FAMix: the loop and metrics of FATrainer."""
+
+    dataset: Dataset
+
+    def train(self, *, n_models: int, state_size: int, n_iters: int = 10, start: Optional[FAMix] = None,
+              metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False, seed: Optional[int] = None,
+              min_noise_ratio: float = 1e-3) -> FAMix:
+        """min_noise_ratio: FATrainer's floor, ratio x the column's observed standard deviation."""
+        model = start or FAMix.init(n_models, state_size, self.dataset, seed=seed)
+        n = len(self.dataset)
+        floor = min_noise_ratio * np.sqrt(self.dataset.column_stats()[2])
+        for idx in range(n_iters):
+            if not quiet:
+                # the llk of the current model is a by-product of the EM pass: no second sweep
+                new_model, llk = model.iterate_with_llk(self.dataset, floor)
+                metrics = _metrics(llk, model.n_parameters, n)
+                print(f"Masked FA mix iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
+                model = new_model
+            else:
+                model = model.iterate(self.dataset, floor)
         return model.to_canonical()

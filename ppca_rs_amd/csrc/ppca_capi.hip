@@ -1815,6 +1815,40 @@ static int mix_em_step_multi(ppca_ctx *ctx, ppca_comm *comm, ppca_dataset *ds, p
     return PPCA_OK;
 }
 
+// Every device block that the component-by-component form of a mixture step over n = ds->n rows will ask for -- the K llk sweeps
+// (mix_posteriors, mix_tables), the component passes (mix_component_enqueue, em_accumulate_impl) -- at the largest size any of them
+// can request: the ONE list of those internals, taken by ppca_host::mix_em_step and ppca_famix_em_step before their first launch.
+static int mix_step_blocks(ppca_ctx *ctx, const ppca_dataset *ds, ppca_model *const *models, int nm) {
+    const int64_t n = ds->n;
+    if (n <= 0) return PPCA_OK;
+    size_t max_len = 0, gws_bytes = 0;
+    bool any_fused = false;
+    for (int c = 0; c < nm; ++c) {
+        max_len = std::max(max_len, (size_t)StatsLayout(models[c]->d, models[c]->k).len);
+        if (ppca_path_kind(models[c]->d, models[c]->k) == 1) any_fused = true;
+        else gws_bytes = std::max(gws_bytes, generic_workspace_bytes(models[c]->d, models[c]->k, n));
+    }
+    const int grid = fused_grid(n, ctx->n_cu);
+    if (int rc = ensure(ctx->mix[0], ctx->mix_cap[0], sizeof(double) * (size_t)nm * n)) return rc;
+    if (int rc = ensure(ctx->mix[1], ctx->mix_cap[1], sizeof(double) * (size_t)nm * n)) return rc;
+    if (int rc = ensure(ctx->mix[2], ctx->mix_cap[2], sizeof(double) * (size_t)n)) return rc;
+    if (int rc = ensure(ctx->mix[4], ctx->mix_cap[4], sizeof(double) * (size_t)n)) return rc;
+    if (int rc = ensure(ctx->scal, ctx->scal_cap, sizeof(double) * ((size_t)grid * 8 + 16))) return rc;
+    if (any_fused && n < (int64_t)1 << 31) {
+        if (int rc = ensure(ctx->mix[5], ctx->mix_cap[5], sizeof(int) * (size_t)n)) return rc;
+        if (int rc = ensure(ctx->mix[6], ctx->mix_cap[6], sizeof(int) * ((size_t)select_blocks(n) + 1))) return rc;
+        // (what em_accumulate_impl will ask for: the partials of both stages, the bounds + workgroup flags)
+        if (int rc = ensure(ctx->part, ctx->part_cap, sizeof(double) * (size_t)grid * max_len * 2)) return rc;
+        if (int rc = ensure(ctx->qtab, ctx->qtab_cap, fused_qtab_bytes())) return rc;
+        if (int rc = ensure(ctx->errb, ctx->errb_cap, sizeof(double) * ((size_t)grid + 1) * W_GUARD_NCOL + sizeof(int) * 2 * (size_t)grid)) return rc;
+    }
+    if (mix_multi_ok(ds, models, nm))  // (the llk sweeps of all components in one launch: one slice table per component, mix_tables)
+        if (int rc = ensure(ctx->mixq, ctx->mixq_cap, ((fused_qtab_bytes() + 255) & ~(size_t)255) * MIX_MAX)) return rc;
+    if (gws_bytes)
+        if (int rc = ensure(ctx->gws, ctx->gws_cap, gws_bytes)) return rc;
+    return PPCA_OK;
+}
+
 int ppca_host::mix_em_step(ppca_ctx *ctx, ppca_comm *comm, ppca_dataset *ds, ppca_model *const *models_in,
                            const double *log_weights_in, int32_t nm, const ppca_prior *prior, ppca_model *const *models_out,
                            double *log_weights_out, double *llk_in) {
@@ -1844,33 +1878,8 @@ int ppca_host::mix_em_step(ppca_ctx *ctx, ppca_comm *comm, ppca_dataset *ds, ppc
     MixAux ax;
     if (int rc = mix_aux(ctx, nm, ax)) return rc;
     // Every device block the step will ask for is taken HERE, before the first collective: a rank whose allocation fails
-    // returns now, while no peer is inside an all-reduce it would never join (the sizes below are the largest any of the
-    // K llk sweeps and component passes of this call can request).
-    if (n > 0) {
-        size_t max_len = 0, gws_bytes = 0;
-        bool any_fused = false;
-        for (int c = 0; c < nm; ++c) {
-            max_len = std::max(max_len, (size_t)StatsLayout(models_in[c]->d, models_in[c]->k).len);
-            if (ppca_path_kind(models_in[c]->d, models_in[c]->k) == 1) any_fused = true;
-            else gws_bytes = std::max(gws_bytes, generic_workspace_bytes(models_in[c]->d, models_in[c]->k, n));
-        }
-        const int grid = fused_grid(n, ctx->n_cu);
-        if (int rc = ensure(ctx->mix[0], ctx->mix_cap[0], sizeof(double) * (size_t)nm * n)) return rc;
-        if (int rc = ensure(ctx->mix[1], ctx->mix_cap[1], sizeof(double) * (size_t)nm * n)) return rc;
-        if (int rc = ensure(ctx->mix[2], ctx->mix_cap[2], sizeof(double) * (size_t)n)) return rc;
-        if (int rc = ensure(ctx->mix[4], ctx->mix_cap[4], sizeof(double) * (size_t)n)) return rc;
-        if (int rc = ensure(ctx->scal, ctx->scal_cap, sizeof(double) * ((size_t)grid * 8 + 16))) return rc;
-        if (any_fused && n < (int64_t)1 << 31) {
-            if (int rc = ensure(ctx->mix[5], ctx->mix_cap[5], sizeof(int) * (size_t)n)) return rc;
-            if (int rc = ensure(ctx->mix[6], ctx->mix_cap[6], sizeof(int) * ((size_t)select_blocks(n) + 1))) return rc;
-            // (what em_accumulate_impl will ask for: the partials of both stages, the bounds + workgroup flags)
-            if (int rc = ensure(ctx->part, ctx->part_cap, sizeof(double) * (size_t)grid * max_len * 2)) return rc;
-            if (int rc = ensure(ctx->qtab, ctx->qtab_cap, fused_qtab_bytes())) return rc;
-            if (int rc = ensure(ctx->errb, ctx->errb_cap, sizeof(double) * ((size_t)grid + 1) * W_GUARD_NCOL + sizeof(int) * 2 * (size_t)grid)) return rc;
-        }
-        if (gws_bytes)
-            if (int rc = ensure(ctx->gws, ctx->gws_cap, gws_bytes)) return rc;
-    }
+    // returns now, while no peer is inside an all-reduce it would never join.
+    if (int rc = mix_step_blocks(ctx, ds, models_in, nm)) return rc;
     if (int rc = ensure_hstage(ctx, sizeof(double) * ax.P + sizeof(int) * (size_t)nm)) return rc;
     double *pack = static_cast<double *>(ctx->mixpack->p);
     double *aux = ax.shift;  // maxima -> shifts
@@ -2459,6 +2468,228 @@ extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32
         double jac = 0.0;
         for (int j = 0; j < d; ++j) jac += h[L.totals + j] * std::log(noise[j]);
         *llk_in = h[L.scalars + SC_LLK] - jac;
+    }
+    return PPCA_OK;
+}
+
+// ------------------------------------------------------------------ mixture of factor analysers, shared column noise
+extern "C" int ppca_dataset_column_moments_multi(ppca_ctx *ctx, ppca_dataset *ds, const double *e_host, const double *e_dev, int32_t n_comp,
+                                                 const double *a_host, const double *b_host, double *sums_host) {
+    if (!ctx || !ds || !sums_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if ((e_host == nullptr) == (e_dev == nullptr)) return fail(PPCA_ERR_INVALID, "exactly one of e_host and e_dev must be given");
+    if (n_comp < 1 || n_comp > MIX_MAX) return fail(PPCA_ERR_INVALID, "n_comp must lie in [1, %d]", MIX_MAX);
+    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int d = ds->d;
+    const size_t len = (size_t)n_comp * 3 * d;
+    std::fill(sums_host, sums_host + len, 0.0);
+    if (n == 0) return PPCA_OK;
+    // every device block first: [a | b], the weights (when they come from the host), the partials + their sum
+    const int grid = moments_multi_grid(n, n_comp, ctx->n_cu);
+    BufRef ab, ew, part;
+    if (int rc = dev_alloc(sizeof(double) * ((size_t)d + (size_t)n_comp * d), &ab)) return rc;
+    if (e_host)
+        if (int rc = dev_alloc(sizeof(double) * (size_t)n_comp * n, &ew)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * ((size_t)grid + 1) * len, &part)) return rc;
+    std::vector<double> h((size_t)d + (size_t)n_comp * d, 0.0);
+    if (a_host) std::memcpy(h.data(), a_host, sizeof(double) * d);
+    if (b_host) std::memcpy(h.data() + d, b_host, sizeof(double) * (size_t)n_comp * d);
+    double *abp = static_cast<double *>(ab->p);
+    HIP_TRY(hipMemcpyAsync(abp, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (e_host) {
+        HIP_TRY(hipMemcpyAsync(ew->p, e_host, sizeof(double) * (size_t)n_comp * n, hipMemcpyHostToDevice, ctx->stream));
+        e_dev = static_cast<const double *>(ew->p);
+    }
+    double *p = static_cast<double *>(part->p), *red = p + (size_t)grid * len;
+    HIP_TRY(launch_column_moments_multi(ds->X, ds->d, n, d, e_dev, n_comp, a_host ? abp : nullptr, abp + d, p, grid, ctx->stream));
+    HIP_TRY(launch_reduce_partials(p, grid, (int64_t)len, red, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sums_host, red, sizeof(double) * len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (h and e_host are read until here)
+    return PPCA_OK;
+}
+
+extern "C" int ppca_famix_finalize_host(int32_t d, int32_t k, int32_t n_comp, const double *noise, const double *transforms,
+                                        const double *means, const double *stats, const double *sq, const double *scale,
+                                        const double *min_noise, double *noise_out, double *transforms_out, double *means_out) {
+    if (d < 1 || k < 0 || n_comp < 1 || !noise || !means || !stats || !sq || !noise_out || !means_out ||
+        (k > 0 && (!transforms || !transforms_out)))
+        return fail(PPCA_ERR_INVALID, "null argument");
+    if (k == 0) {  // state size 0 = one zero column per component, as ppca_fa_finalize_host
+        std::vector<double> c0((size_t)n_comp * d, 0.0), c1((size_t)n_comp * d, 0.0);
+        return ppca_famix_finalize_host(d, 1, n_comp, noise, c0.data(), means, stats, sq, scale, min_noise, noise_out, c1.data(), means_out);
+    }
+    const StatsLayout L(d, k);
+    for (int c = 0; c < n_comp; ++c)
+        if (scale && !(scale[c] >= 0.0 && std::isfinite(scale[c]))) return fail(PPCA_ERR_INVALID, "scale[%d] is not a finite number >= 0", c);
+    std::vector<double> S((size_t)L.kp), a((size_t)k);
+    for (int j = 0; j < d; ++j) {
+        const double s = noise[j];
+        if (!(s > 0.0) || !std::isfinite(s)) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+        double num = 0.0, den = 0.0;  // the residual sum of squares and the weight of column j, all components pooled
+        for (int c = 0; c < n_comp; ++c) {
+            const double *st = stats + (int64_t)c * L.len, *tr = transforms + ((int64_t)c * d + j) * k;
+            const double *Sj = st + L.S + (int64_t)j * L.kp, *cr = st + L.cross + (int64_t)j * k, *Uj = st + L.U + (int64_t)j * k;
+            const double tot = st[L.totals + j], mean = means[(int64_t)c * d + j];
+            // 1. the whitened row of component c: S_cj a = cross_cj; a pivot <= 0 keeps the old row c_cj / s_j
+            for (int e = 0; e < L.kp; ++e) S[e] = Sj[e];
+            for (int b = 0; b < k; ++b) a[b] = cr[b];
+            const bool solved = chol_packed(S.data(), k);
+            if (solved)
+                chol_solve_packed(S.data(), k, a.data());
+            else
+                for (int b = 0; b < k; ++b) a[b] = tr[b] / s;
+            // 2. its whitened mean moves by delta, with the NEW row
+            double au = 0.0, ac = 0.0, asa = 0.0;
+            for (int b = 0; b < k; ++b) {
+                au += a[b] * Uj[b];
+                ac += a[b] * cr[b];
+                double row = 0.0;
+                for (int e = 0; e < k; ++e) row += Sj[e <= b ? tri(b, e) : tri(e, b)] * a[e];
+                asa += a[b] * row;
+            }
+            const double delta = tot > 0.0 ? (st[L.sumx + j] - au) / tot : 0.0;
+            // 3. its share of the pooled sums, brought to the common scale of the components
+            const double sc = scale ? scale[c] : 1.0;
+            if (tot > 0.0) {
+                num += sc * (sq[(int64_t)c * d + j] - 2.0 * ac + asa - delta * delta * tot);
+                den += sc * tot;
+            }
+            // 4. back to the columns' units (a kept row and an unmoved mean are copied, not rescaled twice)
+            for (int b = 0; b < k; ++b) transforms_out[((int64_t)c * d + j) * k + b] = solved ? s * a[b] : tr[b];
+            means_out[(int64_t)c * d + j] = delta == 0.0 ? mean : s * (mean / s + delta);
+        }
+        const double v = den > 0.0 ? num / den : 0.0;
+        const double pt = (den > 0.0 && std::isfinite(v) && v > 0.0) ? std::sqrt(v) : 1.0;
+        noise_out[j] = std::max(s * pt, min_noise ? min_noise[j] : 0.0);
+    }
+    return PPCA_OK;
+}
+
+// One iteration of the mixture of factor analysers on one GPU, composed from the building blocks of ppca_fa_em_step and of the
+// component-by-component form of ppca_host::mix_em_step (the K component passes each write ONE weight buffer that the next one
+// overwrites, so the multi-component form's K x n selection buffers are of no use to the sweep: the dense weights exp(u_c - shift_c)
+// are written once more, by launch_exp_shift, into a K x n block of their own):
+//   whiten + the weighted column totals (scale_kernel; its entry point synchronises twice: the vectors' upload, the sums)
+//   responsibilities of the K whitened components on Y (one sweep on the fused path), their sum w_i lse_i, the K maxima, the shifts
+//   per component: the gathered weighted EM pass (rows above 2^-200 of the component's largest weight), the dense weights
+//   moments_multi_kernel on Y with a = 1, b_c = mean~_c: sq_cj under the same weights
+//   new log-weights on the device; statistics, sums, shifts and llk to the host in one synchronisation; ppca_famix_finalize_host
+// = three synchronisations per call, two of them inside ppca_dataset_scale_columns.
+extern "C" int ppca_famix_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, int32_t n_comp, const double *noise,
+                                  const double *transforms, const double *means, const double *log_weights, const double *min_noise,
+                                  double *noise_out, double *transforms_out, double *means_out, double *log_weights_out, double *llk_in) {
+    if (!ctx || !ds || !noise || !means || !log_weights || !noise_out || !means_out || !log_weights_out || d < 1 || k < 0 ||
+        (k > 0 && (!transforms || !transforms_out)))
+        return fail(PPCA_ERR_INVALID, "null argument");
+    if (n_comp < 1 || n_comp > MIX_MAX) return fail(PPCA_ERR_INVALID, "n_comp must lie in [1, %d]", MIX_MAX);
+    if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
+    if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
+    if (int rc = check_path(d, k == 0 ? 1 : k)) return rc;
+    for (int j = 0; j < d; ++j)
+        if (!(noise[j] > 0.0) || !std::isfinite(noise[j])) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+    USE_CTX(ctx);
+    const int nm = n_comp;
+    const int64_t n = ds->n;
+    const int ki = k == 0 ? 1 : k;
+    const StatsLayout L(d, ki);
+    const int64_t len = L.len, mlen = model_len(d, ki), sums_at = (int64_t)nm * len, llk_at = sums_at + nm, total = llk_at + 1;
+    const size_t sweep_len = (size_t)nm * 3 * d;
+    // the whitened models PPCAModel(1, A_c, mean~_c) as device buffers, and the whitening vector 1 / s
+    std::vector<double> inv((size_t)d), mw((size_t)nm * d), hm((size_t)nm * mlen, 0.0), tot((size_t)3 * d);
+    for (int j = 0; j < d; ++j) inv[j] = 1.0 / noise[j];
+    for (int c = 0; c < nm; ++c) {
+        double *m = hm.data() + (size_t)c * mlen;
+        m[0] = 1.0;
+        m[1] = 1.0;  // sigma, sigma^2, ln sigma = 0
+        for (int j = 0; j < d; ++j) {
+            for (int b = 0; b < k; ++b) m[MODEL_HDR + (int64_t)j * ki + b] = transforms[((int64_t)c * d + j) * k + b] / noise[j];
+            mw[(size_t)c * d + j] = m[MODEL_HDR + (int64_t)d * ki + j] = means[(int64_t)c * d + j] / noise[j];
+        }
+    }
+    struct Held {  // released on every return path; the whitened copy goes back to the context's block cache
+        ppca_dataset *y = nullptr;
+        std::vector<ppca_model *> m;
+        ~Held() {
+            ppca_dataset_free(y);
+            for (ppca_model *p : m) ppca_model_free(p);
+        }
+    } held;
+    // every device block of the step, before its first launch: the K whitened models, mix_step_blocks' list for the llk sweeps and
+    // component passes (the whitened copy has the shape of ds), then the step's own
+    for (int c = 0; c < nm; ++c) {
+        ppca_model *m = nullptr;
+        if (int rc = ppca_model_alloc(ctx, d, k, &m)) return rc;
+        held.m.push_back(m);
+    }
+    const int sgrid = moments_multi_grid(n, nm, ctx->n_cu);
+    MixAux ax;
+    if (int rc = mix_aux(ctx, nm, ax)) return rc;
+    if (int rc = ensure(ctx->mixpack, ctx->mixpack_cap, sizeof(double) * (size_t)total)) return rc;
+    if (int rc = mix_step_blocks(ctx, ds, held.m.data(), nm)) return rc;
+    BufRef ew, bdev, spart;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)nm * n, &ew)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)nm * d, &bdev)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * ((size_t)sgrid + 1) * sweep_len, &spart)) return rc;
+    // 1. whiten; tot_j = sum_i w_i m_ij for the Jacobian term of the llk
+    if (int rc = ppca_dataset_scale_columns(ctx, ds, inv.data(), nullptr, nullptr, &held.y, tot.data(), nullptr)) return rc;
+    for (int c = 0; c < nm; ++c) {
+        touch(held.m[c]);
+        HIP_TRY(hipMemcpyAsync(held.m[c]->p(), hm.data() + (size_t)c * mlen, sizeof(double) * (size_t)mlen, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(bdev->p, mw.data(), sizeof(double) * mw.size(), hipMemcpyHostToDevice, ctx->stream));
+    // 2. responsibilities u_ic = ln w_i + log r_ic, the mixture llk, 3. the shifts
+    double *pack = static_cast<double *>(ctx->mixpack->p), *aux = ax.shift, *work = static_cast<double *>(ctx->work->p);
+    BufRef llk, u, lse;
+    if (int rc = mix_posteriors(ctx, held.y, held.m.data(), log_weights, nm, llk, u, lse, nullptr)) return rc;
+    HIP_TRY(launch_reduce_sum(static_cast<double *>(lse->p), held.y->w, n, pack + llk_at, work, ctx->stream));
+    const double *ud = static_cast<const double *>(u->p);
+    for (int c = 0; c < nm; ++c) HIP_TRY(launch_reduce_max(ud + (size_t)c * n, n, aux + c, work, ctx->stream));
+    HIP_TRY(launch_mix_shift(aux, nm, ctx->stream));
+    // 4. the component passes and their dense weights
+    ctx->stats_llk_at = -1;
+    double *ewp = static_cast<double *>(ew->p);
+    for (int c = 0; c < nm; ++c) {
+        if (int rc = mix_component_enqueue(ctx, held.y, held.m[c], ud + (size_t)c * n, aux + c, pack + (size_t)c * len, pack + sums_at + c, nullptr))
+            return rc;
+        HIP_TRY(launch_exp_shift(ud + (size_t)c * n, aux + c, n, ewp + (size_t)c * n, ctx->stream));
+    }
+    // 5. sq_cj on Y
+    double *sp = static_cast<double *>(spart->p), *sred = sp + (size_t)sgrid * sweep_len;
+    HIP_TRY(launch_column_moments_multi(held.y->X, held.y->d, n, d, ewp, nm, nullptr, static_cast<const double *>(bdev->p), sp, sgrid, ctx->stream));
+    HIP_TRY(launch_reduce_partials(sp, sgrid, (int64_t)sweep_len, sred, ctx->stream));
+    // 6. new log-weights; everything to the host
+    HIP_TRY(launch_mix_logweights(pack + sums_at, aux, pack + llk_at, nm, ax.out, ctx->stream));
+    std::vector<double> h((size_t)total), hs(sweep_len), hshift((size_t)nm), hlw((size_t)nm + 1);
+    HIP_TRY(hipMemcpyAsync(h.data(), pack, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), sred, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hshift.data(), aux, sizeof(double) * hshift.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hlw.data(), ax.out, sizeof(double) * hlw.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // component c's statistics carry the factor exp(-shift_c): to the common scale exp(-max shift) before pooling
+    std::vector<double> scale((size_t)nm), sq((size_t)nm * d);
+    // (the largest shift of the components that have weight: one with none anywhere, a log-weight of -inf say, has the shift 0 that
+    // launch_mix_shift gives a non-finite maximum, which would push every live scale below the smallest double where row
+    // log-densities lie below -745)
+    double top = 0.0;
+    bool any = false;
+    for (int c = 0; c < nm; ++c)
+        if (h[sums_at + c] > 0.0 && (!any || hshift[c] > top)) {
+            top = hshift[c];
+            any = true;
+        }
+    for (int c = 0; c < nm; ++c) {
+        scale[c] = h[sums_at + c] > 0.0 ? std::exp(hshift[c] - top) : 0.0;
+        std::memcpy(sq.data() + (size_t)c * d, hs.data() + ((size_t)c * 3 + 2) * d, sizeof(double) * d);
+    }
+    if (int rc = ppca_famix_finalize_host(d, k, nm, noise, transforms, means, h.data(), sq.data(), scale.data(), min_noise, noise_out,
+                                          transforms_out, means_out))
+        return rc;
+    for (int c = 0; c < nm; ++c) log_weights_out[c] = hlw[c];
+    if (llk_in) {
+        double jac = 0.0;
+        for (int j = 0; j < d; ++j) jac += tot[j] * std::log(noise[j]);
+        *llk_in = hlw[nm] - jac;
     }
     return PPCA_OK;
 }

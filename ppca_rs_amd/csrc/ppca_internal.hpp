@@ -297,6 +297,12 @@ hipError_t launch_scale_columns(const double *X, int64_t ldx, const double *w, i
                                 double *part, int grid, double *rowsum, hipStream_t s);
 hipError_t launch_fill_masked(const double *X, int64_t ldx, const double *F, int64_t ldf, int64_t n, int d, const double *a_dev,
                               double *out, int n_cu, hipStream_t s);
+// The same three column sums for nc row-weight vectors e_dev[nc][n] (instead of the dataset's weights) and nc offset vectors
+// b_dev[nc][d] in one sweep (a_dev nullable = 1): part[grid][nc][3][d], grid = moments_multi_grid(n, nc, n_cu);
+// reduce with launch_reduce_partials over nc * 3 * d.
+int moments_multi_grid(int64_t n, int nc, int n_cu);
+hipError_t launch_column_moments_multi(const double *X, int64_t ldx, int64_t n, int d, const double *e_dev, int nc, const double *a_dev,
+                                       const double *b_dev, double *part, int grid, hipStream_t s);
 
 // mixture helpers
 // llk: [n_models][n]; logw: [n_models]; w nullable.  Writes u: [n_models][n] =

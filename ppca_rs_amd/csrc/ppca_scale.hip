@@ -9,6 +9,11 @@
 //                  With a = 1 / psi, b = mean / psi it whitens the dataset for the EM pass of PPCAModel(1, A, mean~) and takes the
 //                  one sum of squares the packed statistics lack; with l = ln psi it gives the rows' Jacobian terms of llks.
 //   fill_kernel    out_ij = x_ij (bit-exact) where x is observed, fill_ij a_j elsewhere (FAModel.extrapolate).
+//   moments_multi_kernel   scale_kernel's three column sums for K row-weight vectors e[c][i] (used INSTEAD of the dataset's weights)
+//                  and K offset vectors b_c in ONE sweep (the mixture of factor analysers):
+//                    tot_cj = sum_i e_ci m_ij,  sum_cj = sum_i e_ci m_ij (x_ij a_j - b_cj),  sq_cj = sum_i e_ci m_ij (x_ij a_j - b_cj)^2
+//                  Every element is centred on its OWN component's b_cj before it is squared (no common pivot corrected afterwards:
+//                  with the components' means many standard deviations apart that correction cancels).
 //
 // scale_kernel is bandwidth bound: a thread owns one 16-byte column pair (d even, rows 16-byte aligned; one column otherwise) of
 // SCALE_ROWS rows per step, so that a wave's load is one contiguous 1 KiB segment and SCALE_ROWS of them are requested before the
@@ -18,6 +23,14 @@
 // to part[workgroup][3 d] through a fixed-order sum over the row groups in LDS, and launch_reduce_partials adds the workgroups in
 // its fixed order: no float atomics, bit-reproducible for a given grid.  out and rowsum depend on their row alone (the row sum is
 // a 64-lane butterfly, then the row's waves in index order, then the column blocks in order), hence not on the grid.
+//
+// moments_multi_kernel keeps that layout (column pair per thread, SCALE_ROWS rows in flight, non-temporal loads, persistent grid,
+// column sums in registers for any d, fixed-order partials part[workgroup][K][3][d], no float atomics).  A thread holds the
+// 3 x VEC sums of KB components at once (KB = 1, 2, 4 or 8: the smallest that covers K, MULTI_KB_MAX = 8 beyond); K > 8 takes the
+// components in blocks of 8, each block over the workgroup's run of rows again (at K <= 8 X is read once).  The weights of a
+// row are read once per row and component by every thread of the row: the same address across the row's lanes.
+// The mask enters as a factor 1 / 0 on the weight, not as a select on the term: the offsets b_cj must be finite (a masked entry's
+// term is 0 * (0 - b_cj)), where scale_kernel's select form would ignore a non-finite offset on masked entries.
 #include <algorithm>
 
 #include "ppca_device.hpp"
@@ -201,6 +214,125 @@ __global__ __launch_bounds__(SCALE_THREADS) void fill_kernel(const double *X, in
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- the column sums of K weight vectors in one sweep
+constexpr int MULTI_KB_MAX = 8;  // components whose sums a thread holds at once (3 x VEC x KB doubles)
+
+struct MultiArgs {
+    const double *X;
+    int64_t ldx, n;
+    int d, nc;
+    const double *e;       // [nc][n] row weights, component-major
+    const double *a;       // nullable (= 1), d
+    const double *b;       // [nc][d]
+    double *part;          // [grid][nc][3][d]: tot, sum, sq of every component
+    int tpr_log2;
+    int64_t rows_per_wg;
+};
+
+template <int VEC, int KB>
+__global__ __launch_bounds__(SCALE_THREADS) void moments_multi_kernel(MultiArgs a) {
+    __shared__ double red[SCALE_THREADS];
+    const int t = threadIdx.x, d = a.d;
+    const int tpr = 1 << a.tpr_log2, rps = SCALE_THREADS >> a.tpr_log2;
+    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
+    const int slots = (d + VEC - 1) / VEC;
+    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    double *part = a.part + (int64_t)blockIdx.x * a.nc * 3 * d;
+    const double qnan = __builtin_nan("");
+    for (int c0 = 0; c0 < slots; c0 += tpr) {
+        const int slot = c0 + tc;
+        const bool on = slot < slots;
+        const int j = slot * VEC;
+        double av[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) av[v] = (on && a.a) ? a.a[j + v] : 1.0;
+        for (int k0 = 0; k0 < a.nc; k0 += KB) {  // (one trip when nc <= KB)
+            const int kn = a.nc - k0 < KB ? a.nc - k0 : KB;
+            double bv[KB][VEC], tot[KB][VEC], sum[KB][VEC], sq[KB][VEC];
+#pragma unroll
+            for (int q = 0; q < KB; ++q)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    bv[q][v] = (on && q < kn) ? a.b[(int64_t)(k0 + q) * d + j + v] : 0.0;
+                    tot[q][v] = sum[q][v] = sq[q][v] = 0.0;
+                }
+            for (int64_t rb = r0; rb < r1; rb += (int64_t)rps * SCALE_ROWS) {
+                Vec<VEC> x[SCALE_ROWS];
+#pragma unroll
+                for (int u = 0; u < SCALE_ROWS; ++u) {
+                    const int64_t r = rb + (int64_t)u * rps + tr;
+                    if (on && r < r1) {
+                        x[u] = load_vec<VEC, true>(a.X + r * a.ldx + j);
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) x[u].v[v] = qnan;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < SCALE_ROWS; ++u) {
+                    const int64_t r = rb + (int64_t)u * rps + tr;
+                    const bool live = on && r < r1;
+                    const int64_t rr = r < r1 ? r : r1 - 1;  // (loads without a branch: a dead row or component re-reads a live one's weight)
+                    double wv[KB];
+#pragma unroll
+                    for (int q = 0; q < KB; ++q) {
+                        const double w = a.e[(int64_t)(k0 + (q < kn ? q : kn - 1)) * a.n + rr];
+                        wv[q] = (live && q < kn && __builtin_isfinite(w)) ? w : 0.0;  // a non-finite weight counts as 0
+                    }
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) {
+                        // the mask as a factor 1 / 0 on the (finite) weight, one multiply per component where two 64-bit selects
+                        // would stand: a masked entry's e = -b_cj is finite and meets the weight 0, so it adds exactly nothing
+                        const bool obs = __builtin_isfinite(x[u].v[v]);
+                        const double mk = obs ? 1.0 : 0.0;
+                        const double yv = obs ? __dmul_rn(x[u].v[v], av[v]) : 0.0;
+#pragma unroll
+                        for (int q = 0; q < KB; ++q) {
+                            const double e = __dsub_rn(yv, bv[q][v]);  // centred on the component's own offset
+                            const double wm = __dmul_rn(wv[q], mk);
+                            tot[q][v] += wm;
+                            sum[q][v] = fma(wm, e, sum[q][v]);
+                            sq[q][v] = fma(wm * e, e, sq[q][v]);
+                        }
+                    }
+                }
+            }
+            // column sums of the block: per component and sum, the row groups in index order
+#pragma unroll
+            for (int q = 0; q < KB; ++q) {
+                if (q >= kn) break;  // (uniform over the workgroup)
+#pragma unroll
+                for (int m = 0; m < 3; ++m)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) {
+                        red[t] = m == 0 ? tot[q][v] : (m == 1 ? sum[q][v] : sq[q][v]);
+                        __syncthreads();
+                        if (tr == 0 && on) {
+                            double s = red[tc];
+                            for (int g = 1; g < rps; ++g) s += red[g * tpr + tc];
+                            part[((int64_t)(k0 + q) * 3 + m) * d + j + v] = s;
+                        }
+                        __syncthreads();
+                    }
+            }
+        }
+    }
+}
+
+template <int VEC>
+void launch_multi_vec(int kb, dim3 g, dim3 b, hipStream_t s, const MultiArgs &a) {
+    if (kb == 1)
+        hipLaunchKernelGGL((moments_multi_kernel<VEC, 1>), g, b, 0, s, a);
+    else if (kb == 2)
+        hipLaunchKernelGGL((moments_multi_kernel<VEC, 2>), g, b, 0, s, a);
+    else if (kb == 4)
+        hipLaunchKernelGGL((moments_multi_kernel<VEC, 4>), g, b, 0, s, a);
+    else
+        hipLaunchKernelGGL((moments_multi_kernel<VEC, MULTI_KB_MAX>), g, b, 0, s, a);
+}
+
+int multi_kb(int nc) { return nc <= 1 ? 1 : (nc <= 2 ? 2 : (nc <= 4 ? 4 : MULTI_KB_MAX)); }
+
 }  // namespace
 
 int scale_grid(int64_t n, int d, int n_cu) {
@@ -229,6 +361,32 @@ hipError_t launch_scale_columns(const double *X, int64_t ldx, const double *w, i
         else
             hipLaunchKernelGGL((scale_kernel<1, false>), g, b, 0, s, a);
     }
+    return hipGetLastError();
+}
+
+// Workgroups of the multi-component sweep: what is resident at once at the kernel's register count (KB = 8: 219 VGPRs, two waves
+// per SIMD = two workgroups per CU; KB = 4: 156, three; KB <= 2: at most 113, four) -- one wave of workgroups, each with one equal
+// run of rows -- which also keeps the partials, grid x K x 3 d doubles, small.
+int moments_multi_grid(int64_t n, int nc, int n_cu) {
+    if (n <= 0) return 0;
+    const int kb = multi_kb(nc);
+    const int per_cu = kb <= 2 ? 4 : (kb == 4 ? 3 : 2);
+    return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(n_cu, 1) * per_cu, (n + 7) / 8));
+}
+
+hipError_t launch_column_moments_multi(const double *X, int64_t ldx, int64_t n, int d, const double *e_dev, int nc, const double *a_dev,
+                                       const double *b_dev, double *part, int grid, hipStream_t s) {
+    if (n <= 0 || grid <= 0 || nc <= 0) return hipSuccess;
+    const bool vec = d % 2 == 0 && ldx % 2 == 0 && aligned16(X);
+    const int slots = vec ? d / 2 : d;
+    int lg = 0;
+    while ((1 << lg) < slots && lg < 8) ++lg;
+    MultiArgs a{X, ldx, n, d, nc, e_dev, a_dev, b_dev, part, lg, (n + grid - 1) / grid};
+    const dim3 g((unsigned)grid), b(SCALE_THREADS);
+    if (vec)
+        launch_multi_vec<2>(multi_kb(nc), g, b, s, a);
+    else
+        launch_multi_vec<1>(multi_kb(nc), g, b, s, a);
     return hipGetLastError();
 }
 

@@ -3,7 +3,10 @@ extrapolate, covariance diagonal, posterior sample / impute, leave-one-out predi
 then the host posterior sampler (infer + numpy) on a slice of at most 1 M rows.  `--mix NM` adds the mixture's leave-one-out
 predictive over NM components next to its extrapolated covariance diagonal.  `--fa` runs ONLY the legs of the factor-analysis
 pass: the column-scale pass with and without output against a device-to-device hipMemcpy of the same N x d array
-in the same process, and one FA iteration against one PPCA iteration; every repetition timed on its own (median, min, max)."""
+in the same process, and one FA iteration against one PPCA iteration; every repetition timed on its own (median, min, max).
+`--famix NM` runs ONLY the legs of the FA mixture, in one process: the sums-only scale pass, the multi-component
+column sweep at NM components (device-resident weights), ppca_mix_em_step and ppca_famix_em_step at NM components, and the parts the
+difference of the two goes to (the whitening pass, the sweep, the host finalisation)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -88,6 +91,92 @@ def fa_legs(reps=12):
 
 if "--fa" in sys.argv:
     fa_legs()
+    sys.exit(0)
+
+def famix_legs(nm, reps=12):
+    def series(fn):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts, nbytes=None):
+        med = float(np.median(ts))
+        rate = f"{nbytes/med/1e6:8.1f} GB/s" if nbytes else " " * 13
+        print(f"{name:52s} median {med:8.3f} ms  min {ts.min():8.3f}  max {ts.max():8.3f}  {rate}  ({reps} repetitions)", flush=True)
+        return med
+
+    rng = np.random.default_rng(5)
+    a, b = rng.uniform(0.5, 2.0, d), rng.standard_normal(d)
+    sums = np.empty((3, d))
+    def scale(with_out):
+        o = C.c_void_p()
+        _lib.check(L.ppca_dataset_scale_columns(ctx.handle, ds._h, _lib.ptr(a), _lib.ptr(b), None, C.byref(o) if with_out else None,
+                                                _lib.ptr(sums), None))
+        if with_out:
+            L.ppca_dataset_free(o)
+    # K x n weights on the device: in [0, 1], most of a row's weight in few components, as exp-shifted responsibilities are
+    e = rng.uniform(0.0, 1.0, (nm * n, 1)) ** 4
+    E = P.Dataset(e)
+    del e
+    e_dev = L.ppca_dataset_device_x(E._h)
+    bm = np.ascontiguousarray(rng.standard_normal((nm, d)))
+    msums = np.empty((nm, 3, d))
+    def sweep():
+        _lib.check(L.ppca_dataset_column_moments_multi(ctx.handle, ds._h, None, C.c_void_p(e_dev), nm, _lib.ptr(a), _lib.ptr(bm), _lib.ptr(msums)))
+    t_a, t_b = [], []
+    for _ in range(2):  # the two sweeps alternate, so that both see the same machine
+        t_a.append(series(lambda: scale(False))); t_b.append(series(sweep))
+    t_a, t_b = np.concatenate(t_a), np.concatenate(t_b)
+    reps *= 2
+    ta = report("(a) scale pass, sums only", t_a, 8.0 * n * d)
+    tb = report(f"(b) multi-component sweep, K = {nm}", t_b, n * (8.0 * d + 8.0 * nm))
+    print(f"  (b) / (a) = {tb / ta:.3f}   (the {nm} separate sweeps it replaces: {nm} x (a) = {nm * ta:.3f} ms, {nm * ta / tb:.2f} x (b))")
+    reps //= 2
+    tw = report("whitening: scale pass with output (+ sums)", series(lambda: scale(True)), 16.0 * n * d)
+    del E
+    # the two mixture iterations from the same components: perturbed copies of m, as the --mix leg
+    comps = [P.PPCAModel(1.0, m.transform + 0.1 * rng.standard_normal((d, k)), m.mean) for _ in range(nm)]
+    mix = P.PPCAMix(comps, np.full(nm, -np.log(nm)))
+    devs, arr = mix._handles(ctx)
+    outs = []
+    for _ in range(nm):
+        hh = C.c_void_p()
+        _lib.check(L.ppca_model_alloc(ctx.handle, d, k, C.byref(hh)))
+        outs.append(hh)
+    oarr = (C.c_void_p * nm)(*outs)
+    lw_out, llk = np.empty(nm), C.c_double()
+    t_c = series(lambda: _lib.check(L.ppca_mix_em_step(ctx.handle, ds._h, arr, _lib.ptr(mix._lw), nm, None, oarr, _lib.ptr(lw_out), C.byref(llk))))
+    for hh in outs:
+        L.ppca_model_free(hh)
+    fm = P.FAMix.from_ppca_mix(mix)
+    no, co, mo = np.empty(d), np.empty((nm, d, k)), np.empty((nm, d))
+    t_d = series(lambda: _lib.check(L.ppca_famix_em_step(ctx.handle, ds._h, d, k, nm, _lib.ptr(fm._noise), _lib.ptr(fm._c), _lib.ptr(fm._mean),
+                                                         _lib.ptr(fm._lw), None, _lib.ptr(no), _lib.ptr(co), _lib.ptr(mo), _lib.ptr(lw_out), C.byref(llk))))
+    tc = report(f"(c) PPCA mixture iteration (ppca_mix_em_step, K = {nm})", t_c)
+    td = report(f"(d) FA mixture iteration (ppca_famix_em_step, K = {nm})", t_d)
+    # the host finalisation alone, on statistics of the right shape (S_cj = I, so that every row solve runs)
+    slen = int(L.ppca_stats_len(d, k))
+    kp = k * (k + 1) // 2
+    st = rng.standard_normal((nm, slen))
+    eye = np.array([1.0 if p_ == q_ else 0.0 for p_ in range(k) for q_ in range(p_ + 1)])
+    st[:, d * k:d * k + d * kp] = np.tile(eye, d)
+    st[:, 2 * d * k + d * kp + d:2 * d * k + d * kp + 2 * d] = 1.0  # totals
+    sq = np.full((nm, d), 100.0)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        _lib.check(L.ppca_famix_finalize_host(d, k, nm, _lib.ptr(fm._noise), _lib.ptr(fm._c), _lib.ptr(fm._mean), _lib.ptr(st), _lib.ptr(sq), None,
+                                              None, _lib.ptr(no), _lib.ptr(co), _lib.ptr(mo)))
+    tf = (time.perf_counter() - t0) * 1e3 / reps
+    print(f"  (d) / (c) = {td / tc:.3f}   (d) - (c) = {td - tc:.3f} ms; the whitening {tw:.3f} ms, the sweep {tb:.3f} ms, "
+          f"the host finalisation {tf:.3f} ms, the rest {td - tc - tw - tb - tf:.3f} ms")
+
+if "--famix" in sys.argv:
+    famix_legs(int(sys.argv[sys.argv.index("--famix") + 1]))
     sys.exit(0)
 
 def timed(name, fn, bytes_per_sample, reps=5):
