@@ -245,6 +245,21 @@ int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model
  * and row_sums do not depend on the grid at all.  At least one output is given.  Synchronises. */
 int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const double *a_host, const double *b_host, const double *l_host,
                                ppca_dataset **out, double *col_sums_host, double *row_sums);
+/* ppca_dataset_pairwise_moments: the second moments between every two columns over the entries that are there.  With
+ * center_host (d, nullable = 0; every entry finite) and x~_ij = x_ij - center_j on observed entries, 0 on masked ones, three d x d
+ * row-major host matrices:
+ *   sums_host[j][l]   = sum_i w_i x~_ij x~_il   (only rows with both observed contribute)            symmetric
+ *   counts_host[j][l] = sum_i w_i m_ij m_il                                                        symmetric
+ *   cross_host[j][l]  = sum_i w_i x~_ij m_il    (centred column j over the rows where l is observed)   nullable, not symmetric
+ * The centring happens before the product (a column with mean 1e6 and unit spread does not cancel) and the weights enter as in the
+ * column sums of ppca_dataset_scale_columns: diag(counts) is that pass's tot and diag(sums) its sq for b = center.  sums / counts is the
+ * covariance around a common centre; (sums - cross o cross^T / counts) / (counts - 1) is the pairwise-complete covariance.  Dense fp64
+ * MFMA contractions over 64-column tile pairs I <= J x runs of rows, per-job partials added in a fixed order (no float atomics:
+ * bit-reproducible for a given grid) and the upper triangle mirrored, so that sums and counts are symmetric bit for bit.  cross costs as
+ * much as the other two together and is computed only when asked for.  An empty dataset gives zeros.  Scratch comes from the context's
+ * block cache and does not grow with N.  Synchronises. */
+int ppca_dataset_pairwise_moments(ppca_ctx *ctx, ppca_dataset *ds, const double *center_host, double *sums_host, double *counts_host,
+                                  double *cross_host);
 /* out_ij = x_ij, bit-exact, where ds is observed; fill_ij a_j elsewhere (fill: a dataset of the same shape; a_host: d).  A new
  * dataset carrying the weights of ds: the last step of the FA model's extrapolate.  Synchronises. */
 int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *fill, const double *a_host, ppca_dataset **out);

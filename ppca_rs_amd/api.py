@@ -164,6 +164,40 @@ class Dataset:
         var = np.where(tot > 0.0, s2[2] / safe - (s2[1] / safe) ** 2, 0.0)
         return tot, mean, np.maximum(var, 0.0)
 
+    def pairwise_moments(self, center="mean", cross: bool = False) -> "PairwiseMoments":
+        """The second moments between every two columns over the entries that are there, as one dense fp64 MFMA pass on the GPU
+        (ppca_dataset_pairwise_moments): with x~ = x - center on observed entries, sums = sum_i w_i x~_ij x~_il over the rows where
+        both are observed, counts = sum_i w_i m_ij m_il and, with cross=True (twice the work), cross = sum_i w_i x~_ij m_il.
+
+        center="mean": the weighted column means over observed entries (0 for an empty column; one sums sweep); None: zeros; or an
+        array of length d.  Nothing of the dataset comes to the host but the d x d results."""
+        d = self._d
+        if center is None:
+            c = np.zeros(d)
+        elif isinstance(center, str):
+            if center != "mean":
+                raise ValueError(f"center must be 'mean', None or an array of length {d}")
+            _, s1, _ = self._scale_columns(np.ones(d), out=False, col_sums=True)
+            c = np.where(s1[0] > 0.0, s1[1] / np.where(s1[0] > 0.0, s1[0], 1.0), 0.0)
+        else:
+            c = f64(center).reshape(-1)
+            if c.shape[0] != d:
+                raise ValueError(f"center must have length {d}")
+        if not np.all(np.isfinite(c)):
+            raise ValueError("every entry of center must be finite")
+        sums, counts = np.empty((d, d)), np.empty((d, d))
+        cr = np.empty((d, d)) if cross else None
+        check(lib().ppca_dataset_pairwise_moments(self._ctx.handle, self._h, ptr(c), ptr(sums), ptr(counts), ptr(cr)))
+        return PairwiseMoments(c, sums, counts, cr)
+
+    def covariance(self, mode: str = "global", ddof: float = 0.0, center="mean") -> np.ndarray:
+        """`pairwise_moments(center, cross=(mode == "pairwise")).covariance(mode, ddof)`."""
+        return self.pairwise_moments(center, cross=(mode == "pairwise")).covariance(mode, ddof)
+
+    def correlation(self, mode: str = "global", center="mean") -> np.ndarray:
+        """`pairwise_moments(center, cross=(mode == "pairwise")).correlation(mode)`."""
+        return self.pairwise_moments(center, cross=(mode == "pairwise")).correlation(mode)
+
     def chunks(self, chunks: int) -> "DatasetChunks":
         """Iterator over ceil(N / chunks)-row slices (src/python_bindings.rs:110-118)."""
         return DatasetChunks(self, chunks)
@@ -241,6 +275,96 @@ class DatasetChunks:
             self.position += self.stride
             return out
         raise StopIteration
+
+
+# --------------------------------------------------------------------------- pairwise second moments
+class PairwiseMoments:
+    """What `Dataset.pairwise_moments` returns, host arrays: `center` (d) and the d x d matrices `sums`, `counts` and (optional)
+    `cross` of include/ppca_hip.h, ppca_dataset_pairwise_moments.  Constructible from host arrays; the sums are additive over row
+    blocks (`a + b` for two results with the same centre: chunks, shards)."""
+
+    def __init__(self, center, sums, counts, cross=None):
+        c = np.array(center, dtype=np.float64).reshape(-1)
+        d = c.shape[0]
+        self._center = c
+        self._sums = np.array(sums, dtype=np.float64).reshape(d, d)
+        self._counts = np.array(counts, dtype=np.float64).reshape(d, d)
+        self._cross = np.array(cross, dtype=np.float64).reshape(d, d) if cross is not None else None
+        for a in (self._center, self._sums, self._counts, self._cross):
+            if a is not None:
+                a.setflags(write=False)
+
+    @property
+    def center(self) -> np.ndarray:
+        return self._center.copy()
+
+    @property
+    def sums(self) -> np.ndarray:
+        return self._sums.copy()
+
+    @property
+    def counts(self) -> np.ndarray:
+        return self._counts.copy()
+
+    @property
+    def cross(self) -> Optional[np.ndarray]:
+        return self._cross.copy() if self._cross is not None else None
+
+    def __add__(self, other: "PairwiseMoments") -> "PairwiseMoments":
+        if not isinstance(other, PairwiseMoments):
+            return NotImplemented
+        if self._center.shape != other._center.shape or not np.array_equal(self._center, other._center):
+            raise ValueError("the two results are centred differently: their sums do not add")
+        both = self._cross is not None and other._cross is not None
+        return PairwiseMoments(self._center, self._sums + other._sums, self._counts + other._counts,
+                               self._cross + other._cross if both else None)
+
+    def covariance(self, mode: str = "global", ddof: float = 0.0) -> np.ndarray:
+        """"global": sums / (counts - ddof), the second moment around the common centre over the rows where both columns are
+        observed.  "pairwise" (needs `cross`): (sums - cross o cross^T / counts) / (counts - ddof), each pair centred on its own
+        means over the co-observed rows -- with unit weights and ddof=1 what pandas.DataFrame.cov() computes.  NaN where
+        counts <= ddof."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if mode == "global":
+                num = self._sums
+            elif mode == "pairwise":
+                if self._cross is None:
+                    raise ValueError("mode='pairwise' needs cross: pairwise_moments(cross=True)")
+                num = self._sums - self._cross * self._cross.T / self._counts
+            else:
+                raise ValueError("mode must be 'global' or 'pairwise'")
+            return np.where(self._counts > ddof, num / (self._counts - ddof), np.nan)
+
+    def correlation(self, mode: str = "global") -> np.ndarray:
+        """cov_jl / sqrt(cov_jj cov_ll) of `covariance(mode)`.  NOT pandas' pairwise `corr`, which rescales each pair by the
+        variances over the pair's co-observed rows only (a fourth matrix); here every pair is rescaled by the two columns' own
+        variances over all their observed rows."""
+        cov = self.covariance(mode)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sd = np.sqrt(np.diag(cov))
+            return cov / np.outer(sd, sd)
+
+
+def _spectral_start(sigma_mat: np.ndarray, live: np.ndarray, k: int):
+    """The closed-form maximum-likelihood PPCA model of a covariance matrix (Tipping and Bishop 1999) on its live columns:
+    (sigma, C) with C (d x k), zero rows on the other columns and zero columns beyond the live ones."""
+    d = sigma_mat.shape[0]
+    c = np.zeros((d, k))
+    idx = np.flatnonzero(live)
+    dl = idx.shape[0]
+    if dl == 0:
+        return 1.0, c
+    sub = np.nan_to_num(sigma_mat[np.ix_(idx, idx)], nan=0.0, posinf=0.0, neginf=0.0)
+    trace = float(np.trace(sub))
+    if not trace > 0.0:
+        return 1.0, c
+    lam, u = np.linalg.eigh(0.5 * (sub + sub.T))
+    lam, u = lam[::-1], u[:, ::-1]
+    floor = 1e-8 * trace / dl
+    s2 = max(float(np.mean(lam[k:])), floor) if k < dl else floor
+    kk = min(k, dl)
+    c[idx, :kk] = u[:, :kk] * np.sqrt(np.maximum(lam[:kk] - s2, 0.0))
+    return math.sqrt(s2), c
 
 
 # --------------------------------------------------------------------------- Prior
@@ -402,10 +526,11 @@ class PPCAModel:
 
     # -- construction ---------------------------------------------------------
     @staticmethod
-    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None) -> "PPCAModel":
+    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "PPCAModel":
         """Random untrained model (ppca_model.rs:51-70): C ~ N(0,1) with the rows of
         all-masked dimensions zeroed, sigma = 1, mean = 0.  `seed` is an extension
-        (the reference's RNG cannot be seeded).
+        (the reference's RNG cannot be seeded).  method="pca" (an extension): the spectral start
+        `from_moments(state_size, dataset.pairwise_moments())` instead; `seed` is not used.
 
         LIMIT: state_size <= 64.  The reference takes any state size; here the per-sample k x k inversion is one
         wave's job (a 64 x 64 matrix in 33 KB of LDS, ppca_generic.hip::solve_mfma_kernel) and the M-step row solves
@@ -419,6 +544,10 @@ class PPCAModel:
         # state_size = 0 (an isotropic Gaussian around the mean, ppca_model.rs:51-70 with an empty transform; to_canonical
         # :399-402) is accepted as the reference accepts it: the library carries it as ONE zero transform column, with
         # which every pass reproduces the k = 0 model exactly (include/ppca_hip.h, ppca_model_create)
+        if method == "pca":
+            return PPCAModel.from_moments(state_size, dataset.pairwise_moments())
+        if method != "random":
+            raise ValueError("method must be 'random' or 'pca'")
         d = dataset.output_size()
         rng = np.random.default_rng(seed)
         # DMatrix::from_vec is column-major (utils.rs:16-25)
@@ -426,6 +555,28 @@ class PPCAModel:
         for j in dataset.empty_dimensions():
             c[j, :] = 0.0
         return PPCAModel(1.0, c, np.zeros(d))
+
+    @staticmethod
+    def from_moments(state_size: int, moments: "PairwiseMoments") -> "PPCAModel":
+        """The spectral start: the closed-form maximum-likelihood PPCA model (Tipping and Bishop 1999) of the covariance
+        sums / counts of `moments` (NaN -> 0) on the columns with an observed entry -- the top state_size eigenpairs (U, lambda),
+        sigma^2 = the mean of the other eigenvalues (at least 1e-8 of the mean variance), C = U sqrt(max(lambda - sigma^2, 0)), zero
+        rows on empty columns, mean = the centre; canonical, so the signs are determined.  With complete data it is a fixed point of
+        EM; with masked data it is the standard start.  sigma = 1, C = 0 when the data has no variance.  Host-side numpy."""
+        k = int(state_size)
+        if k < 0:
+            raise ValueError("state_size must be >= 0")
+        counts = moments._counts
+        sigma, c = _spectral_start(moments.covariance("global", 0.0), np.diag(counts) > 0.0, k)
+        return PPCAModel(sigma, PPCAModel._canonical_transform(c), moments._center)
+
+    @staticmethod
+    def _canonical_transform(c: np.ndarray) -> np.ndarray:
+        """The transform of to_canonical at the same state size: the SVD of a d x k matrix with k > d has d columns, the rest are 0."""
+        out = np.zeros_like(c)
+        t = PPCAModel(1.0, c, np.zeros(c.shape[0])).to_canonical()._c
+        out[:, :t.shape[1]] = t
+        return out
 
     def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None, *, ctx=None) -> Dataset:
         """ppca_model.rs:186-191, generated on the GPU with a counter-based RNG."""
@@ -724,8 +875,9 @@ class PPCATrainer:
 
     def train(self, *, start: Optional[PPCAModel] = None, prior: Optional[Prior] = None, state_size: int,
               n_iters: int = 10, metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False,
-              seed: Optional[int] = None) -> PPCAModel:
-        model = start or PPCAModel.init(state_size, self.dataset, seed=seed)
+              seed: Optional[int] = None, init: str = "random") -> PPCAModel:
+        """init: the method of PPCAModel.init ("random" or "pca"), used only when `start` is None."""
+        model = start or PPCAModel.init(state_size, self.dataset, seed=seed, method=init)
         n = len(self.dataset)
         for idx in range(n_iters):
             if not quiet:
@@ -803,10 +955,32 @@ class FAModel:
 
     # -- construction -------------------------------------------------------------
     @staticmethod
-    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None) -> "FAModel":
-        """The transform of PPCAModel.init (same seed, same draw), noise = 1, mean = 0."""
-        m = PPCAModel.init(state_size, dataset, seed=seed)
+    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "FAModel":
+        """The transform of PPCAModel.init (same seed, same draw), noise = 1, mean = 0.  method="pca": the spectral start
+        `from_moments(state_size, dataset.pairwise_moments())` instead."""
+        if method not in ("random", "pca"):
+            raise ValueError("method must be 'random' or 'pca'")
+        m = PPCAModel.init(state_size, dataset, seed=seed)  # (the checks of state_size and of an empty dataset, for both methods)
+        if method == "pca":
+            return FAModel.from_moments(state_size, dataset.pairwise_moments())
         return FAModel(np.ones(m.output_size), m._c, m._mean)
+
+    @staticmethod
+    def from_moments(state_size: int, moments: "PairwiseMoments") -> "FAModel":
+        """The spectral start of factor analysis: the closed form of PPCAModel.from_moments on the CORRELATION matrix (C_r, with
+        sd_j = sqrt(cov_jj), 1 where that is not positive), then C = diag(sd) C_r, noise_j = sd_j sqrt(max(1 - |C_r,j|^2, 1e-4))
+        (1 for an empty column) and mean = the centre.  Rescaling a column rescales its row of C, its noise and its mean with it."""
+        k = int(state_size)
+        if k < 0:
+            raise ValueError("state_size must be >= 0")
+        cov = np.nan_to_num(moments.covariance("global", 0.0), nan=0.0, posinf=0.0, neginf=0.0)
+        live = np.diag(moments._counts) > 0.0
+        var = np.diag(cov)
+        sd = np.where(var > 0.0, np.sqrt(np.where(var > 0.0, var, 1.0)), 1.0)
+        _, c_r = _spectral_start(cov / np.outer(sd, sd), live, k)
+        c_r = PPCAModel._canonical_transform(c_r)  # (signs and order fixed BEFORE the columns get their scale back)
+        noise = np.where(live, sd * np.sqrt(np.maximum(1.0 - np.sum(c_r * c_r, axis=1), 1e-4)), 1.0)
+        return FAModel(noise, sd[:, None] * c_r, moments._center)
 
     @staticmethod
     def from_ppca(model: PPCAModel) -> "FAModel":
@@ -918,11 +1092,12 @@ class FATrainer:
 
     def train(self, *, state_size: int, n_iters: int = 10, start: Optional[FAModel] = None,
               metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False, seed: Optional[int] = None,
-              min_noise_ratio: float = 1e-3) -> FAModel:
-        """min_noise_ratio: the new noise of column j is kept at or above ratio x the column's observed standard deviation -- a guard
+              min_noise_ratio: float = 1e-3, init: str = "random") -> FAModel:
+        """init: the method of FAModel.init ("random" or "pca"), used only when `start` is None.
+        min_noise_ratio: the new noise of column j is kept at or above ratio x the column's observed standard deviation -- a guard
         against a noise level collapsing to 0 (a Heywood case), not a tuned number: at 1e-3 it bounds the share of a column's
         variance the latent state may explain at 1 - 1e-6."""
-        model = start or FAModel.init(state_size, self.dataset, seed=seed)
+        model = start or FAModel.init(state_size, self.dataset, seed=seed, method=init)
         n = len(self.dataset)
         floor = min_noise_ratio * np.sqrt(self.dataset.column_stats()[2])
         for idx in range(n_iters):

@@ -2352,6 +2352,46 @@ extern "C" int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const
     return PPCA_OK;
 }
 
+// ------------------------------------------------------------------ pairwise second moments
+extern "C" int ppca_dataset_pairwise_moments(ppca_ctx *ctx, ppca_dataset *ds, const double *center_host, double *sums_host,
+                                             double *counts_host, double *cross_host) {
+    if (!ctx || !ds || !sums_host || !counts_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    const int64_t n = ds->n;
+    const int d = ds->d;
+    if (center_host)
+        for (int j = 0; j < d; ++j)
+            if (!std::isfinite(center_host[j])) return fail(PPCA_ERR_INVALID, "center[%d] is not a finite number", j);
+    USE_CTX(ctx);
+    const size_t dd = (size_t)d * d;
+    if (n <= 0) {  // an empty dataset: zeros
+        std::fill(sums_host, sums_host + dd, 0.0);
+        std::fill(counts_host, counts_host + dd, 0.0);
+        if (cross_host) std::fill(cross_host, cross_host + dd, 0.0);
+        return PPCA_OK;
+    }
+    const MomentsPlan plan = moments_plan(n, d, ctx->n_cu, cross_host != nullptr);
+    const int nout = cross_host ? 3 : 2;
+    BufRef cen, part, res;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)d, &cen)) return rc;
+    if (int rc = dev_alloc(plan.scratch_bytes, &part)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * dd * nout, &res)) return rc;
+    std::vector<double> c0;
+    if (!center_host) {
+        c0.assign((size_t)d, 0.0);
+        center_host = c0.data();
+    }
+    HIP_TRY(hipMemcpyAsync(cen->p, center_host, sizeof(double) * (size_t)d, hipMemcpyHostToDevice, ctx->stream));
+    double *r = static_cast<double *>(res->p);
+    HIP_TRY(launch_pairwise_moments(ds->X, ds->d, ds->w, n, d, static_cast<const double *>(cen->p), plan, static_cast<double *>(part->p), r,
+                                    r + dd, cross_host ? r + 2 * dd : nullptr, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sums_host, r, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counts_host, r + dd, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
+    if (cross_host) HIP_TRY(hipMemcpyAsync(cross_host, r + 2 * dd, sizeof(double) * dd, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (c0 and the buffers leave scope)
+    return PPCA_OK;
+}
+
 extern "C" int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *fill, const double *a_host, ppca_dataset **out) {
     if (!ctx || !ds || !fill || !a_host || !out) return fail(PPCA_ERR_INVALID, "null argument");
     if (ds->n != fill->n || ds->d != fill->d) return fail(PPCA_ERR_INVALID, "the two datasets differ in shape");

@@ -304,6 +304,19 @@ int moments_multi_grid(int64_t n, int nc, int n_cu);
 hipError_t launch_column_moments_multi(const double *X, int64_t ldx, int64_t n, int d, const double *e_dev, int nc, const double *a_dev,
                                        const double *b_dev, double *part, int grid, hipStream_t s);
 
+// pairwise second moments (ppca_moments.hip): sums = X~^T diag(w) X~, counts = M^T diag(w) M and (cross
+// nullable) cross = X~^T diag(w) M, d x d row-major each, x~ = x - center on observed entries.  A job = (pair of 64-column tiles,
+// I <= J) x (run of rows); its partials go to part (p.scratch_bytes) and a second kernel adds the runs in order and mirrors the
+// upper triangle of sums / counts.  moments_plan takes the number of runs from n_cu; n = 0 launches nothing (nsplit = 0).
+struct MomentsPlan {
+    int tiles, npairs, nsplit, nq;
+    int64_t rows_per;
+    size_t scratch_bytes;
+};
+MomentsPlan moments_plan(int64_t n, int d, int n_cu, bool cross);
+hipError_t launch_pairwise_moments(const double *X, int64_t ldx, const double *w, int64_t n, int d, const double *center_dev,
+                                   const MomentsPlan &p, double *part, double *sums, double *counts, double *cross, hipStream_t s);
+
 // mixture helpers
 // llk: [n_models][n]; logw: [n_models]; w nullable.  Writes u: [n_models][n] =
 // ln w_i + log posterior_ic (-inf when w_i <= 0) and lse[n] (mixture llk per sample).

@@ -6,7 +6,10 @@ pass: the column-scale pass with and without output against a d
 in the same process, and one FA iteration against one PPCA iteration; every repetition timed on its own (median, min, max).
 `--famix NM` runs ONLY the legs of the FA mixture, in one process: the sums-only scale pass, the multi-component
 column sweep at NM components (device-resident weights), ppca_mix_em_step and ppca_famix_em_step at NM components, and the parts the
-difference of the two goes to (the whitening pass, the sweep, the host finalisation)."""
+difference of the two goes to (the whitening pass, the sweep, the host finalisation).  `--moments` runs ONLY the legs of the
+pairwise second moments, in one process: the pass without and with `cross`, one PPCA iteration (ppca_em_step at
+state size k) and the device-to-device copy of X; per pass the multiple of one EM iteration and the fraction of the measured fp64
+MFMA rate (profiles/r04/mfma_peak.txt), counting n d (d + 1) flop per symmetric matrix."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -177,6 +180,60 @@ def famix_legs(nm, reps=12):
 
 if "--famix" in sys.argv:
     famix_legs(int(sys.argv[sys.argv.index("--famix") + 1]))
+    sys.exit(0)
+
+def moments_legs(reps=12):
+    MFMA_TFLOPS = 47.9  # v_mfma_f64_16x16x4_f64 at two waves per SIMD, profiles/r04/mfma_peak.txt
+    hip = C.CDLL(_lib.LIB_PATH)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipDeviceSynchronize.argtypes = []
+
+    def series(fn):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:44s} median {med:8.3f} ms  min {ts.min():8.3f}  max {ts.max():8.3f}  max/median {ts.max()/med:5.3f}  "
+              f"({reps} repetitions)", flush=True)
+        return med
+
+    center = ds.column_stats()[1]
+    sums, counts, cross = np.empty((d, d)), np.empty((d, d)), np.empty((d, d))
+    def moments(with_cross):
+        _lib.check(L.ppca_dataset_pairwise_moments(ctx.handle, ds._h, _lib.ptr(center), _lib.ptr(sums), _lib.ptr(counts),
+                                                   _lib.ptr(cross) if with_cross else None))
+    out = C.c_void_p()
+    _lib.check(L.ppca_model_alloc(ctx.handle, d, k, C.byref(out)))
+    llk = C.c_double()
+    def em():
+        _lib.check(L.ppca_em_step(ctx.handle, ds._h, md.h, None, out, C.byref(llk)))
+    dst = C.c_void_p()
+    _lib.check(L.ppca_dataset_scale_columns(ctx.handle, ds._h, _lib.ptr(np.ones(d)), None, None, C.byref(dst), None, None))
+    src_p, dst_p = L.ppca_dataset_device_x(ds._h), L.ppca_dataset_device_x(dst)
+    def copy():
+        assert hip.hipMemcpy(dst_p, src_p, C.c_size_t(8 * n * d), 3) == 0  # hipMemcpyDeviceToDevice
+        assert hip.hipDeviceSynchronize() == 0
+    t_em = report(f"PPCA iteration (ppca_em_step, k = {k})", series(em))
+    t_cp = report("hipMemcpy device to device (N x d)", series(copy))
+    t_s = report("pairwise moments: sums, counts", series(lambda: moments(False)))
+    t_x = report("pairwise moments: sums, counts, cross", series(lambda: moments(True)))
+    L.ppca_dataset_free(dst)
+    L.ppca_model_free(out)
+    sym = float(n) * d * (d + 1)  # flop of one symmetric matrix
+    for name, t, flop in (("without cross", t_s, 2 * sym), ("with cross", t_x, 2 * sym + 2.0 * n * d * d)):
+        print(f"  {name}: {t / t_em:6.2f} EM iterations, {t / t_cp:6.2f} copies of X, {flop / t / 1e9:6.2f} Tflop/s = "
+              f"{flop / t / 1e9 / MFMA_TFLOPS:5.3f} of the measured fp64 MFMA rate ({MFMA_TFLOPS} Tflop/s)")
+    print(f"  condition: without cross < 17 EM iterations: {t_s / t_em:.2f} -> {'met' if t_s < 17 * t_em else 'NOT met'}")
+
+if "--moments" in sys.argv:
+    moments_legs()
     sys.exit(0)
 
 def timed(name, fn, bytes_per_sample, reps=5):
