@@ -260,6 +260,32 @@ int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const double *a_
  * block cache and does not grow with N.  Synchronises. */
 int ppca_dataset_pairwise_moments(ppca_ctx *ctx, ppca_dataset *ds, const double *center_host, double *sums_host, double *counts_host,
                                   double *cross_host);
+/* ------------------------------------- masked k-means */
+/* ppca_dataset_kmeans_step: one Lloyd iteration.  centers_host (n_clusters x d, row-major, every entry finite), scale_host (d, nullable
+ * = 1, finite), n_clusters in 1 .. 16 (PPCA_ERR_UNSUPPORTED outside; a non-finite centre or scale: PPCA_ERR_INVALID, before any launch).
+ *   dist_ic   = sum_j m_ij (a_j (x_ij - mu_cj))^2     over the row's observed entries: difference, then scale, then square
+ *   labels[i] = the SMALLEST c that attains min_c dist_ic (an exact tie goes to the lowest index; a row with no observed entry: 0)
+ *   dist[i]   = that minimum                            labels, dist: n each, nullable, host or device destinations
+ *   sums_host [n_clusters][2][d], nullable:  tot_cj = sum_{i: labels[i] = c} w_i m_ij | sum_cj = sum_{i: labels[i] = c} w_i m_ij (x_ij - mu_cj)
+ *             (unscaled and centred on the OLD centre: nothing cancels).  The new centre is mu_cj + sum_cj / tot_cj where tot_cj > 0
+ *             and mu_cj elsewhere: the caller divides.
+ *   inertia_host (nullable) = sum_i w_i dist[i].  The dataset's weights enter sums and inertia, not the assignment.
+ *   reads_host (nullable): the sweeps over X the call made -- 1 with d <= 512 and n_clusters <= 8 (the sums are taken from the read
+ *             that assigns) and whenever sums_host is NULL and n_clusters <= 8; otherwise an assignment sweep per block of 8 centres
+ *             plus, with sums_host, an update sweep per block.
+ * Per-workgroup partials added in a fixed order (no float atomics): sums and inertia are bit-reproducible for a given grid; labels and
+ * dist do not depend on the grid at all.  An empty dataset gives zeros and writes no labels.  Scratch comes from the context's block
+ * cache: the partials and, when they are needed, the two per-row arrays.  Synchronises once. */
+int ppca_dataset_kmeans_step(ppca_ctx *ctx, ppca_dataset *ds, const double *centers_host, const double *scale_host, int32_t n_clusters,
+                             int32_t *labels, double *dist, double *sums_host, double *inertia_host, int32_t *reads_host);
+/* ppca_dataset_kmeans_seed: k-means++ from n_clusters caller-drawn numbers u_host in [0, 1).  Centre 0 is the smallest row r with
+ * cumsum(w)_r > u_0 sum(w); centre c >= 1 the smallest r with cumsum(w D)_r > u_c sum(w D), D_i the row's distance (as above) to the
+ * nearest centre chosen so far (that total 0: the rule of centre 0).  A centre made from row r is x_rj where observed and the weighted
+ * mean of column j over its observed entries (0 for an empty column) elsewhere.  The pick has two levels -- block sums of w D choose a
+ * block of rows, then only that block's slice comes to the host.  n_clusters - 1 reads of X plus the mean sweep.  centers_host
+ * (n_clusters x d); rows_host (n_clusters, nullable): the chosen rows.  An empty dataset: PPCA_ERR_EMPTY. */
+int ppca_dataset_kmeans_seed(ppca_ctx *ctx, ppca_dataset *ds, const double *scale_host, int32_t n_clusters, const double *u_host,
+                             double *centers_host, int64_t *rows_host);
 /* out_ij = x_ij, bit-exact, where ds is observed; fill_ij a_j elsewhere (fill: a dataset of the same shape; a_host: d).  A new
  * dataset carrying the weights of ds: the last step of the FA model's extrapolate.  Synchronises. */
 int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *fill, const double *a_host, ppca_dataset **out);

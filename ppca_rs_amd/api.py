@@ -190,6 +190,103 @@ class Dataset:
         check(lib().ppca_dataset_pairwise_moments(self._ctx.handle, self._h, ptr(c), ptr(sums), ptr(counts), ptr(cr)))
         return PairwiseMoments(c, sums, counts, cr)
 
+    def _kmeans_scale(self, scale) -> Optional[np.ndarray]:
+        """The column scale of the k-means calls: None, "std" or an array of length d, checked."""
+        d = self._d
+        if scale is None:
+            return None
+        if isinstance(scale, str):
+            if scale != "std":
+                raise ValueError(f"scale must be None, 'std' or an array of length {d}")
+            var = self.column_stats()[2]
+            return np.where(var > 0.0, 1.0 / np.sqrt(np.where(var > 0.0, var, 1.0)), 1.0)
+        a = f64(scale).reshape(-1)
+        if a.shape[0] != d:
+            raise ValueError(f"scale must have length {d}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("every entry of scale must be finite")
+        return a
+
+    def _kmeans_centers(self, centers) -> np.ndarray:
+        d = self._d
+        c = f64(centers)
+        if c.ndim != 2 or c.shape[1] != d:
+            raise ValueError(f"centers must have shape (K, {d})")
+        if not 1 <= c.shape[0] <= 16:
+            raise ValueError("the number of clusters must lie in 1 .. 16")
+        if not np.all(np.isfinite(c)):
+            raise ValueError("every entry of centers must be finite")
+        return c
+
+    def _kmeans_call(self, c: np.ndarray, a: Optional[np.ndarray], labels: bool, distances: bool, sums: bool) -> "KMeansStep":
+        n, d, nc = len(self), self._d, c.shape[0]
+        lab = np.zeros(n, dtype=np.int32) if labels else None
+        dist = np.zeros(n) if distances else None
+        out = np.zeros((nc, 2, d)) if sums else None
+        inertia, reads = C.c_double(0.0), C.c_int32(0)
+        check(lib().ppca_dataset_kmeans_step(self._ctx.handle, self._h, ptr(c), ptr(a), nc, ptr(lab), ptr(dist), ptr(out),
+                                             C.byref(inertia), C.byref(reads)))
+        return KMeansStep(c, out[:, 0] if sums else None, out[:, 1] if sums else None, inertia.value, labels=lab, distances=dist,
+                          reads=int(reads.value))
+
+    def kmeans_step(self, centers, scale=None, *, labels: bool = True, distances: bool = False) -> "KMeansStep":
+        """One Lloyd iteration of masked k-means on the GPU (ppca_dataset_kmeans_step): every row goes to the centre nearest to it over
+        the row's observed entries, dist_ic = sum_j m_ij (scale_j (x_ij - centers_cj))^2 (the lowest index on an exact tie; label 0 for a
+        row with no observed entry), and every cluster's weighted column sums over the observed entries of its rows come from the same
+        read of the dataset (d <= 512 and K <= 8; otherwise an assignment sweep and an update sweep per 8 centres: `reads`).
+
+        centers: (K, d), K in 1 .. 16, finite; scale: None or an array of length d, finite.  labels / distances: fetch the rows' labels
+        (int32) and distances to the host.  `KMeansStep.centers()` gives the updated centres.  A dataset without rows gives zeros (the
+        steps of row blocks add up: `KMeansStep.__add__`)."""
+        if isinstance(scale, str):
+            raise TypeError("scale must be None or an array here; Dataset.kmeans resolves 'std'")
+        return self._kmeans_call(self._kmeans_centers(centers), self._kmeans_scale(scale), bool(labels), bool(distances), True)
+
+    def _kmeans_seed(self, n_clusters: int, u, a: Optional[np.ndarray]):
+        """ppca_dataset_kmeans_seed: (centres (K, d), rows (K)) of k-means++ from the K numbers u in [0, 1)."""
+        d = self._d
+        u = f64(u, (n_clusters,))
+        centers, rows = np.empty((n_clusters, d)), np.empty(n_clusters, dtype=np.int64)
+        check(lib().ppca_dataset_kmeans_seed(self._ctx.handle, self._h, ptr(a), n_clusters, ptr(u), ptr(centers), ptr(rows)))
+        return centers, rows
+
+    def kmeans(self, n_clusters: int, *, n_iters: int = 20, seed: Optional[int] = None, scale=None, start=None) -> "KMeans":
+        """Masked k-means on the GPU: k-means++ seeding on the device (`numpy.random.default_rng(seed).random(n_clusters)` are the
+        numbers it picks with; `start`, (K, d) centres, replaces it), then at most `n_iters` Lloyd iterations of one `kmeans_step`
+        each without fetching labels, stopping early when a step leaves every centre bit-identical, then one labelling call.
+
+        scale: None; "std" (1 / the observed standard deviation of `column_stats()`, 1 for a column without variance: no column's
+        unit dominates the distance); or an array of length d.  Every step decreases the weighted inertia (`history`: the inertia
+        before each update); k-means has local optima, which a different seed may leave."""
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
+            raise TypeError("n_clusters must be an integer")
+        nc = int(n_clusters)
+        if not 1 <= nc <= 16:
+            raise ValueError("n_clusters must lie in 1 .. 16")
+        if int(n_iters) < 0:
+            raise ValueError("n_iters must be >= 0")
+        if start is not None:
+            centers = self._kmeans_centers(start).copy()
+            if centers.shape[0] != nc:
+                raise ValueError(f"start must have shape ({nc}, {self._d})")
+        if len(self) == 0:
+            raise ValueError("dataset is empty")
+        a = self._kmeans_scale(scale)
+        if start is None:
+            centers, _ = self._kmeans_seed(nc, np.random.default_rng(seed).random(nc), a)
+        history, converged = [], False
+        for _ in range(int(n_iters)):
+            step = self._kmeans_call(centers, a, False, False, True)
+            history.append(step.inertia)
+            new = step.centers()
+            if np.array_equal(new, centers):
+                converged = True
+                break
+            centers = new
+        last = self._kmeans_call(centers, a, True, False, False)
+        cw = np.bincount(last.labels, weights=self.weights(), minlength=nc).astype(np.float64)
+        return KMeans(centers, last.labels, last.inertia, np.array(history), cw, len(history), converged)
+
     def covariance(self, mode: str = "global", ddof: float = 0.0, center="mean") -> np.ndarray:
         """`pairwise_moments(center, cross=(mode == "pairwise")).covariance(mode, ddof)`."""
         return self.pairwise_moments(center, cross=(mode == "pairwise")).covariance(mode, ddof)
@@ -343,6 +440,76 @@ class PairwiseMoments:
         with np.errstate(divide="ignore", invalid="ignore"):
             sd = np.sqrt(np.diag(cov))
             return cov / np.outer(sd, sd)
+
+
+# --------------------------------------------------------------------------- masked k-means
+class KMeansStep:
+    """What `Dataset.kmeans_step` returns, host arrays: `labels` (int32 N, or None), `distances` (N, or None), `totals` and `sums`
+    ((K, d): tot_cj = sum of w_i over the rows of cluster c that observe column j, sum_cj = the same sum of w_i (x_ij - centre_cj),
+    unscaled and centred on the centre the step was taken from), `inertia` (sum_i w_i dist_i) and `reads` (sweeps over the dataset).
+    `a + b` adds the totals, sums and inertia of two steps taken with the same centres (chunks, shards); labels are dropped."""
+
+    def __init__(self, centers, totals, sums, inertia, *, labels=None, distances=None, reads: int = 0):
+        self._centers = np.array(centers, dtype=np.float64)
+        if self._centers.ndim != 2:
+            raise ValueError("centers must have shape (K, d)")
+        shape = self._centers.shape
+        self.totals = np.array(totals, dtype=np.float64).reshape(shape) if totals is not None else None
+        self.sums = np.array(sums, dtype=np.float64).reshape(shape) if sums is not None else None
+        self.inertia = float(inertia)
+        self.labels = labels
+        self.distances = distances
+        self.reads = int(reads)
+
+    def centers(self) -> np.ndarray:
+        """The updated centres: centre_cj + sum_cj / tot_cj where tot_cj > 0, the old centre_cj elsewhere (an empty cluster, or a
+        column a cluster never observes, keeps its value)."""
+        if self.totals is None:
+            return self._centers.copy()
+        ok = self.totals > 0.0
+        return np.where(ok, self._centers + self.sums / np.where(ok, self.totals, 1.0), self._centers)
+
+    def __add__(self, other: "KMeansStep") -> "KMeansStep":
+        if not isinstance(other, KMeansStep):
+            return NotImplemented
+        if self._centers.shape != other._centers.shape or not np.array_equal(self._centers, other._centers):
+            raise ValueError("the two steps were taken with different centres: their sums do not add")
+        if self.totals is None or other.totals is None:
+            raise ValueError("a step without sums does not add")
+        return KMeansStep(self._centers, self.totals + other.totals, self.sums + other.sums, self.inertia + other.inertia,
+                          reads=max(self.reads, other.reads))
+
+
+@dataclass
+class KMeans:
+    """What `Dataset.kmeans` returns: `centers` (K, d), the final `labels` (int32 N) and `inertia`, `history` (the inertia before each
+    update), `cluster_weights` (the sum of w over each cluster's rows), `n_iters_run` and `converged` (a step left every centre
+    bit-identical)."""
+
+    centers: np.ndarray
+    labels: np.ndarray
+    inertia: float
+    history: np.ndarray
+    cluster_weights: np.ndarray
+    n_iters_run: int
+    converged: bool
+
+
+def _kmeans_cluster_moments(dataset: Dataset, km: KMeans):
+    """([the pairwise moments of every cluster's rows, None for a cluster of weight 0], the whole dataset's where one is needed, the
+    log-weights of the start): K moment passes over the dataset with the weights w * (labels == c) -- rows of weight 0 add exactly
+    nothing there.  A cluster of weight 0 gets the weight of the lightest cluster that has some."""
+    labels = np.asarray(km.labels)
+    if labels.shape != (len(dataset),):
+        raise ValueError("km.labels and the dataset differ in length")
+    w = dataset.weights()
+    cw = np.asarray(km.cluster_weights, dtype=np.float64)
+    if not np.any(cw > 0.0):
+        raise ValueError("no cluster has any weight")
+    moms = [dataset.with_weights(w * (labels == c)).pairwise_moments() if cw[c] > 0.0 else None for c in range(cw.shape[0])]
+    whole = dataset.pairwise_moments() if any(m is None for m in moms) else None
+    cw = np.where(cw > 0.0, cw, cw[cw > 0.0].min())
+    return moms, whole, np.log(cw / cw.sum())
 
 
 def _spectral_start(sigma_mat: np.ndarray, live: np.ndarray, k: int):
@@ -1136,11 +1303,23 @@ class PPCAMix:
         self._lw = _log_softmax(lw)  # mix.rs:69
 
     @staticmethod
-    def init(n_models: int, state_size: int, dataset: Dataset, seed: Optional[int] = None) -> "PPCAMix":
-        """mix.rs:76-83"""
+    def init(n_models: int, state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "PPCAMix":
+        """mix.rs:76-83.  method="kmeans" (an extension): `from_kmeans(state_size, dataset, dataset.kmeans(n_models, seed=seed))`."""
+        if method == "kmeans":
+            return PPCAMix.from_kmeans(state_size, dataset, dataset.kmeans(n_models, seed=seed))
+        if method != "random":
+            raise ValueError("method must be 'random' or 'kmeans'")
         ss = np.random.SeedSequence(seed)
         seeds = [int(s.generate_state(1)[0]) for s in ss.spawn(n_models)]
         return PPCAMix([PPCAModel.init(state_size, dataset, seed=s) for s in seeds], np.zeros(n_models))
+
+    @staticmethod
+    def from_kmeans(state_size: int, dataset: Dataset, km: "KMeans") -> "PPCAMix":
+        """The k-means start: component c is `PPCAModel.from_moments` of the rows of cluster c (the dataset under the weights
+        w * (km.labels == c): one moment pass per cluster), log_weights = ln(cluster_weights / their sum).  A cluster of weight 0 takes
+        the whole dataset's `from_moments` model and the weight of the lightest cluster that has some."""
+        moms, whole, lw = _kmeans_cluster_moments(dataset, km)
+        return PPCAMix([PPCAModel.from_moments(state_size, m if m is not None else whole) for m in moms], lw)
 
     @property
     def output_size(self) -> int:
@@ -1459,8 +1638,9 @@ class PPCAMixTrainer:
 
     def train(self, *, start: Optional[PPCAMix] = None, prior: Optional[Prior] = None, n_models: int,
               state_size: int, n_iters: int = 10, metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False,
-              seed: Optional[int] = None) -> PPCAMix:
-        model = start or PPCAMix.init(n_models, state_size, self.dataset, seed=seed)
+              seed: Optional[int] = None, init: str = "random") -> PPCAMix:
+        """init: the `method` of `PPCAMix.init` when no `start` is given."""
+        model = start or PPCAMix.init(n_models, state_size, self.dataset, seed=seed, method=init)
         n = len(self.dataset)
         for idx in range(n_iters):
             if not quiet:
@@ -1546,11 +1726,34 @@ class FAMix:
 
     # -- construction -------------------------------------------------------------
     @staticmethod
-    def init(n_models: int, state_size: int, dataset: Dataset, seed: Optional[int] = None) -> "FAMix":
-        """The components of PPCAMix.init (same seed, same draws), noise = 1, equal weights."""
+    def init(n_models: int, state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "FAMix":
+        """The components of PPCAMix.init (same seed, same draws), noise = 1, equal weights.  method="kmeans":
+        `from_kmeans(state_size, dataset, dataset.kmeans(n_models, seed=seed, scale="std"))` -- clustered in units of every column's
+        own standard deviation, so that the whole start commutes with rescaling a column."""
+        if method == "kmeans":
+            return FAMix.from_kmeans(state_size, dataset, dataset.kmeans(n_models, seed=seed, scale="std"))
+        if method != "random":
+            raise ValueError("method must be 'random' or 'kmeans'")
         mix = PPCAMix.init(n_models, state_size, dataset, seed=seed)
         return FAMix(np.ones(mix.output_size), np.stack([m._c for m in mix._models]), np.stack([m._mean for m in mix._models]),
                      mix._lw)
+
+    @staticmethod
+    def from_kmeans(state_size: int, dataset: Dataset, km: "KMeans") -> "FAMix":
+        """The k-means start: per cluster `FAModel.from_moments` of the cluster's rows (the moments of PPCAMix.from_kmeans, the same rule
+        for a cluster of weight 0), weights as there; the shared noise pools the clusters' own, noise_j^2 = sum_c tot_cj noise_cj^2 /
+        sum_c tot_cj with tot_cj the weight of cluster c's rows that observe column j (1 where no cluster observes the column)."""
+        moms, whole, lw = _kmeans_cluster_moments(dataset, km)
+        parts = [FAModel.from_moments(state_size, m if m is not None else whole) for m in moms]
+        d = parts[0].output_size
+        num, den = np.zeros(d), np.zeros(d)
+        for m, f in zip(moms, parts):
+            if m is not None:
+                tot = np.diag(m._counts)
+                num += tot * f._noise ** 2
+                den += tot
+        noise = np.where(den > 0.0, np.sqrt(num / np.where(den > 0.0, den, 1.0)), 1.0)
+        return FAMix(noise, np.stack([f._c for f in parts]), np.stack([f._mean for f in parts]), lw)
 
     @staticmethod
     def from_ppca_mix(mix: PPCAMix) -> "FAMix":
@@ -1681,9 +1884,10 @@ class FAMixTrainer:
 
     def train(self, *, n_models: int, state_size: int, n_iters: int = 10, start: Optional[FAMix] = None,
               metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False, seed: Optional[int] = None,
-              min_noise_ratio: float = 1e-3) -> FAMix:
-        """min_noise_ratio: FATrainer's floor, ratio x the column's observed standard deviation."""
-        model = start or FAMix.init(n_models, state_size, self.dataset, seed=seed)
+              min_noise_ratio: float = 1e-3, init: str = "random") -> FAMix:
+        """min_noise_ratio: FATrainer's floor, ratio x the column's observed standard deviation.  init: the `method` of `FAMix.init`
+        when no `start` is given."""
+        model = start or FAMix.init(n_models, state_size, self.dataset, seed=seed, method=init)
         n = len(self.dataset)
         floor = min_noise_ratio * np.sqrt(self.dataset.column_stats()[2])
         for idx in range(n_iters):

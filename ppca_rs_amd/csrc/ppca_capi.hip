@@ -2512,6 +2512,188 @@ extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32
     return PPCA_OK;
 }
 
+// ------------------------------------------------------------------ masked k-means
+static int kmeans_check(const ppca_ctx *ctx, const ppca_dataset *ds, const double *scale_host, int32_t n_clusters) {
+    if (n_clusters < 1 || n_clusters > MIX_MAX) return fail(PPCA_ERR_UNSUPPORTED, "n_clusters must lie in [1, %d]", MIX_MAX);
+    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    if (scale_host)
+        for (int j = 0; j < ds->d; ++j)
+            if (!std::isfinite(scale_host[j])) return fail(PPCA_ERR_INVALID, "scale[%d] is not a finite number", j);
+    return PPCA_OK;
+}
+
+// kmeans_grid sizes the launch by what is resident per CU; a grid limit of the context (test hook) caps the launch itself, so that a
+// limit of 1 is one workgroup walking every row.
+static int kmeans_ctx_grid(const ppca_ctx *ctx, int64_t n, int nc) {
+    const int grid = kmeans_grid(n, nc, ctx->n_cu);
+    return ctx->n_cu < ctx->n_cu_device ? std::min(grid, std::max(ctx->n_cu, 1)) : grid;
+}
+
+extern "C" int ppca_dataset_kmeans_step(ppca_ctx *ctx, ppca_dataset *ds, const double *centers_host, const double *scale_host,
+                                        int32_t n_clusters, int32_t *labels, double *dist, double *sums_host, double *inertia_host,
+                                        int32_t *reads_host) {
+    if (!ctx || !ds || !centers_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = kmeans_check(ctx, ds, scale_host, n_clusters)) return rc;
+    const int64_t n = ds->n;
+    const int d = ds->d, K = n_clusters;
+    for (size_t e = 0; e < (size_t)K * d; ++e)
+        if (!std::isfinite(centers_host[e])) return fail(PPCA_ERR_INVALID, "centers[%zu][%zu] is not a finite number", e / d, e % d);
+    USE_CTX(ctx);
+    const size_t slen = (size_t)K * 2 * d;
+    if (sums_host) std::fill(sums_host, sums_host + slen, 0.0);
+    if (inertia_host) *inertia_host = 0.0;
+    if (reads_host) *reads_host = 0;
+    if (n == 0) return PPCA_OK;  // an empty dataset: zeros, no labels written
+    // fused: the sums by label from the read that assigns (a row fits the workgroup once, every centre in one launch)
+    const bool fused = sums_host && d <= 512 && K <= KMEANS_KB_MAX;
+    // the two per-row arrays, when they are needed: asked for, read by the update sweep, or carrying the minimum over centre blocks
+    const bool blocks = K > KMEANS_KB_MAX;
+    const bool rows_lab = labels || blocks || (sums_host && !fused), rows_dist = dist || blocks;
+    const int grid = kmeans_ctx_grid(ctx, n, K);
+    const int64_t plen = (sums_host ? (int64_t)slen : 0) + 1;  // [K][2][d] | inertia
+    BufRef cen, part, lab, dst;
+    if (int rc = dev_alloc(sizeof(double) * ((size_t)K * d + d), &cen)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * ((size_t)grid + 1) * plen, &part)) return rc;
+    if (rows_lab)
+        if (int rc = dev_alloc(sizeof(int32_t) * (size_t)n, &lab)) return rc;
+    if (rows_dist)
+        if (int rc = dev_alloc(sizeof(double) * (size_t)n, &dst)) return rc;
+    std::vector<double> h((size_t)K * d + d, 1.0), out((size_t)plen, 0.0);
+    std::memcpy(h.data(), centers_host, sizeof(double) * (size_t)K * d);
+    if (scale_host) std::memcpy(h.data() + (size_t)K * d, scale_host, sizeof(double) * d);
+    double *mu = static_cast<double *>(cen->p), *p = static_cast<double *>(part->p), *red = p + (size_t)grid * plen;
+    const double *a_dev = scale_host ? mu + (size_t)K * d : nullptr;
+    int32_t *lab_dev = lab ? static_cast<int32_t *>(lab->p) : nullptr;
+    double *dist_dev = dst ? static_cast<double *>(dst->p) : nullptr;
+    HIP_TRY(hipMemcpyAsync(mu, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, ctx->stream));
+    int reads = 0;
+    if (fused) {
+        HIP_TRY(launch_kmeans_assign(ds->X, ds->d, ds->w, n, d, mu, a_dev, K, 0, 0, lab_dev, dist_dev, true, p, plen, 1, grid, ctx->stream));
+        ++reads;
+    } else {
+        for (int k0 = 0; k0 < K; k0 += KMEANS_KB_MAX, ++reads) {  // centre blocks of 8, the running minimum in lab / dst
+            const int nc = std::min(KMEANS_KB_MAX, K - k0);
+            HIP_TRY(launch_kmeans_assign(ds->X, ds->d, ds->w, n, d, mu + (size_t)k0 * d, a_dev, nc, k0, k0 > 0, lab_dev, dist_dev, false, p,
+                                         plen, k0 + nc == K, grid, ctx->stream));
+        }
+        if (sums_host)
+            for (int k0 = 0; k0 < K; k0 += KMEANS_KB_MAX, ++reads)
+                HIP_TRY(launch_kmeans_update(ds->X, ds->d, ds->w, n, d, mu + (size_t)k0 * d, std::min(KMEANS_KB_MAX, K - k0), k0, lab_dev, p,
+                                             plen, grid, ctx->stream));
+    }
+    HIP_TRY(launch_reduce_partials(p, grid, plen, red, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out.data(), red, sizeof(double) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (labels)  // (host or device destinations, as ppca_llk's per-sample output)
+        HIP_TRY(hipMemcpyAsync(labels, lab_dev, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, ctx->stream));
+    if (dist) HIP_TRY(hipMemcpyAsync(dist, dist_dev, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the one synchronisation; h is read until here)
+    if (sums_host) std::memcpy(sums_host, out.data(), sizeof(double) * slen);
+    if (inertia_host) *inertia_host = out[(size_t)plen - 1];
+    if (reads_host) *reads_host = reads;
+    return PPCA_OK;
+}
+
+// The smallest row r of the dataset with cumsum(w D)_r > u * total (w, D nullable = 1), in two levels: the block sums of
+// launch_wd_block_sums choose the block, then only that block's slice of w and D comes to the host.  total_out: the sum of the blocks.
+static int kmeans_pick(ppca_ctx *ctx, const ppca_dataset *ds, const double *dist_dev, double u, double *bs_dev, int64_t *row,
+                       double *total_out) {
+    const int64_t n = ds->n, nb = wd_blocks(n), br = wd_block_rows();
+    std::vector<double> bs((size_t)nb);
+    HIP_TRY(launch_wd_block_sums(ds->w, dist_dev, n, bs_dev, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(bs.data(), bs_dev, sizeof(double) * bs.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    double total = 0.0;
+    for (double v : bs) total += v;
+    *total_out = total;
+    if (!(total > 0.0) || !std::isfinite(total)) return PPCA_OK;  // (the caller falls back to the rule of centre 0, or fails)
+    const double target = u * total;
+    int64_t b = -1, last = -1;
+    double before = 0.0, run = 0.0;
+    for (int64_t q = 0; q < nb; ++q) {  // the first block whose running sum passes the target
+        if (bs[(size_t)q] > 0.0) last = q;
+        if (run + bs[(size_t)q] > target) {
+            b = q;
+            before = run;
+            break;
+        }
+        run += bs[(size_t)q];
+    }
+    if (b < 0) {  // (rounding at the very end: the last block that weighs anything)
+        b = last;
+        before = 0.0;
+        for (int64_t q = 0; q < b; ++q) before += bs[q];
+    }
+    const int64_t b0 = b * br, len = std::min(br, n - b0);
+    std::vector<double> wv((size_t)len, 1.0), dv((size_t)len, 1.0);
+    if (ds->w) HIP_TRY(hipMemcpyAsync(wv.data(), ds->w + b0, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist_dev) HIP_TRY(hipMemcpyAsync(dv.data(), dist_dev + b0, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    double cum = before;
+    int64_t pick = -1, heavy = -1;
+    for (int64_t i = 0; i < len && pick < 0; ++i) {
+        const double term = wv[(size_t)i] * dv[(size_t)i];
+        if (term > 0.0) heavy = i;
+        cum += term;
+        if (cum > target) pick = i;
+    }
+    if (pick < 0) pick = heavy >= 0 ? heavy : len - 1;  // (the block's sum and its scan round differently: its last row of weight)
+    *row = b0 + pick;
+    return PPCA_OK;
+}
+
+extern "C" int ppca_dataset_kmeans_seed(ppca_ctx *ctx, ppca_dataset *ds, const double *scale_host, int32_t n_clusters,
+                                        const double *u_host, double *centers_host, int64_t *rows_host) {
+    if (!ctx || !ds || !u_host || !centers_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = kmeans_check(ctx, ds, scale_host, n_clusters)) return rc;
+    const int64_t n = ds->n;
+    const int d = ds->d, K = n_clusters;
+    for (int c = 0; c < K; ++c)
+        if (!(u_host[c] >= 0.0 && u_host[c] < 1.0)) return fail(PPCA_ERR_INVALID, "u[%d] does not lie in [0, 1)", c);
+    if (n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
+    USE_CTX(ctx);
+    // g: the weighted column means over the observed entries (0 for an empty column), one sums-only sweep
+    std::vector<double> one((size_t)d, 1.0), sums((size_t)3 * d), g((size_t)d, 0.0);
+    if (int rc = ppca_dataset_scale_columns(ctx, ds, one.data(), nullptr, nullptr, nullptr, sums.data(), nullptr)) return rc;
+    for (int j = 0; j < d; ++j)
+        if (sums[j] > 0.0) g[j] = sums[(size_t)d + j] / sums[j];
+    const int grid = kmeans_ctx_grid(ctx, n, 1);
+    BufRef cen, dst, bsb;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)2 * d, &cen)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)n, &dst)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)wd_blocks(n), &bsb)) return rc;
+    double *mu = static_cast<double *>(cen->p), *dist_dev = static_cast<double *>(dst->p), *bs_dev = static_cast<double *>(bsb->p);
+    BufRef labb;
+    if (int rc = dev_alloc(sizeof(int32_t) * (size_t)n, &labb)) return rc;  // (the running minimum carries a label with it)
+    int32_t *lab_dev = static_cast<int32_t *>(labb->p);
+    if (scale_host) {
+        HIP_TRY(hipMemcpyAsync(mu + d, scale_host, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    std::vector<double> row((size_t)d);
+    for (int c = 0; c < K; ++c) {
+        int64_t r = -1;
+        double total = 0.0;
+        if (c > 0)
+            if (int rc = kmeans_pick(ctx, ds, dist_dev, u_host[c], bs_dev, &r, &total)) return rc;
+        if (r < 0) {  // centre 0, or every row sits on a centre already: by the weights alone
+            if (int rc = kmeans_pick(ctx, ds, nullptr, u_host[c], bs_dev, &r, &total)) return rc;
+            if (r < 0) return fail(PPCA_ERR_INVALID, "the weights of the dataset do not sum to a positive finite number");
+        }
+        HIP_TRY(hipMemcpyAsync(row.data(), ds->X + r * ds->d, sizeof(double) * d, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        double *ch = centers_host + (size_t)c * d;
+        for (int j = 0; j < d; ++j) ch[j] = std::isfinite(row[j]) ? row[j] : g[j];  // a centre must be complete
+        if (rows_host) rows_host[c] = r;
+        if (c + 1 < K) {  // D: the running minimum over the centres so far, one 1-centre sweep per new centre
+            HIP_TRY(hipMemcpyAsync(mu, ch, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(launch_kmeans_assign(ds->X, ds->d, ds->w, n, d, mu, scale_host ? mu + d : nullptr, 1, c, c > 0, lab_dev, dist_dev, false,
+                                         nullptr, 0, 0, grid, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));  // (ch may be rewritten by the caller's next pick only after the copy)
+        }
+    }
+    return PPCA_OK;
+}
+
 // ------------------------------------------------------------------ mixture of factor analysers, shared column noise
 extern "C" int ppca_dataset_column_moments_multi(ppca_ctx *ctx, ppca_dataset *ds, const double *e_host, const double *e_dev, int32_t n_comp,
                                                  const double *a_host, const double *b_host, double *sums_host) {

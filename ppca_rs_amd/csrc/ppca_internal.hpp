@@ -304,6 +304,24 @@ int moments_multi_grid(int64_t n, int nc, int n_cu);
 hipError_t launch_column_moments_multi(const double *X, int64_t ldx, int64_t n, int d, const double *e_dev, int nc, const double *a_dev,
                                        const double *b_dev, double *part, int grid, hipStream_t s);
 
+// masked k-means (ppca_kmeans.hip).  launch_kmeans_assign: one sweep with the nc <= KMEANS_KB_MAX complete
+// centres mu_dev[nc][d] (labels k0 .. k0 + nc) and the column scale a_dev (nullable = 1): labels / dist (nullable, n) = the nearest
+// centre over the observed entries and its distance, the lowest index on a tie; carry: the minimum over the centre blocks before is in
+// labels / dist.  accumulate (d <= 512, every centre in the launch): the workgroups' sums part[grid][plen] = [nc][2][d] tot / sum by
+// label, from the same read of X.  inertia: the workgroups' sum_i w_i dist_i at part[.][plen - 1].  launch_kmeans_update: tot / sum of
+// the centres k0 .. k0 + nc from the labels of an earlier sweep.  Reduce with launch_reduce_partials over plen; grid = kmeans_grid.
+// launch_wd_block_sums: out[b] = sum of w_i dist_i (both nullable = 1) over the rows of block b (wd_block_rows() rows, wd_blocks(n)).
+constexpr int KMEANS_KB_MAX = 8;
+int kmeans_grid(int64_t n, int nc, int n_cu);
+hipError_t launch_kmeans_assign(const double *X, int64_t ldx, const double *w, int64_t n, int d, const double *mu_dev, const double *a_dev,
+                                int nc, int k0, int carry, int32_t *labels, double *dist, bool accumulate, double *part, int64_t plen,
+                                int inertia, int grid, hipStream_t s);
+hipError_t launch_kmeans_update(const double *X, int64_t ldx, const double *w, int64_t n, int d, const double *mu_dev, int nc, int k0,
+                                const int32_t *labels, double *part, int64_t plen, int grid, hipStream_t s);
+int64_t wd_blocks(int64_t n);
+int64_t wd_block_rows();
+hipError_t launch_wd_block_sums(const double *w, const double *dist, int64_t n, double *out, hipStream_t s);
+
 // pairwise second moments (ppca_moments.hip): sums = X~^T diag(w) X~, counts = M^T diag(w) M and (cross
 // nullable) cross = X~^T diag(w) M, d x d row-major each, x~ = x - center on observed entries.  A job = (pair of 64-column tiles,
 // I <= J) x (run of rows); its partials go to part (p.scratch_bytes) and a second kernel adds the runs in order and mirrors the

@@ -9,7 +9,11 @@ column sweep at NM components (device-resident weights), ppca_mix_em_step and pp
 difference of the two goes to (the whitening pass, the sweep, the host finalisation).  `--moments` runs ONLY the legs of the
 pairwise second moments, in one process: the pass without and with `cross`, one PPCA iteration (ppca_em_step at
 state size k) and the device-to-device copy of X; per pass the multiple of one EM iteration and the fraction of the measured fp64
-MFMA rate (profiles/r04/mfma_peak.txt), counting n d (d + 1) flop per symmetric matrix."""
+MFMA rate (profiles/r04/mfma_peak.txt), counting n d (d + 1) flop per symmetric matrix.  `--kmeans K` runs ONLY the legs of masked
+k-means and the k-means start, in one process: the fused Lloyd step, the labelling-only call, the two-sweep composition
+the fused step replaces (a labelling call, then ppca_dataset_column_moments_multi with one-hot weights), the sums-only scale pass (one
+read of X: the floor), the whole `Dataset.kmeans` (seeding plus iterations), the K moment passes of `from_kmeans`, and one
+ppca_mix_em_step at K components."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -234,6 +238,98 @@ def moments_legs(reps=12):
 
 if "--moments" in sys.argv:
     moments_legs()
+    sys.exit(0)
+
+def kmeans_legs(nc, reps=12):
+    from ppca_rs_amd.api import _kmeans_cluster_moments
+
+    def series(fn, reps=reps):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts, nbytes=None):
+        med = float(np.median(ts))
+        rate = f"{nbytes/med/1e6:8.1f} GB/s" if nbytes else " " * 13
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  {rate}  ({len(ts)} repetitions)", flush=True)
+        return med
+
+    rng = np.random.default_rng(5)
+    nd_bytes = 8.0 * n * d
+    _, mean, var = ds.column_stats()
+    centers = np.ascontiguousarray(mean + np.sqrt(var) * rng.standard_normal((nc, d)))
+    sums, inertia, reads = np.empty((nc, 2, d)), C.c_double(), C.c_int32()
+    lab_buf = P.Dataset(np.zeros((n, 1)))  # n x 8 bytes on the device: the destination of the labels
+    lab_dev = C.c_void_p(L.ppca_dataset_device_x(lab_buf._h))
+    def step():
+        _lib.check(L.ppca_dataset_kmeans_step(ctx.handle, ds._h, _lib.ptr(centers), None, nc, None, None, _lib.ptr(sums), C.byref(inertia),
+                                              C.byref(reads)))
+    def label():
+        _lib.check(L.ppca_dataset_kmeans_step(ctx.handle, ds._h, _lib.ptr(centers), None, nc, lab_dev, None, None, C.byref(inertia),
+                                              C.byref(reads)))
+    # the composition the fused step replaces: labels, then the column sums of K one-hot weight vectors (device-resident)
+    lab_host = np.zeros(n, dtype=np.int32)
+    _lib.check(L.ppca_dataset_kmeans_step(ctx.handle, ds._h, _lib.ptr(centers), None, nc, _lib.ptr(lab_host), None, None, C.byref(inertia),
+                                          C.byref(reads)))
+    print(f"  rows per cluster under these centres: {np.bincount(lab_host, minlength=nc).tolist()}", flush=True)
+    onehot = np.zeros((nc, n))
+    onehot[lab_host, np.arange(n)] = 1.0  # the labels' own one-hot weights: what the composition would hand to the sweep
+    del lab_host
+    E = P.Dataset(onehot.reshape(-1, 1))
+    del onehot
+    e_dev = C.c_void_p(L.ppca_dataset_device_x(E._h))
+    msums = np.empty((nc, 3, d))
+    def multi():
+        _lib.check(L.ppca_dataset_column_moments_multi(ctx.handle, ds._h, None, e_dev, nc, None, _lib.ptr(centers), _lib.ptr(msums)))
+    def composition():
+        label(); multi()
+    one, ssums = np.ones(d), np.empty((3, d))
+    def scale():
+        _lib.check(L.ppca_dataset_scale_columns(ctx.handle, ds._h, _lib.ptr(one), _lib.ptr(mean), None, None, _lib.ptr(ssums), None))
+    t_f, t_c, t_s = [], [], []
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        t_s.append(series(scale, reps // 2)); t_f.append(series(step, reps // 2)); t_c.append(series(composition, reps // 2))
+    step()
+    r_step = reads.value
+    ts = report("(a) scale pass, sums only (one read of X: the floor)", np.concatenate(t_s), nd_bytes)
+    tf = report(f"(b) Lloyd step, K = {nc} ({r_step} read{'s' if r_step != 1 else ''} of X)", np.concatenate(t_f), r_step * nd_bytes)
+    tl = report(f"(c) labelling only, K = {nc} (labels to a device buffer)", series(label), nd_bytes)
+    tc = report(f"(d) labelling + one-hot multi-component sweep, K = {nc}", np.concatenate(t_c), 2 * nd_bytes)
+    print(f"  (b) / (a) = {tf / ts:.3f}   (c) / (a) = {tl / ts:.3f}   (b) / (d) = {tf / tc:.3f}   "
+          f"({'the step is faster than the composition' if tf < tc else 'the step is NOT faster than the composition'})")
+    del E
+    kms = []
+    def whole():
+        kms.append(ds.kmeans(nc, seed=1))
+    t_km = report(f"(e) Dataset.kmeans({nc}): seeding + Lloyd iterations + labels", series(whole, 3))
+    km = kms[-1]
+    print(f"  iterations run {km.n_iters_run}, converged {km.converged}, inertia {km.history[0]:.6g} -> {km.inertia:.6g}")
+    t_mo = report(f"(f) the {nc} moment passes of from_kmeans", series(lambda: _kmeans_cluster_moments(ds, km), 3))
+    comps = [P.PPCAModel(1.0, m.transform + 0.1 * rng.standard_normal((d, k)), m.mean) for _ in range(nc)]
+    mix = P.PPCAMix(comps, np.full(nc, -np.log(nc)))
+    devs, arr = mix._handles(ctx)
+    outs = []
+    for _ in range(nc):
+        hh = C.c_void_p()
+        _lib.check(L.ppca_model_alloc(ctx.handle, d, k, C.byref(hh)))
+        outs.append(hh)
+    oarr = (C.c_void_p * nc)(*outs)
+    lw_out, llk = np.empty(nc), C.c_double()
+    t_em = report(f"(g) PPCA mixture iteration (ppca_mix_em_step, K = {nc}, k = {k})",
+                  series(lambda: _lib.check(L.ppca_mix_em_step(ctx.handle, ds._h, arr, _lib.ptr(mix._lw), nc, None, oarr, _lib.ptr(lw_out),
+                                                               C.byref(llk)))))
+    for hh in outs:
+        L.ppca_model_free(hh)
+    print(f"  the whole start: (e) + (f) = {t_km + t_mo:.3f} ms = {(t_km + t_mo) / t_em:.2f} mixture EM iterations "
+          f"((e) {t_km / t_em:.2f}, (f) {t_mo / t_em:.2f}); one Lloyd step = {tf / t_em:.3f} iterations")
+
+if "--kmeans" in sys.argv:
+    kmeans_legs(int(sys.argv[sys.argv.index("--kmeans") + 1]))
     sys.exit(0)
 
 def timed(name, fn, bytes_per_sample, reps=5):
