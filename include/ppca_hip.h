@@ -354,6 +354,53 @@ int ppca_famix_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, in
                        const double *means, const double *log_weights, const double *min_noise, double *noise_out,
                        double *transforms_out, double *means_out, double *log_weights_out, double *llk_in);
 
+/* --------------------------------------------------- Student-t PPCA for masked data */
+/* An extension with no reference counterpart (Archambeau, Delannay and Verleysen's robust PPCA; the ECM of Lange, Little and Taylor):
+ * x | u = C z + mean + eps with z ~ N(0, I / u), eps ~ N(0, sigma^2 I / u) and u ~ Gamma(nu / 2, rate nu / 2), so the observed part of a
+ * row is multivariate t with nu degrees of freedom.  A model is (sigma, C, mean) -- an ordinary ppca_model -- and nu.  For a row with m
+ * observed entries, posterior mean z (what ppca_infer returns: it does not depend on nu), x~ = x_O - mean_O and r = x~ - C_O z:
+ *   delta = (|r|^2 + sigma^2 |z|^2) / sigma^2                 the Mahalanobis distance x~^T (C_O C_O^T + sigma^2 I)^-1 x~
+ *   u     = (nu + m) / (nu + delta)                           the row's weight E[u | x]: small = outlying, at most (nu + m) / nu
+ *   ell   = lg[m] - 1/2 logdet - 1/2 (nu + m) log1p(delta / nu)   the t log-density, logdet = (m - k) ln sigma^2 + ln det M
+ * A row without an observed entry has delta = 0, u = 1, ell = 0.  Covers 1 <= k <= 16 and 1 <= d <= 1024 (PPCA_ERR_UNSUPPORTED beyond,
+ * before any launch).
+ *
+ * ppca_t_tables_host: host only.  lg_out[m] = ln Gamma((nu + m) / 2) - ln Gamma(nu / 2) - (m / 2) ln(nu pi) and
+ * g_out[m] = psi((nu + m) / 2) - ln((nu + m) / 2) for m = 0 .. d (d + 1 doubles each); std::lgamma (Stirling's series term by term from
+ * nu >= 2e4 on, where the difference of the two values cancels), digamma by upward recurrence and its asymptotic series. */
+int ppca_t_tables_host(int32_t d, double dof, double *lg_out, double *g_out);
+/* ppca_t_estep: the posterior pass of ppca_infer / ppca_llk into (k + 1) doubles per row of scratch (by row chunks of at most 1 GiB), then
+ * ONE streaming sweep over the dataset.  Every output is nullable; at least one must be given.
+ *   scaled_out     a new dataset y_ij = sqrt(u_i) (x_ij - mean_j) -- bit for bit fl(fl(sqrt(u_i)) fl(x_ij - mean_j)) -- NaN on masked
+ *                  entries, carrying the weights of ds; without it no n x d buffer is allocated or written
+ *   col_sums_host  (k + 3) d doubles, V (d x k) | A (d) | T (d) | sq (d): V_j = sum_i w u m_ij z_i, A_j = sum w u m x~_j, T_j = sum w u m,
+ *                  sq_j = sum w u m x~_j^2
+ *   u, maha, llks  n doubles each: u_i, delta_i, ell_i (host or device destinations, as ppca_llk's per-sample output)
+ *   scalars_host   4 doubles: sum w | sum w ell | sum w (g[m] + ln u - u) | rows with an observed entry
+ * Per-workgroup partials added in a fixed order (no float atomics): the sums are bit-reproducible for a given grid; the per-row outputs
+ * and the scaled rows do not depend on the grid, the chunks or a slice's offset.  An empty dataset gives zeros.  Synchronises once. */
+int ppca_t_estep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, double dof, ppca_dataset **scaled_out, double *col_sums_host,
+                 double *u, double *maha, double *llks, double *scalars_host);
+/* The ECM M-step on host buffers (no GPU needed, like ppca_fa_finalize_host).  stats: the packed statistics of the EM pass of
+ * PPCAModel(sigma, C, 0) on the scaled rows Y of ppca_t_estep -- cross_j = sum w u m x~_j z, S_j = sum w m (Sigma + u z z^T),
+ * totals_j = sum w m; col_sums: ppca_t_estep's.  Each block is maximised given the blocks already updated, so the t log-likelihood
+ * cannot decrease.  Per column j:
+ *   1. c_j = solution of S_j a = cross_j by the Cholesky row solve; a pivot <= 0 keeps the old row; no prior term
+ *   2. delta_j = (A_j - c_j . V_j) / T_j with the NEW c_j (0 if T_j = 0); mean_j += delta_j
+ *   3. sigma^2 = sum_j (sq_j - 2 c_j . cross_j + c_j^T S_j c_j - delta_j^2 T_j) / sum_j totals_j; a non-finite or non-positive value
+ *      keeps the old sigma
+ * This is not the reference's EM step (which uses the old C in its mean and noise updates); as nu -> infinity, u -> 1 and it becomes
+ * the ECM step of ppca_fa_finalize_host's block order with one pooled noise.  Outputs may not alias inputs.  k >= 1. */
+int ppca_t_finalize_host(int32_t d, int32_t k, double sigma, const double *transform, const double *mean, const double *stats,
+                         const double *col_sums, double *sigma_out, double *transform_out, double *mean_out);
+/* One Student-t ECM iteration on a single GPU: the sweep of ppca_t_estep with the scaled rows, ppca_em_accumulate on them with the
+ * model (sigma, C, 0), statistics to the host, ppca_t_finalize_host; the scaled rows are released before returning (peak device memory:
+ * twice the dataset).  llk_in (nullable): the t log-likelihood of the INPUT model, sum_i w_i ell_i; q_out (nullable):
+ * q = sum w (g[m] + ln u - u) / sum w, with which the degrees of freedom are updated as the root of ln(nu / 2) - psi(nu / 2) + 1 + q = 0.
+ * One synchronisation of its own per call (uploads and downloads are queued behind the kernels). */
+int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, double sigma, const double *transform, const double *mean,
+                   double dof, double *sigma_out, double *transform_out, double *mean_out, double *llk_in, double *q_out);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration

@@ -1279,6 +1279,254 @@ class FATrainer:
         return model.to_canonical()
 
 
+# --------------------------------------------------------------------------- Student-t PPCA (robust to outlying rows)
+def _t_tables(d: int, dof: float):
+    lg, g = np.empty(d + 1), np.empty(d + 1)
+    check(lib().ppca_t_tables_host(int(d), float(dof), ptr(lg), ptr(g)))
+    return lg, g
+
+
+def _t_dof_root(q: float, lo: float = 0.5, hi: float = 1e4) -> float:
+    """The root of ln(nu / 2) - psi(nu / 2) + 1 + q = 0 by bisection on [lo, hi]; the upper end when there is no sign change.
+    -(psi(x) - ln x) comes from ppca_t_tables_host (its g[0] at nu = 2 x)."""
+    def f(nu):
+        return -_t_tables(0, nu)[1][0] + 1.0 + q
+    flo, fhi = f(lo), f(hi)
+    if not (flo > 0.0 and fhi < 0.0):  # f falls from +inf to 1 + q: no sign change in the bracket (or q is not a number)
+        return hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if f(mid) > 0.0:
+            lo = mid
+        else:
+            hi = mid
+        if hi - lo <= 1e-13 * hi:
+            break
+    return 0.5 * (lo + hi)
+
+
+class TPPCAModel:
+    """Masked Student-t PPCA: a row is y = mean + (C x + noise) / sqrt(u) with x ~ N(0, I), noise ~ N(0, isotropic_noise^2 I) and a
+    latent scale u ~ Gamma(dof / 2, rate dof / 2) per row, so outlying rows get a small weight E[u | y] instead of pulling the mean,
+    the subspace and the noise (an extension with no reference counterpart; include/ppca_hip.h).
+
+    Given u a row is a Gaussian row scaled by 1 / sqrt(u): an iteration is one streaming sweep (distances, weights, log-densities, the
+    scaled rows, a few column sums) and the EM pass of PPCAModel on the scaled rows.  The step is an ECM step (transform, then mean,
+    then noise, each given the ones before it), not the reference's EM step; as dof -> infinity it becomes that ECM step of the
+    Gaussian model.  LIMITS: state sizes 1 .. 16, output sizes 1 .. 1024.
+    """
+
+    MAX_STATE_SIZE, MAX_OUTPUT_SIZE = 16, 1024
+
+    def __init__(self, isotropic_noise: float, transform, mean, dof: float, *, ctx=None, _estimated_dof: bool = False):
+        base = PPCAModel(isotropic_noise, transform, mean, ctx=ctx)  # (the checks of transform and mean are PPCAModel's)
+        dof = float(dof)
+        if not (np.isfinite(dof) and dof > 0.0):
+            raise ValueError("dof must be a positive finite number")
+        if not (np.isfinite(base._sigma) and base._sigma > 0.0):
+            raise ValueError("isotropic_noise must be a positive finite number")
+        d, k = base.output_size, base.state_size
+        if k < 1 or k > self.MAX_STATE_SIZE or d < 1 or d > self.MAX_OUTPUT_SIZE:
+            raise ValueError(f"the Student-t sweep covers state sizes 1 .. {self.MAX_STATE_SIZE} and output sizes 1 .. "
+                             f"{self.MAX_OUTPUT_SIZE} (got k={k}, d={d})")
+        self._base, self._dof, self._ctx, self._estimated = base, dof, ctx, bool(_estimated_dof)
+
+    # -- getters ----------------------------------------------------------------
+    @property
+    def isotropic_noise(self) -> float:
+        return self._base._sigma
+
+    @property
+    def transform(self) -> np.ndarray:
+        return self._base._c.copy()
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self._base._mean.copy()
+
+    @property
+    def dof(self) -> float:
+        return self._dof
+
+    @property
+    def output_size(self) -> int:
+        return self._base.output_size
+
+    @property
+    def state_size(self) -> int:
+        return self._base.state_size
+
+    @property
+    def n_parameters(self) -> int:
+        """The Gaussian count, plus one once the degrees of freedom have been estimated (iterate(..., estimate_dof=True))."""
+        return self._base.n_parameters + (1 if self._estimated else 0)
+
+    def __repr__(self) -> str:
+        return (f"TPPCAModel(isotropic_noise={self._base._sigma}, transform=array({self._base._c}), mean=array({self._base._mean}), "
+                f"dof={self._dof})")
+
+    # -- construction -------------------------------------------------------------
+    @staticmethod
+    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random", dof: float = 4.0) -> "TPPCAModel":
+        """The start of PPCAModel.init (same seed, same draw; method="pca": its spectral start) with `dof` degrees of freedom."""
+        if state_size < 1:
+            raise ValueError("state_size must be >= 1")
+        return TPPCAModel.from_ppca(PPCAModel.init(state_size, dataset, seed=seed, method=method), dof)
+
+    @staticmethod
+    def from_ppca(model: PPCAModel, dof: float) -> "TPPCAModel":
+        """The t model with the Gaussian model's sigma, C and mean."""
+        return TPPCAModel(model._sigma, model._c, model._mean, dof, ctx=model._ctx)
+
+    def gaussian(self) -> PPCAModel:
+        """PPCAModel with the same sigma, C and mean (the limit dof -> infinity)."""
+        return self._base
+
+    def to_canonical(self) -> "TPPCAModel":
+        """The rotation of PPCAModel.to_canonical on C; sigma, mean and dof are untouched."""
+        b = self._base.to_canonical()
+        return TPPCAModel(b._sigma, b._c, b._mean, self._dof, ctx=self._ctx, _estimated_dof=self._estimated)
+
+    def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None, *, ctx=None) -> Dataset:
+        """Host-side numpy (like posterior_sampler(), not a GPU path): Gaussian rows C x + noise, divided by sqrt(u) with
+        u ~ Gamma(dof / 2, rate dof / 2), the mean added, then masked independently with probability mask_prob."""
+        if not (0.0 <= mask_prob <= 1.0):
+            raise ValueError("invalid mask probability")
+        rng = np.random.default_rng(seed)
+        n, d, k = int(dataset_size), self.output_size, self.state_size
+        rows = rng.standard_normal((n, k)) @ self._base._c.T + self._base._sigma * rng.standard_normal((n, d))
+        u = rng.gamma(0.5 * self._dof, 2.0 / self._dof, size=n)
+        x = self._base._mean + rows / np.sqrt(u)[:, None]
+        x[rng.random((n, d)) < mask_prob] = np.nan
+        return Dataset(x, ctx=ctx or self._ctx)
+
+    # -- passes ---------------------------------------------------------------------
+    def _estep(self, dataset: Dataset, *, scaled: bool = False, col_sums: bool = False, u: bool = False, maha: bool = False,
+               llks: bool = False, scalars: bool = False):
+        """ppca_t_estep: (scaled rows as a Dataset, column sums V | A | T | sq, u, delta, llks, scalars), None where not asked for."""
+        if dataset._d != self.output_size:
+            raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {self.output_size}")
+        ctx, n, d, k = dataset._ctx, len(dataset), self.output_size, self.state_size
+        h = C.c_void_p()
+        cs = np.empty((k + 3) * d) if col_sums else None
+        uu, mm, ll = (np.empty(n) if f else None for f in (u, maha, llks))
+        sc = np.empty(4) if scalars else None
+        check(lib().ppca_t_estep(ctx.handle, dataset._h, self._base._device(ctx).h, self._dof, C.byref(h) if scaled else None, ptr(cs),
+                                 ptr(uu), ptr(mm), ptr(ll), ptr(sc)))
+        return (Dataset._wrap(h, ctx) if scaled else None), cs, uu, mm, ll, sc
+
+    def llks(self, dataset: Dataset) -> np.ndarray:
+        """Per-sample t log-density of the observed entries (0 for a row without any)."""
+        return self._estep(dataset, llks=True)[4]
+
+    def llk(self, dataset: Dataset) -> float:
+        """Weighted t log-likelihood."""
+        return float(self._estep(dataset, scalars=True)[5][1])
+
+    def row_weights(self, dataset: Dataset) -> np.ndarray:
+        """The rows' weights E[u | y] = (dof + m) / (dof + delta): a per-row anomaly score from one pass -- small means outlying; at
+        most (dof + m) / dof; 1 for a row without an observed entry."""
+        return self._estep(dataset, u=True)[2]
+
+    def mahalanobis(self, dataset: Dataset):
+        """(delta, m): the rows' squared Mahalanobis distances (x - mean)_O^T (C_O C_O^T + sigma^2 I)^-1 (x - mean)_O and their
+        numbers of observed entries (a second streaming pass counts them)."""
+        delta = self._estep(dataset, maha=True)[3]
+        m = dataset._scale_columns(np.ones(self.output_size), l=np.ones(self.output_size), out=False, row_sums=True)[2]
+        return delta, np.rint(m).astype(np.int64)
+
+    def infer(self, dataset: Dataset) -> "InferredMasked":
+        """The posterior of gaussian(): the posterior mean of the state does not depend on dof; covariances() are the u = 1
+        covariances (given the row's scale u they are these divided by u)."""
+        return self._base.infer(dataset)
+
+    def smooth(self, dataset: Dataset) -> Dataset:
+        """C z + mean for every dimension (gaussian().smooth)."""
+        return self._base.smooth(dataset)
+
+    def extrapolate(self, dataset: Dataset) -> Dataset:
+        """Observed values kept, masked ones replaced by C z + mean (gaussian().extrapolate)."""
+        return self._base.extrapolate(dataset)
+
+    def _iterate(self, dataset: Dataset, estimate_dof: bool, want_llk: bool):
+        ctx = dataset._ctx
+        if len(dataset) == 0:
+            raise ValueError("dataset is empty")
+        d, k = self.output_size, self.state_size
+        if dataset._d != d:
+            raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {d}")
+        s_out, c_out, m_out = C.c_double(0.0), np.empty((d, k)), np.empty(d)
+        llk, q = C.c_double(0.0), C.c_double(0.0)
+        check(lib().ppca_t_em_step(ctx.handle, dataset._h, d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean), self._dof,
+                                   C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None,
+                                   C.byref(q) if estimate_dof else None))
+        dof = _t_dof_root(q.value) if estimate_dof else self._dof
+        new = TPPCAModel(s_out.value, c_out, m_out, dof, ctx=self._ctx, _estimated_dof=self._estimated or estimate_dof)
+        return new, (llk.value if want_llk else None)
+
+    def iterate(self, dataset: Dataset, estimate_dof: bool = False) -> "TPPCAModel":
+        """One ECM iteration (transform, then mean, then noise, each given the ones before it; with estimate_dof then dof, the root
+        of ln(nu / 2) - psi(nu / 2) + 1 + q = 0 on [0.5, 1e4]): the t log-likelihood cannot decrease."""
+        return self._iterate(dataset, estimate_dof, False)[0]
+
+    def iterate_with_llk(self, dataset: Dataset, estimate_dof: bool = False):
+        """(next model, t log-likelihood of THIS model) from the same pass."""
+        return self._iterate(dataset, estimate_dof, True)
+
+    # -- serialisation (own npz container) ----------------------------------------------
+    def dump(self) -> bytes:
+        buf = io.BytesIO()
+        np.savez(buf, kind="ppca_rs_amd.TPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean,
+                 dof=self._dof, estimated_dof=self._estimated)
+        return buf.getvalue()
+
+    @staticmethod
+    def load(data: bytes) -> "TPPCAModel":
+        try:
+            z = np.load(io.BytesIO(data), allow_pickle=False)
+            if str(z["kind"]) != "ppca_rs_amd.TPPCAModel":
+                raise ValueError(f"not a TPPCAModel container: {z['kind']}")
+            return TPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"], float(z["dof"]),
+                              _estimated_dof=bool(z["estimated_dof"]))
+        except Exception as err:
+            raise Exception(str(err))
+
+    def __getstate__(self):
+        return self.dump()
+
+    def __setstate__(self, state):
+        o = TPPCAModel.load(state)
+        self.__dict__.update(o.__dict__)
+
+    def __getnewargs__(self):
+        return (self.isotropic_noise, self.transform, self.mean, self.dof)
+
+
+@dataclass
+class TPPCATrainer:
+    """EM driver of TPPCAModel: the loop and metrics of FATrainer."""
+
+    dataset: Dataset
+
+    def train(self, *, state_size: int, dof: float = 4.0, estimate_dof: bool = False, n_iters: int = 10,
+              start: Optional[TPPCAModel] = None, metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False,
+              seed: Optional[int] = None, init: str = "random") -> TPPCAModel:
+        """init: the method of PPCAModel.init ("random" or "pca"), used only when `start` is None.  estimate_dof: update the degrees
+        of freedom in every iteration (they start at `dof`, or at start.dof)."""
+        model = start or TPPCAModel.init(state_size, self.dataset, seed=seed, method=init, dof=dof)
+        n = len(self.dataset)
+        for idx in range(n_iters):
+            if not quiet:
+                # the llk of the current model is a by-product of the step: no second sweep
+                new_model, llk = model.iterate_with_llk(self.dataset, estimate_dof)
+                metrics = _metrics(llk, model.n_parameters + (1 if estimate_dof and not model._estimated else 0), n)
+                print(f"Masked t-PPCA iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
+                model = new_model
+            else:
+                model = model.iterate(self.dataset, estimate_dof)
+        return model.to_canonical()
+
+
 # --------------------------------------------------------------------------- mixture
 def _log_softmax(v: np.ndarray) -> np.ndarray:
     v = np.asarray(v, dtype=np.float64)

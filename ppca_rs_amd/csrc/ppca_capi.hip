@@ -2915,3 +2915,235 @@ extern "C" int ppca_famix_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, in
     }
     return PPCA_OK;
 }
+
+// ------------------------------------------------------------------ Student-t PPCA
+// psi(x) - ln(x) for x > 0: the asymptotic series from x >= 10 on (the logarithms cancel in the series, not in the arithmetic), below
+// that the upward recurrence psi(x) = psi(x + n) - sum_i 1 / (x + i).
+static double digamma_minus_log(double x) {
+    double shift = 0.0, y = x;
+    while (y < 10.0) {
+        shift += 1.0 / y;
+        y += 1.0;
+    }
+    const double r = 1.0 / y, r2 = r * r;
+    const double tail = -0.5 * r - r2 * (1.0 / 12.0 - r2 * (1.0 / 120.0 - r2 * (1.0 / 252.0 - r2 * (1.0 / 240.0 - r2 * (1.0 / 132.0)))));
+    return y == x ? tail : (std::log(y) + tail - shift) - std::log(x);
+}
+
+// ln Gamma(a + h) - ln Gamma(a) - h ln(2 pi a).  std::lgamma while a is moderate; from a >= 1e4 the difference of two values near
+// a ln a loses what the result needs, and Stirling's series (error below 1 / (1260 a^5)) is subtracted term by term instead.
+static double t_log_norm(double a, double h) {
+    if (h == 0.0) return 0.0;
+    if (a < 1e4) return std::lgamma(a + h) - std::lgamma(a) - h * std::log(2.0 * M_PI * a);
+    const double b = a + h;
+    const double corr = (1.0 / b - 1.0 / a) / 12.0 - (1.0 / (b * b * b) - 1.0 / (a * a * a)) / 360.0;
+    return (b - 0.5) * std::log1p(h / a) - h - h * std::log(2.0 * M_PI) + corr;
+}
+
+extern "C" int ppca_t_tables_host(int32_t d, double dof, double *lg_out, double *g_out) {
+    if (d < 0 || !lg_out || !g_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!(dof > 0.0) || !std::isfinite(dof)) return fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+    for (int m = 0; m <= d; ++m) {
+        lg_out[m] = t_log_norm(0.5 * dof, 0.5 * m);
+        g_out[m] = digamma_minus_log(0.5 * (dof + m));
+    }
+    return PPCA_OK;
+}
+
+static int t_check(const ppca_dataset *ds, const ppca_model *model, double dof) {
+    if (int rc = check_pair(ds, model)) return rc;
+    if (model->zero_state || !robust_covers(model->d, model->k))
+        return fail(PPCA_ERR_UNSUPPORTED, "the Student-t sweep covers state sizes 1 .. %d and output sizes 1 .. %d (got k=%d, d=%d)",
+                    ROBUST_MAX_K, ROBUST_MAX_D, model->k_user(), model->d);
+    if (!(dof > 0.0) || !std::isfinite(dof)) return fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+    return PPCA_OK;
+}
+
+// What a sweep keeps alive until the caller's synchronisation: the host side of its asynchronous copies and its device scratch.
+struct TSweep {
+    std::vector<double> tabs, res;  // [lg | g] as uploaded; the reduced [column sums | 4 scalars] as downloaded
+    BufRef tabs_dev, llks, states, part;
+    int64_t plen = 0;
+};
+
+// Enqueues the sweep over the whole dataset by row chunks (the posterior pass into scratch, then the streaming kernel) and the copy of
+// the reduced sums into sw.res; no synchronisation.  Y (nullable): n x d on the device; u, maha, ell (nullable): n doubles each on the
+// device.  The chunks bound the scratch at 1 GiB as ppca_loo_predictive's do; the per-row outputs do not depend on them.
+static int t_sweep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, double dof, double *Y, bool sums, double *u, double *maha,
+                   double *ell, TSweep &sw) {
+    const int64_t n = ds->n;
+    const int d = ds->d, k = model->k;
+    const bool so = sums || Y != nullptr;
+    sw.plen = robust_plen(d, k, so);
+    sw.res.assign((size_t)sw.plen, 0.0);
+    if (n <= 0) return PPCA_OK;
+    sw.tabs.resize((size_t)2 * (d + 1));
+    if (int rc = ppca_t_tables_host(d, dof, sw.tabs.data(), sw.tabs.data() + d + 1)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * sw.tabs.size(), &sw.tabs_dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(sw.tabs_dev->p, sw.tabs.data(), sizeof(double) * sw.tabs.size(), hipMemcpyHostToDevice, ctx->stream));
+    const int64_t chunk = std::max<int64_t>(1024, std::min<int64_t>(n, ((int64_t)1 << 30) / ((int64_t)sizeof(double) * (k + 1))));
+    const size_t rows = (size_t)std::min(chunk, n);
+    const int grid_max = robust_grid((int64_t)rows, d, k, ctx->n_cu);
+    if (int rc = dev_alloc(sizeof(double) * rows, &sw.llks)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * rows * k, &sw.states)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * ((size_t)grid_max + 1) * (size_t)sw.plen, &sw.part)) return rc;
+    double *llks = static_cast<double *>(sw.llks->p), *states = static_cast<double *>(sw.states->p);
+    double *part = static_cast<double *>(sw.part->p), *red = part + (size_t)grid_max * sw.plen;
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        ppca_dataset sl = loo_slice(ds, r0, chunk);
+        if (int rc = run_post(ctx, &sl, model, llks, states, nullptr, nullptr, 0, nullptr)) return rc;
+        const int grid = robust_grid(sl.n, d, k, ctx->n_cu);
+        HIP_TRY(launch_robust_sweep(sl.X, sl.d, sl.w, sl.n, d, k, model->p(), llks, states, static_cast<const double *>(sw.tabs_dev->p), dof,
+                                    Y ? Y + r0 * d : nullptr, so, u ? u + r0 : nullptr, maha ? maha + r0 : nullptr, ell ? ell + r0 : nullptr,
+                                    part, grid, ctx->stream));
+        HIP_TRY(launch_reduce_partials(part, grid, sw.plen, red, ctx->stream, r0 > 0 ? 1 : 0));
+    }
+    HIP_TRY(hipMemcpyAsync(sw.res.data(), red, sizeof(double) * sw.res.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return PPCA_OK;
+}
+
+// Waits for the stream on every way out of a scope whose host buffers asynchronous copies still read or write.
+struct TStreamGuard {
+    hipStream_t s;
+    bool armed = true;
+    ~TStreamGuard() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+
+extern "C" int ppca_t_estep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, double dof, ppca_dataset **scaled_out,
+                            double *col_sums_host, double *u, double *maha, double *llks, double *scalars_host) {
+    if (!ctx) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!scaled_out && !col_sums_host && !u && !maha && !llks && !scalars_host) return fail(PPCA_ERR_INVALID, "no output requested");
+    if (int rc = t_check(ds, model, dof)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int d = ds->d, k = model->k;
+    std::unique_ptr<ppca_dataset> nd;
+    if (scaled_out)
+        if (int rc = posterior_out(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
+    BufRef ub, mb, lb;
+    const size_t nb = sizeof(double) * (size_t)std::max<int64_t>(n, 1);
+    if (u)
+        if (int rc = dev_alloc(nb, &ub)) return rc;
+    if (maha)
+        if (int rc = dev_alloc(nb, &mb)) return rc;
+    if (llks)
+        if (int rc = dev_alloc(nb, &lb)) return rc;
+    TSweep sw;
+    TStreamGuard guard{ctx->stream};
+    if (int rc = t_sweep(ctx, ds, model, dof, nd ? static_cast<double *>(nd->xbuf->p) : nullptr, col_sums_host != nullptr,
+                         ub ? static_cast<double *>(ub->p) : nullptr, mb ? static_cast<double *>(mb->p) : nullptr,
+                         lb ? static_cast<double *>(lb->p) : nullptr, sw))
+        return rc;
+    if (n > 0) {  // (host or device destinations, as ppca_llk's per-sample output)
+        if (u) HIP_TRY(hipMemcpyAsync(u, ub->p, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        if (maha) HIP_TRY(hipMemcpyAsync(maha, mb->p, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        if (llks) HIP_TRY(hipMemcpyAsync(llks, lb->p, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+    }
+    guard.armed = false;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (col_sums_host) std::memcpy(col_sums_host, sw.res.data(), sizeof(double) * (size_t)(k + 3) * d);
+    if (scalars_host) std::memcpy(scalars_host, sw.res.data() + sw.plen - 4, sizeof(double) * 4);
+    if (scaled_out) *scaled_out = nd.release();
+    return PPCA_OK;
+}
+
+extern "C" int ppca_t_finalize_host(int32_t d, int32_t k, double sigma, const double *transform, const double *mean, const double *stats,
+                                    const double *col_sums, double *sigma_out, double *transform_out, double *mean_out) {
+    if (d < 1 || k < 1 || !transform || !mean || !stats || !col_sums || !sigma_out || !transform_out || !mean_out)
+        return fail(PPCA_ERR_INVALID, "null argument");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(PPCA_ERR_INVALID, "sigma is not a positive finite number");
+    const StatsLayout L(d, k);
+    const double *V = col_sums, *A = col_sums + (int64_t)d * k, *T = A + d, *sq = T + d;
+    std::vector<double> S((size_t)L.kp), a((size_t)k);
+    double num = 0.0, den = 0.0;
+    for (int j = 0; j < d; ++j) {
+        const double *Sj = stats + L.S + (int64_t)j * L.kp, *cr = stats + L.cross + (int64_t)j * k, *Vj = V + (int64_t)j * k;
+        // 1. the row: S_j a = cross_j; a pivot <= 0 keeps the old row
+        for (int e = 0; e < L.kp; ++e) S[e] = Sj[e];
+        for (int b = 0; b < k; ++b) a[b] = cr[b];
+        if (chol_packed(S.data(), k))
+            chol_solve_packed(S.data(), k, a.data());
+        else
+            for (int b = 0; b < k; ++b) a[b] = transform[(int64_t)j * k + b];
+        // 2. the mean moves by delta, with the NEW row
+        double av = 0.0, ac = 0.0, asa = 0.0;
+        for (int b = 0; b < k; ++b) {
+            av += a[b] * Vj[b];
+            ac += a[b] * cr[b];
+            double row = 0.0;
+            for (int c = 0; c < k; ++c) row += Sj[c <= b ? tri(b, c) : tri(c, b)] * a[c];
+            asa += a[b] * row;
+        }
+        const double delta = T[j] > 0.0 ? (A[j] - av) / T[j] : 0.0;
+        // 3. the pooled noise, full form (the row may have been kept)
+        num += sq[j] - 2.0 * ac + asa - delta * delta * T[j];
+        den += stats[L.totals + j];
+        for (int b = 0; b < k; ++b) transform_out[(int64_t)j * k + b] = a[b];
+        mean_out[j] = mean[j] + delta;
+    }
+    const double v = num / den;
+    *sigma_out = (std::isfinite(v) && v > 0.0) ? std::sqrt(v) : sigma;
+    return PPCA_OK;
+}
+
+extern "C" int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, double sigma, const double *transform,
+                              const double *mean, double dof, double *sigma_out, double *transform_out, double *mean_out, double *llk_in,
+                              double *q_out) {
+    if (!ctx || !ds || !transform || !mean || !sigma_out || !transform_out || !mean_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (d < 1 || k < 0) return fail(PPCA_ERR_INVALID, "invalid shape d=%d k=%d", d, k);
+    if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
+    if (!robust_covers(d, k))
+        return fail(PPCA_ERR_UNSUPPORTED, "the Student-t sweep covers state sizes 1 .. %d and output sizes 1 .. %d (got k=%d, d=%d)",
+                    ROBUST_MAX_K, ROBUST_MAX_D, k, d);
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(PPCA_ERR_INVALID, "sigma is not a positive finite number");
+    if (!(dof > 0.0) || !std::isfinite(dof)) return fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+    if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
+    USE_CTX(ctx);
+    struct Held {  // released on every return path; the scaled copy goes back to the context's block cache
+        ppca_dataset *y = nullptr;
+        ppca_model *m = nullptr, *m0 = nullptr;
+        ~Held() {
+            ppca_dataset_free(y);
+            ppca_model_free(m);
+            ppca_model_free(m0);
+        }
+    } held;
+    // the model (sigma, C, mean) of the sweep and (sigma, C, 0) of the EM pass on the centred, scaled rows: uploaded without a wait
+    // (hm, hm0 are read until the synchronisation below)
+    if (int rc = ppca_model_alloc(ctx, d, k, &held.m)) return rc;
+    if (int rc = ppca_model_alloc(ctx, d, k, &held.m0)) return rc;
+    std::vector<double> hm((size_t)model_len(d, k), 0.0), hm0;
+    hm[0] = sigma;
+    hm[1] = sigma * sigma;
+    hm[2] = std::log(sigma);
+    std::memcpy(hm.data() + MODEL_HDR, transform, sizeof(double) * (size_t)d * k);
+    hm0 = hm;
+    std::memcpy(hm.data() + MODEL_HDR + (size_t)d * k, mean, sizeof(double) * d);
+    TSweep sw;
+    TStreamGuard guard{ctx->stream};
+    touch(held.m);
+    touch(held.m0);
+    HIP_TRY(hipMemcpyAsync(held.m->p(), hm.data(), sizeof(double) * hm.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(held.m0->p(), hm0.data(), sizeof(double) * hm0.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = check_pair(ds, held.m)) return rc;
+    std::unique_ptr<ppca_dataset> nd;
+    if (int rc = posterior_out(ctx, ds, true, nd)) return rc;
+    held.y = nd.release();
+    if (int rc = t_sweep(ctx, ds, held.m, dof, static_cast<double *>(held.y->xbuf->p), true, nullptr, nullptr, nullptr, sw)) return rc;
+    const StatsLayout L(d, k);
+    if (int rc = ensure(ctx->stats, ctx->stats_cap, sizeof(double) * (size_t)L.len)) return rc;
+    double *stats = static_cast<double *>(ctx->stats->p);
+    ctx->stats_llk_at = -1;  // (the llk in the buffer is the scaled rows' Gaussian one: ppca_em_last_llk does not apply)
+    if (int rc = ppca_em_accumulate(ctx, held.y, held.m0, stats)) return rc;
+    std::vector<double> h((size_t)L.len);
+    HIP_TRY(hipMemcpyAsync(h.data(), stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    guard.armed = false;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (int rc = ppca_t_finalize_host(d, k, sigma, transform, mean, h.data(), sw.res.data(), sigma_out, transform_out, mean_out)) return rc;
+    const double *sc = sw.res.data() + sw.plen - 4;
+    if (llk_in) *llk_in = sc[1];
+    if (q_out) *q_out = sc[0] > 0.0 ? sc[2] / sc[0] : 0.0;
+    return PPCA_OK;
+}

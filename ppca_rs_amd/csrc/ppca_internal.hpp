@@ -322,6 +322,21 @@ int64_t wd_blocks(int64_t n);
 int64_t wd_block_rows();
 hipError_t launch_wd_block_sums(const double *w, const double *dist, int64_t n, double *out, hipStream_t s);
 
+// the Student-t sweep (ppca_robust.hip) over the n rows of a chunk whose posterior means (states, n x k) and
+// Gaussian log-densities (llks, n) a posterior pass wrote: u, maha, ell (nullable, n) = the rows' weights, Mahalanobis distances and
+// t log-densities; Y (nullable, n x d) = sqrt(u) (x - mean), NaN on masked entries; part[grid][plen], plen = robust_plen(d, k, sums
+// || Y): the workgroups' column sums V (d x k) | A | T | sq (only with sums || Y) and the four scalars sum w | sum w ell |
+// sum w (g[m] + ln u - u) | non-empty rows (reduce with launch_reduce_partials).  tabs = [lg (d + 1) | g (d + 1)] on the device
+// (ppca_t_tables_host).  grid = robust_grid(n, d, k, n_cu).  Covers 1 <= k <= ROBUST_MAX_K, 1 <= d <= ROBUST_MAX_D.
+constexpr int ROBUST_MAX_K = 16;    // k + 3 sums per column and the thread's rows of C live in registers
+constexpr int ROBUST_MAX_D = 1024;  // four columns per thread of a 256-thread row
+bool robust_covers(int d, int k);
+int64_t robust_plen(int d, int k, bool sums);
+int robust_grid(int64_t n, int d, int k, int n_cu);
+hipError_t launch_robust_sweep(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k, const double *model,
+                               const double *llks, const double *states, const double *tabs, double nu, double *Y, bool sums, double *u,
+                               double *maha, double *ell, double *part, int grid, hipStream_t s);
+
 // pairwise second moments (ppca_moments.hip): sums = X~^T diag(w) X~, counts = M^T diag(w) M and (cross
 // nullable) cross = X~^T diag(w) M, d x d row-major each, x~ = x - center on observed entries.  A job = (pair of 64-column tiles,
 // I <= J) x (run of rows); its partials go to part (p.scratch_bytes) and a second kernel adds the runs in order and mirrors the

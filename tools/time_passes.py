@@ -13,7 +13,9 @@ MFMA rate (profiles/r04/mfma_peak.txt), counting n d (d + 1) flop per symmetric 
 k-means and the k-means start, in one process: the fused Lloyd step, the labelling-only call, the two-sweep composition
 the fused step replaces (a labelling call, then ppca_dataset_column_moments_multi with one-hot weights), the sums-only scale pass (one
 read of X: the floor), the whole `Dataset.kmeans` (seeding plus iterations), the K moment passes of `from_kmeans`, and one
-ppca_mix_em_step at K components."""
+ppca_mix_em_step at K components.  `--robust` runs ONLY the legs of Student-t PPCA, in one process: the sweep with and
+without the scaled rows, a whole TPPCAModel.iterate, and the passes they are compared with (PPCAModel.llks, the column-scale pass,
+PPCAModel.iterate)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -98,6 +100,47 @@ def fa_legs(reps=12):
 
 if "--fa" in sys.argv:
     fa_legs()
+    sys.exit(0)
+
+def robust_legs(reps=10):
+    """The Student-t sweep with and without the scaled rows, a whole TPPCAModel.iterate, and in the same process the
+    passes whose traffic the sweep adds up to (two reads and one write of N x d): PPCAModel.llks, the column-scale pass with output and
+    sums, and PPCAModel.iterate.  Every repetition timed on its own (median, min, max)."""
+    def series(fn):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:8.3f} ms  min {ts.min():8.3f}  max {ts.max():8.3f}  ({reps} repetitions)", flush=True)
+        return med
+
+    t = P.TPPCAModel.from_ppca(m, 4.0)
+    a, b = np.ones(d), m.mean
+    legs = [("PPCAModel.llks (posterior pass, llks to the host)", lambda: m.llks(ds)),
+            ("scale pass with output and column sums", lambda: ds._scale_columns(a, b, out=True, col_sums=True)),
+            ("t sweep without the scaled rows (llks to the host)", lambda: t.llks(ds)),
+            ("t sweep with the scaled rows and column sums", lambda: t._estep(ds, scaled=True, col_sums=True, scalars=True)),
+            ("PPCAModel.iterate", lambda: m.iterate(ds)),
+            ("TPPCAModel.iterate", lambda: t.iterate(ds))]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn))
+    reps *= 2
+    med = [report(name, np.concatenate(got[name])) for name, _ in legs]
+    print(f"  sweep without Y / llks = {med[2] / med[0]:.3f}   (the sweep alone: {med[2] - med[0]:.3f} ms)")
+    print(f"  sweep with Y / (llks + scale) = {med[3] / (med[0] + med[1]):.3f}   (the sweep alone: {med[3] - med[0]:.3f} ms; scale pass {med[1]:.3f} ms)")
+    print(f"  t iterate / Gaussian iterate = {med[5] / med[4]:.3f}   (t - Gaussian = {med[5] - med[4]:.3f} ms)")
+
+if "--robust" in sys.argv:
+    robust_legs()
     sys.exit(0)
 
 def famix_legs(nm, reps=12):
