@@ -1034,6 +1034,22 @@ def _metrics(llk: float, n_parameters: int, n: int) -> TrainMetrics:
     return TrainMetrics(llk=llk / n, aic=2.0 * (n_parameters - llk) / n, bic=(llk - n_parameters * np.log(n)) / n)
 
 
+def _train_loop(model, n_iters: int, quiet: bool, metric: str, label: str, n: int, step_with_llk, step, n_parameters=None):
+    """The loop of every trainer (python/ppca_rs/__init__.py:45-66).  step_with_llk(model) -> (next model, llk of `model`);
+    step(model) -> next model, the quiet form, which reads no llk back; n_parameters(model): the count behind aic / bic where it is
+    not model.n_parameters."""
+    for idx in range(n_iters):
+        if quiet:
+            model = step(model)
+            continue
+        # the llk of the current model is a by-product of the EM pass: no second sweep
+        new_model, llk = step_with_llk(model)
+        metrics = _metrics(llk, n_parameters(model) if n_parameters else model.n_parameters, n)
+        print(f"Masked {label} iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
+        model = new_model
+    return model.to_canonical()
+
+
 @dataclass
 class PPCATrainer:
     """EM driver (python/ppca_rs/__init__.py:21-67)."""
@@ -1044,18 +1060,29 @@ class PPCATrainer:
               n_iters: int = 10, metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False,
               seed: Optional[int] = None, init: str = "random") -> PPCAModel:
         """init: the method of PPCAModel.init ("random" or "pca"), used only when `start` is None."""
-        model = start or PPCAModel.init(state_size, self.dataset, seed=seed, method=init)
-        n = len(self.dataset)
-        for idx in range(n_iters):
-            if not quiet:
-                # the llk of the current model is a by-product of the EM pass: no second sweep
-                new_model, llk = model.iterate_with_llk(self.dataset, prior)
-                metrics = _metrics(llk, model.n_parameters, n)
-                print(f"Masked PPCA iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
-                model = new_model
-            else:
-                model = model.iterate_with_prior(self.dataset, prior) if prior is not None else model.iterate(self.dataset)
-        return model.to_canonical()
+        ds = self.dataset
+        model = start or PPCAModel.init(state_size, ds, seed=seed, method=init)
+        return _train_loop(model, n_iters, quiet, metric, "PPCA", len(ds), lambda m: m.iterate_with_llk(ds, prior),
+                           lambda m: m.iterate_with_prior(ds, prior) if prior is not None else m.iterate(ds))
+
+
+# --------------------------------------------------------------------------- own npz containers (FAModel, TPPCAModel, FAMix)
+def _npz_dump(kind: str, **arrays) -> bytes:
+    buf = io.BytesIO()
+    np.savez(buf, kind=kind, **arrays)
+    return buf.getvalue()
+
+
+def _npz_load(data: bytes, kind: str, label: str, build):
+    """build(the container's arrays) once its `kind` is the expected one; label: the class with its article, as the mismatch message
+    names it.  Whatever fails on the way is raised as a plain Exception with that failure's text."""
+    try:
+        z = np.load(io.BytesIO(data), allow_pickle=False)
+        if str(z["kind"]) != kind:
+            raise ValueError(f"not {label} container: {z['kind']}")
+        return build(z)
+    except Exception as err:
+        raise Exception(str(err))
 
 
 # --------------------------------------------------------------------------- factor analysis (per-column noise)
@@ -1226,26 +1253,17 @@ class FAModel:
 
     # -- serialisation (own npz container) ----------------------------------------------
     def dump(self) -> bytes:
-        buf = io.BytesIO()
-        np.savez(buf, kind="ppca_rs_amd.FAModel", noise=self._noise, transform=self._c, mean=self._mean)
-        return buf.getvalue()
+        return _npz_dump("ppca_rs_amd.FAModel", noise=self._noise, transform=self._c, mean=self._mean)
 
     @staticmethod
     def load(data: bytes) -> "FAModel":
-        try:
-            z = np.load(io.BytesIO(data), allow_pickle=False)
-            if str(z["kind"]) != "ppca_rs_amd.FAModel":
-                raise ValueError(f"not an FAModel container: {z['kind']}")
-            return FAModel(z["noise"], z["transform"], z["mean"])
-        except Exception as err:
-            raise Exception(str(err))
+        return _npz_load(data, "ppca_rs_amd.FAModel", "an FAModel", lambda z: FAModel(z["noise"], z["transform"], z["mean"]))
 
     def __getstate__(self):
         return self.dump()
 
     def __setstate__(self, state):
-        o = FAModel.load(state)
-        self.__dict__.update(o.__dict__)
+        self.__dict__.update(FAModel.load(state).__dict__)
 
     def __getnewargs__(self):
         return (self.noise, self.transform, self.mean)
@@ -1264,19 +1282,11 @@ class FATrainer:
         min_noise_ratio: the new noise of column j is kept at or above ratio x the column's observed standard deviation -- a guard
         against a noise level collapsing to 0 (a Heywood case), not a tuned number: at 1e-3 it bounds the share of a column's
         variance the latent state may explain at 1 - 1e-6."""
-        model = start or FAModel.init(state_size, self.dataset, seed=seed, method=init)
-        n = len(self.dataset)
-        floor = min_noise_ratio * np.sqrt(self.dataset.column_stats()[2])
-        for idx in range(n_iters):
-            if not quiet:
-                # the llk of the current model is a by-product of the EM pass: no second sweep
-                new_model, llk = model.iterate_with_llk(self.dataset, floor)
-                metrics = _metrics(llk, model.n_parameters, n)
-                print(f"Masked FA iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
-                model = new_model
-            else:
-                model = model.iterate(self.dataset, floor)
-        return model.to_canonical()
+        ds = self.dataset
+        model = start or FAModel.init(state_size, ds, seed=seed, method=init)
+        floor = min_noise_ratio * np.sqrt(ds.column_stats()[2])
+        return _train_loop(model, n_iters, quiet, metric, "FA", len(ds), lambda m: m.iterate_with_llk(ds, floor),
+                           lambda m: m.iterate(ds, floor))
 
 
 # --------------------------------------------------------------------------- Student-t PPCA (robust to outlying rows)
@@ -1475,28 +1485,20 @@ class TPPCAModel:
 
     # -- serialisation (own npz container) ----------------------------------------------
     def dump(self) -> bytes:
-        buf = io.BytesIO()
-        np.savez(buf, kind="ppca_rs_amd.TPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean,
-                 dof=self._dof, estimated_dof=self._estimated)
-        return buf.getvalue()
+        return _npz_dump("ppca_rs_amd.TPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean,
+                         dof=self._dof, estimated_dof=self._estimated)
 
     @staticmethod
     def load(data: bytes) -> "TPPCAModel":
-        try:
-            z = np.load(io.BytesIO(data), allow_pickle=False)
-            if str(z["kind"]) != "ppca_rs_amd.TPPCAModel":
-                raise ValueError(f"not a TPPCAModel container: {z['kind']}")
-            return TPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"], float(z["dof"]),
-                              _estimated_dof=bool(z["estimated_dof"]))
-        except Exception as err:
-            raise Exception(str(err))
+        return _npz_load(data, "ppca_rs_amd.TPPCAModel", "a TPPCAModel",
+                         lambda z: TPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"], float(z["dof"]),
+                                              _estimated_dof=bool(z["estimated_dof"])))
 
     def __getstate__(self):
         return self.dump()
 
     def __setstate__(self, state):
-        o = TPPCAModel.load(state)
-        self.__dict__.update(o.__dict__)
+        self.__dict__.update(TPPCAModel.load(state).__dict__)
 
     def __getnewargs__(self):
         return (self.isotropic_noise, self.transform, self.mean, self.dof)
@@ -1513,18 +1515,12 @@ class TPPCATrainer:
               seed: Optional[int] = None, init: str = "random") -> TPPCAModel:
         """init: the method of PPCAModel.init ("random" or "pca"), used only when `start` is None.  estimate_dof: update the degrees
         of freedom in every iteration (they start at `dof`, or at start.dof)."""
-        model = start or TPPCAModel.init(state_size, self.dataset, seed=seed, method=init, dof=dof)
-        n = len(self.dataset)
-        for idx in range(n_iters):
-            if not quiet:
-                # the llk of the current model is a by-product of the step: no second sweep
-                new_model, llk = model.iterate_with_llk(self.dataset, estimate_dof)
-                metrics = _metrics(llk, model.n_parameters + (1 if estimate_dof and not model._estimated else 0), n)
-                print(f"Masked t-PPCA iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
-                model = new_model
-            else:
-                model = model.iterate(self.dataset, estimate_dof)
-        return model.to_canonical()
+        ds = self.dataset
+        model = start or TPPCAModel.init(state_size, ds, seed=seed, method=init, dof=dof)
+        return _train_loop(model, n_iters, quiet, metric, "t-PPCA", len(ds), lambda m: m.iterate_with_llk(ds, estimate_dof),
+                           lambda m: m.iterate(ds, estimate_dof),
+                           # (a dof about to be estimated for the first time counts as a parameter already)
+                           n_parameters=lambda m: m.n_parameters + (1 if estimate_dof and not m._estimated else 0))
 
 
 # --------------------------------------------------------------------------- mixture
@@ -1888,17 +1884,10 @@ class PPCAMixTrainer:
               state_size: int, n_iters: int = 10, metric: Literal["aic", "bic", "llk"] = "aic", quiet: bool = False,
               seed: Optional[int] = None, init: str = "random") -> PPCAMix:
         """init: the `method` of `PPCAMix.init` when no `start` is given."""
-        model = start or PPCAMix.init(n_models, state_size, self.dataset, seed=seed, method=init)
-        n = len(self.dataset)
-        for idx in range(n_iters):
-            if not quiet:
-                new_model, llk = model.iterate_with_llk(self.dataset, prior)
-                metrics = _metrics(llk, model.n_parameters, n)
-                print(f"Masked PPCA mix iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
-                model = new_model
-            else:
-                model = model.iterate_with_prior(self.dataset, prior) if prior is not None else model.iterate(self.dataset)
-        return model.to_canonical()
+        ds = self.dataset
+        model = start or PPCAMix.init(n_models, state_size, ds, seed=seed, method=init)
+        return _train_loop(model, n_iters, quiet, metric, "PPCA mix", len(ds), lambda m: m.iterate_with_llk(ds, prior),
+                           lambda m: m.iterate_with_prior(ds, prior) if prior is not None else m.iterate(ds))
 
 
 # --------------------------------------------------------------------------- mixture of factor analysers (shared column noise)
@@ -2099,26 +2088,18 @@ class FAMix:
 
     # -- serialisation (own npz container) ----------------------------------------------
     def dump(self) -> bytes:
-        buf = io.BytesIO()
-        np.savez(buf, kind="ppca_rs_amd.FAMix", noise=self._noise, transforms=self._c, means=self._mean, log_weights=self._lw)
-        return buf.getvalue()
+        return _npz_dump("ppca_rs_amd.FAMix", noise=self._noise, transforms=self._c, means=self._mean, log_weights=self._lw)
 
     @staticmethod
     def load(data: bytes) -> "FAMix":
-        try:
-            z = np.load(io.BytesIO(data), allow_pickle=False)
-            if str(z["kind"]) != "ppca_rs_amd.FAMix":
-                raise ValueError(f"not an FAMix container: {z['kind']}")
-            return FAMix(z["noise"], z["transforms"], z["means"], z["log_weights"])
-        except Exception as err:
-            raise Exception(str(err))
+        return _npz_load(data, "ppca_rs_amd.FAMix", "an FAMix",
+                         lambda z: FAMix(z["noise"], z["transforms"], z["means"], z["log_weights"]))
 
     def __getstate__(self):
         return self.dump()
 
     def __setstate__(self, state):
-        o = FAMix.load(state)
-        self.__dict__.update(o.__dict__)
+        self.__dict__.update(FAMix.load(state).__dict__)
 
     def __getnewargs__(self):
         return (self.noise, self.transforms, self.means, self.log_weights)
@@ -2135,16 +2116,8 @@ class FAMixTrainer:
               min_noise_ratio: float = 1e-3, init: str = "random") -> FAMix:
         """min_noise_ratio: FATrainer's floor, ratio x the column's observed standard deviation.  init: the `method` of `FAMix.init`
         when no `start` is given."""
-        model = start or FAMix.init(n_models, state_size, self.dataset, seed=seed, method=init)
-        n = len(self.dataset)
-        floor = min_noise_ratio * np.sqrt(self.dataset.column_stats()[2])
-        for idx in range(n_iters):
-            if not quiet:
-                # the llk of the current model is a by-product of the EM pass: no second sweep
-                new_model, llk = model.iterate_with_llk(self.dataset, floor)
-                metrics = _metrics(llk, model.n_parameters, n)
-                print(f"Masked FA mix iteration {idx + 1}: {metric}={getattr(metrics, metric)}")
-                model = new_model
-            else:
-                model = model.iterate(self.dataset, floor)
-        return model.to_canonical()
+        ds = self.dataset
+        model = start or FAMix.init(n_models, state_size, ds, seed=seed, method=init)
+        floor = min_noise_ratio * np.sqrt(ds.column_stats()[2])
+        return _train_loop(model, n_iters, quiet, metric, "FA mix", len(ds), lambda m: m.iterate_with_llk(ds, floor),
+                           lambda m: m.iterate(ds, floor))

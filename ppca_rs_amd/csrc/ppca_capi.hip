@@ -182,6 +182,115 @@ int ppca_host::ensure_hstage(ppca_ctx *ctx, size_t bytes) {
     return PPCA_OK;
 }
 
+// ------------------------------------------------------------------ helpers shared by the entry points
+// Handles an entry point owns until it returns: released on every return path.
+struct DatasetFree {
+    void operator()(ppca_dataset *p) const { ppca_dataset_free(p); }
+};
+struct ModelFree {
+    void operator()(ppca_model *p) const { ppca_model_free(p); }
+};
+typedef std::unique_ptr<ppca_dataset, DatasetFree> DatasetPtr;
+typedef std::unique_ptr<ppca_model, ModelFree> ModelPtr;
+
+// Waits for the stream on every way out of a scope whose host buffers asynchronous copies still read or write.
+struct StreamGuard {
+    hipStream_t s;
+    bool armed = true;
+    ~StreamGuard() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+
+// An output dataset shaped like ds on ctx: n x d doubles from the pool (one row's worth when n = 0), with the input's weights when
+// carry_weights (ppca_model.rs:242, :259; the mixture outputs collect fresh samples, mix.rs:245-265, and carry none).
+static int dataset_like(ppca_ctx *ctx, const ppca_dataset *ds, bool carry_weights, DatasetPtr &nd) {
+    nd.reset(new ppca_dataset());
+    nd->ctx = ctx;
+    nd->n = ds->n;
+    nd->d = ds->d;
+    if (carry_weights) {
+        nd->wbuf = ds->wbuf;
+        nd->w = ds->w;
+    }
+    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(ds->n, 1) * ds->d, &nd->xbuf)) return rc;
+    nd->X = static_cast<const double *>(nd->xbuf->p);
+    return PPCA_OK;
+}
+
+// Rows r0 .. r0 + rows of ds (cut at its end) as a dataset of their own, weights included; owns nothing.
+static ppca_dataset row_slice(const ppca_dataset *ds, int64_t r0, int64_t rows) {
+    ppca_dataset part(*ds);
+    part.n = std::min(rows, ds->n - r0);
+    part.X = ds->X + r0 * ds->d;
+    part.w = ds->w ? ds->w + r0 : nullptr;
+    return part;
+}
+
+// Rows a pass that keeps bytes_per_row of scratch per row takes at once: what fits 1 GiB, at least 1024 (N x k x k doubles would
+// not fit at N = 10 M, k = 64).  The per-row outputs of the chunked passes depend on the row alone, not on the chunk.
+static int64_t chunk_rows(int64_t n, int64_t bytes_per_row) {
+    return std::max<int64_t>(1024, std::min<int64_t>(std::max<int64_t>(n, 1), ((int64_t)1 << 30) / bytes_per_row));
+}
+
+// Per-workgroup partial sums p[grid][len] and, behind them, red[len]: their sum in the fixed order of launch_reduce_partials.
+struct Partials {
+    BufRef buf;
+    double *p = nullptr, *red = nullptr;
+    int grid = 0;
+    int64_t len = 0;
+    int alloc(int grid_, int64_t len_) {
+        if (int rc = dev_alloc(sizeof(double) * ((size_t)grid_ + 1) * (size_t)len_, &buf)) return rc;
+        grid = grid_;
+        len = len_;
+        p = static_cast<double *>(buf->p);
+        red = p + (size_t)grid * len;
+        return PPCA_OK;
+    }
+    // used: the workgroups of the launch that wrote p, when fewer than were allocated for
+    hipError_t reduce(hipStream_t s, int accumulate = 0, int used = -1) const {
+        return launch_reduce_partials(p, used < 0 ? grid : used, len, red, s, accumulate);
+    }
+};
+
+// The device image of a model, [sigma, sigma^2, ln sigma, 0 | C (d x ki; the caller's k <= ki columns, the rest 0) | mean].
+static std::vector<double> model_image(double sigma, const double *C, const double *mean, int d, int k, int ki) {
+    std::vector<double> h((size_t)model_len(d, ki), 0.0);
+    h[0] = sigma;
+    h[1] = sigma * sigma;  // isotropic_noise.powi(2), output_covariance.rs:62
+    h[2] = std::log(sigma);
+    for (int j = 0; j < d; ++j)
+        for (int b = 0; b < k; ++b) h[MODEL_HDR + (size_t)j * ki + b] = C[(size_t)j * k + b];
+    std::memcpy(h.data() + MODEL_HDR + (size_t)d * ki, mean, sizeof(double) * d);
+    return h;
+}
+// Enqueues the upload of an image into m, without a wait: h is read until the stream's next synchronisation.
+static hipError_t model_upload(ppca_ctx *ctx, ppca_model *m, const std::vector<double> &h) {
+    touch(m);
+    return hipMemcpyAsync(m->p(), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, ctx->stream);
+}
+
+// Argument checks that several entry points share: each records its message and returns its code.
+static int check_noise(const double *noise, int d) {
+    for (int j = 0; j < d; ++j)
+        if (!(noise[j] > 0.0) || !std::isfinite(noise[j])) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+    return PPCA_OK;
+}
+static int check_sigma(double sigma) {
+    return sigma > 0.0 && std::isfinite(sigma) ? PPCA_OK : fail(PPCA_ERR_INVALID, "sigma is not a positive finite number");
+}
+static int check_dof(double dof) {
+    return dof > 0.0 && std::isfinite(dof) ? PPCA_OK : fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+}
+static int check_same_device(const ppca_dataset *ds, const ppca_ctx *ctx) {
+    return ds->ctx->device == ctx->device ? PPCA_OK : fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+}
+static int check_t_covers(int d, int k) {  // k: the caller's state size (0 is not covered)
+    if (robust_covers(d, k)) return PPCA_OK;
+    return fail(PPCA_ERR_UNSUPPORTED, "the Student-t sweep covers state sizes 1 .. %d and output sizes 1 .. %d (got k=%d, d=%d)",
+                ROBUST_MAX_K, ROBUST_MAX_D, k, d);
+}
+
 // ------------------------------------------------------------------ device -> host, pipelined
 // A pageable hipMemcpy of a large block comes back at ~12-25 GB/s (one staging thread, first-touch page faults of the
 // destination on that same thread).  Here the block leaves in 64 MB chunks: [canonicalising copy on the device ->]
@@ -703,16 +812,8 @@ extern "C" int ppca_model_create(ppca_ctx *ctx, int32_t d, int32_t k, double sig
     if (!mean || (k > 0 && !transform)) return fail(PPCA_ERR_INVALID, "null model arrays");
     ppca_model *m = nullptr;
     if (int rc = ppca_model_alloc(ctx, d, k, &m)) return rc;
-    const int ki = m->k;  // (k = 0: one zero column)
-    std::vector<double> h((size_t)model_len(d, ki), 0.0);
-    h[0] = sigma;
-    h[1] = sigma * sigma;  // isotropic_noise.powi(2), output_covariance.rs:62
-    h[2] = std::log(sigma);
-    h[3] = 0.0;
-    if (k > 0) std::memcpy(h.data() + MODEL_HDR, transform, sizeof(double) * (size_t)d * k);
-    std::memcpy(h.data() + MODEL_HDR + (size_t)d * ki, mean, sizeof(double) * d);
-    touch(m);
-    hipError_t e = hipMemcpyAsync(m->p(), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, ctx->stream);
+    const std::vector<double> h = model_image(sigma, transform, mean, d, k, m->k);  // (k = 0: one zero column)
+    hipError_t e = model_upload(ctx, m, h);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         delete m;
@@ -1262,14 +1363,8 @@ static int recon_common(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model
     if (!ctx || !out) return fail(PPCA_ERR_INVALID, "null argument");
     if (int rc = check_pair(ds, model)) return rc;
     USE_CTX(ctx);
-    auto nd = std::make_unique<ppca_dataset>();
-    nd->ctx = ctx;
-    nd->n = ds->n;
-    nd->d = ds->d;
-    nd->wbuf = ds->wbuf;  // weights carried over (ppca_model.rs:242, :259)
-    nd->w = ds->w;
-    if (int rc = dev_alloc(sizeof(double) * (size_t)ds->n * ds->d, &nd->xbuf)) return rc;
-    nd->X = static_cast<const double *>(nd->xbuf->p);
+    DatasetPtr nd;
+    if (int rc = dataset_like(ctx, ds, true, nd)) return rc;  // weights carried over (ppca_model.rs:242, :259)
     if (int rc = run_post(ctx, ds, model, nullptr, nullptr, nullptr, static_cast<double *>(nd->xbuf->p), mode, nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1291,41 +1386,23 @@ extern "C" int ppca_covariance_diagonal(ppca_ctx *ctx, ppca_dataset *ds, const p
 
 // ------------------------------------------------------------------ posterior sampling
 // The draw of ppca_sample.hip over the dataset's rows into out (dataset rows x d): the posterior means and covariances of a
-// chunk of rows (the pass of ppca_infer, fused or generic) into scratch, then one draw kernel over the chunk.  Chunks bound the
-// scratch at 1 GiB (N x k x k doubles would not fit at N = 10 M, k = 64); the draw depends on the row alone, not on the chunk.
+// chunk of rows (the pass of ppca_infer, fused or generic) into scratch, then one draw kernel over the chunk (chunk_rows; the draw
+// depends on the row alone, not on the chunk).
 static int posterior_sample_rows(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int mode, uint64_t seed,
                                  int64_t row_offset, double *out, const int *choice, int comp) {
     const int k = model->k;
-    const int64_t per_row = (int64_t)sizeof(double) * ((int64_t)k * k + k);
-    const int64_t chunk = std::max<int64_t>(1024, std::min<int64_t>(ds->n, ((int64_t)1 << 30) / per_row));
+    const int64_t chunk = chunk_rows(ds->n, (int64_t)sizeof(double) * ((int64_t)k * k + k));
     const size_t rows = (size_t)std::min(chunk, ds->n);
     BufRef st, cv;
     if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
     if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
     double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
     for (int64_t r0 = 0; r0 < ds->n; r0 += chunk) {
-        ppca_dataset part(*ds);
-        part.n = std::min(chunk, ds->n - r0);
-        part.X = ds->X + r0 * ds->d;
-        part.w = ds->w ? ds->w + r0 : nullptr;
+        ppca_dataset part = row_slice(ds, r0, chunk);
         if (int rc = run_post(ctx, &part, model, nullptr, states, covs, nullptr, 0, nullptr)) return rc;
         HIP_TRY(launch_posterior_draw(ds->X, ds->d, ds->d, k, part.n, r0, row_offset, model->p(), states, covs, out, mode, seed,
                                       choice, comp, ctx->n_cu, ctx->stream));
     }
-    return PPCA_OK;
-}
-
-static int posterior_out(ppca_ctx *ctx, ppca_dataset *ds, bool carry_weights, std::unique_ptr<ppca_dataset> &nd) {
-    nd = std::make_unique<ppca_dataset>();
-    nd->ctx = ctx;
-    nd->n = ds->n;
-    nd->d = ds->d;
-    if (carry_weights) {
-        nd->wbuf = ds->wbuf;
-        nd->w = ds->w;
-    }
-    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(ds->n, 1) * ds->d, &nd->xbuf)) return rc;
-    nd->X = static_cast<const double *>(nd->xbuf->p);
     return PPCA_OK;
 }
 
@@ -1336,8 +1413,8 @@ extern "C" int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca
     if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
     if (int rc = check_pair(ds, model)) return rc;
     USE_CTX(ctx);
-    std::unique_ptr<ppca_dataset> nd;
-    if (int rc = posterior_out(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
+    DatasetPtr nd;
+    if (int rc = dataset_like(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
     if (ds->n > 0) {
         if (int rc = posterior_sample_rows(ctx, ds, model, mode, seed, row_offset, static_cast<double *>(nd->xbuf->p), nullptr, 0))
             return rc;
@@ -1348,11 +1425,9 @@ extern "C" int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca
 }
 
 // ------------------------------------------------------------------ leave-one-out predictive
-// Rows that fit 1 GiB of scratch at once (the posterior covariances, and per_entry doubles per row and dimension): the chunking of
-// posterior_sample_rows.  Every output of the LOO kernels depends on its row alone, not on the chunk.
+// The rows of a LOO chunk: per row the posterior covariance, the state and the llk, and per_entry doubles per dimension.
 static int64_t loo_chunk_rows(int64_t n, int d, int k, int per_entry) {
-    const int64_t per_row = (int64_t)sizeof(double) * ((int64_t)k * k + k + (int64_t)per_entry * d + 1);
-    return std::max<int64_t>(1024, std::min<int64_t>(std::max<int64_t>(n, 1), ((int64_t)1 << 30) / per_row));
+    return chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)k * k + k + (int64_t)per_entry * d + 1));
 }
 
 // The LOO pass of one model over part (a chunk of rows): the posterior pass of ppca_infer (fused or generic) into states / covs, then
@@ -1363,14 +1438,6 @@ static int loo_part(ppca_ctx *ctx, ppca_dataset *part, const ppca_model *model, 
     HIP_TRY(launch_loo(part->X, part->d, part->d, model->k, part->n, model->p(), states, covs, mean, var, ell, llks, ctx->n_cu,
                        ctx->stream));
     return PPCA_OK;
-}
-
-static ppca_dataset loo_slice(const ppca_dataset *ds, int64_t r0, int64_t rows) {
-    ppca_dataset part(*ds);
-    part.n = std::min(rows, ds->n - r0);
-    part.X = ds->X + r0 * ds->d;
-    part.w = ds->w ? ds->w + r0 : nullptr;
-    return part;
 }
 
 // total_host = sum_i w_i llks[i] (the fixed-order reduction of ppca_mix_llk), per_sample_host = llks; n = 0: total 0.
@@ -1399,11 +1466,11 @@ extern "C" int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_m
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int k = model->k;
-    std::unique_ptr<ppca_dataset> md, vd;  // the input weights carried over, as ppca_reconstruct does
+    DatasetPtr md, vd;  // the input weights carried over, as ppca_reconstruct does
     if (mean_out)
-        if (int rc = posterior_out(ctx, ds, true, md)) return rc;
+        if (int rc = dataset_like(ctx, ds, true, md)) return rc;
     if (var_out)
-        if (int rc = posterior_out(ctx, ds, true, vd)) return rc;
+        if (int rc = dataset_like(ctx, ds, true, vd)) return rc;
     const bool want_l = total_host || per_sample_host;
     BufRef lb;
     if (want_l)
@@ -1417,7 +1484,7 @@ extern "C" int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_m
         if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
         if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
         for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            ppca_dataset part = loo_slice(ds, r0, chunk);
+            ppca_dataset part = row_slice(ds, r0, chunk);
             if (int rc = loo_part(ctx, &part, model, static_cast<double *>(st->p), static_cast<double *>(cv->p),
                                   mean ? mean + r0 * ds->d : nullptr, var ? var + r0 * ds->d : nullptr, nullptr,
                                   llks ? llks + r0 : nullptr))
@@ -2006,12 +2073,8 @@ extern "C" int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model 
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int d = ds->d, nm = n_models;
-    auto nd = std::make_unique<ppca_dataset>();
-    nd->ctx = ctx;
-    nd->n = n;
-    nd->d = d;  // weights are NOT carried over: mix.rs:245-265 collects fresh samples
-    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1) * d, &nd->xbuf)) return rc;
-    nd->X = static_cast<const double *>(nd->xbuf->p);
+    DatasetPtr nd;
+    if (int rc = dataset_like(ctx, ds, false, nd)) return rc;  // weights are NOT carried over: mix.rs:245-265 collects fresh samples
     if (n == 0) {
         *out = nd.release();
         return PPCA_OK;
@@ -2020,9 +2083,11 @@ extern "C" int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model 
     if (int rc = mix_posteriors(ctx, ds, models, log_weights, nm, llk, u, lse, &lp)) return rc;
     const double *logpost = static_cast<const double *>(lp->p);
     double *o = static_cast<double *>(nd->xbuf->p);
-    struct Tmp {  // frees the per-component output on every exit path
+    auto recon = [&](int c, int m, DatasetPtr &to) {  // a per-component output: freed on every exit path
         ppca_dataset *p = nullptr;
-        ~Tmp() { if (p) ppca_dataset_free(p); }
+        const int rc = recon_common(ctx, ds, models[c], m, &p);
+        to.reset(p);
+        return rc;
     };
     const int vmode = mode & 1;  // 0 smooth-like, 1 extrapolate-like
     BufRef meanbuf;
@@ -2033,17 +2098,17 @@ extern "C" int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model 
     }
     double *first_target = mode >= 2 ? mean : o;
     for (int c = 0; c < nm; ++c) {
-        Tmp val;
-        if (int rc = recon_common(ctx, ds, models[c], vmode, &val.p)) return rc;
-        HIP_TRY(launch_mix_accumulate(first_target, val.p->X, nullptr, nullptr, logpost, c, nm, n, d, c == 0, ctx->stream));
+        DatasetPtr val;
+        if (int rc = recon(c, vmode, val)) return rc;
+        HIP_TRY(launch_mix_accumulate(first_target, val->X, nullptr, nullptr, logpost, c, nm, n, d, c == 0, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     if (mode >= 2) {
         for (int c = 0; c < nm; ++c) {
-            Tmp val, dg;
-            if (int rc = recon_common(ctx, ds, models[c], vmode, &val.p)) return rc;
-            if (int rc = recon_common(ctx, ds, models[c], 2 + vmode, &dg.p)) return rc;
-            HIP_TRY(launch_mix_accumulate(o, dg.p->X, val.p->X, mean, logpost, c, nm, n, d, c == 0, ctx->stream));
+            DatasetPtr val, dg;
+            if (int rc = recon(c, vmode, val)) return rc;
+            if (int rc = recon(c, 2 + vmode, dg)) return rc;
+            HIP_TRY(launch_mix_accumulate(o, dg->X, val->X, mean, logpost, c, nm, n, d, c == 0, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
         }
     }
@@ -2060,8 +2125,8 @@ extern "C" int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_m
     if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
     if (int rc = mix_check(ds, models, n_models)) return rc;
     USE_CTX(ctx);
-    std::unique_ptr<ppca_dataset> nd;
-    if (int rc = posterior_out(ctx, ds, false, nd)) return rc;  // no weights, like the other mixture outputs
+    DatasetPtr nd;
+    if (int rc = dataset_like(ctx, ds, false, nd)) return rc;  // no weights, like the other mixture outputs
     const int64_t n = ds->n;
     if (n > 0) {
         BufRef llk, u, lse, lp, ch;
@@ -2091,11 +2156,11 @@ extern "C" int ppca_mix_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, ppca_mod
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int d = ds->d, nm = n_models;
-    std::unique_ptr<ppca_dataset> md, vd;  // no weights, like the other mixture outputs
+    DatasetPtr md, vd;  // no weights, like the other mixture outputs
     if (mean_out)
-        if (int rc = posterior_out(ctx, ds, false, md)) return rc;
+        if (int rc = dataset_like(ctx, ds, false, md)) return rc;
     if (var_out)
-        if (int rc = posterior_out(ctx, ds, false, vd)) return rc;
+        if (int rc = dataset_like(ctx, ds, false, vd)) return rc;
     const bool want_l = total_host || per_sample_host, want_m = mean_out || var_out;
     BufRef lb;
     if (want_l)
@@ -2118,7 +2183,7 @@ extern "C" int ppca_mix_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, ppca_mod
         double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
         double *m = static_cast<double *>(sc->p), *v = m + nd, *ell = v + nd, *mx = ell + nd, *sm = mx + nd, *wm = sm + nd;
         for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            ppca_dataset part = loo_slice(ds, r0, chunk);
+            ppca_dataset part = row_slice(ds, r0, chunk);
             const double *lpc = logpost + r0 * nm;
             for (int c = 0; c < nm; ++c) {
                 if (int rc = loo_part(ctx, &part, models[c], states, covs, want_m ? m : nullptr, nullptr, ell, nullptr)) return rc;
@@ -2312,36 +2377,28 @@ extern "C" int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const
                                           const double *l_host, ppca_dataset **out, double *col_sums_host, double *row_sums) {
     if (!ctx || !ds || !a_host) return fail(PPCA_ERR_INVALID, "null argument");
     if (!out && !col_sums_host && !row_sums) return fail(PPCA_ERR_INVALID, "no output requested");
-    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    if (int rc = check_same_device(ds, ctx)) return rc;
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int d = ds->d;
-    std::unique_ptr<ppca_dataset> nd;
-    if (out) {
-        nd = std::make_unique<ppca_dataset>();
-        nd->ctx = ctx;
-        nd->n = n;
-        nd->d = d;
-        nd->wbuf = ds->wbuf;  // the input weights carried over, as ppca_reconstruct does
-        nd->w = ds->w;
-        if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1) * d, &nd->xbuf)) return rc;
-        nd->X = static_cast<const double *>(nd->xbuf->p);
-    }
+    DatasetPtr nd;
+    if (out)
+        if (int rc = dataset_like(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
     std::vector<double> sums((size_t)3 * d, 0.0);
     if (n > 0) {
-        BufRef abl, part, rs;
+        BufRef abl, rs;
+        Partials part;
         if (int rc = upload_abl(ctx, d, a_host, b_host, l_host, &abl)) return rc;
         const int grid = scale_grid(n, d, ctx->n_cu);
-        if (int rc = dev_alloc(sizeof(double) * ((size_t)grid + 1) * 3 * d, &part)) return rc;
+        if (int rc = part.alloc(grid, (int64_t)3 * d)) return rc;
         if (row_sums)
             if (int rc = dev_alloc(sizeof(double) * (size_t)n, &rs)) return rc;
-        double *p = static_cast<double *>(part->p), *red = p + (size_t)grid * 3 * d;
         HIP_TRY(launch_scale_columns(ds->X, ds->d, ds->w, n, d, static_cast<const double *>(abl->p),
-                                     nd ? static_cast<double *>(nd->xbuf->p) : nullptr, p, grid, rs ? static_cast<double *>(rs->p) : nullptr,
+                                     nd ? static_cast<double *>(nd->xbuf->p) : nullptr, part.p, grid, rs ? static_cast<double *>(rs->p) : nullptr,
                                      ctx->stream));
         if (col_sums_host) {
-            HIP_TRY(launch_reduce_partials(p, grid, (int64_t)3 * d, red, ctx->stream));
-            HIP_TRY(hipMemcpyAsync(sums.data(), red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(part.reduce(ctx->stream));
+            HIP_TRY(hipMemcpyAsync(sums.data(), part.red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
         }
         if (row_sums)  // (host or device destination, as ppca_llk's per-sample output)
             HIP_TRY(hipMemcpyAsync(row_sums, rs->p, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
@@ -2356,7 +2413,7 @@ extern "C" int ppca_dataset_scale_columns(ppca_ctx *ctx, ppca_dataset *ds, const
 extern "C" int ppca_dataset_pairwise_moments(ppca_ctx *ctx, ppca_dataset *ds, const double *center_host, double *sums_host,
                                              double *counts_host, double *cross_host) {
     if (!ctx || !ds || !sums_host || !counts_host) return fail(PPCA_ERR_INVALID, "null argument");
-    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    if (int rc = check_same_device(ds, ctx)) return rc;
     const int64_t n = ds->n;
     const int d = ds->d;
     if (center_host)
@@ -2400,14 +2457,8 @@ extern "C" int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_da
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int d = ds->d;
-    auto nd = std::make_unique<ppca_dataset>();
-    nd->ctx = ctx;
-    nd->n = n;
-    nd->d = d;
-    nd->wbuf = ds->wbuf;
-    nd->w = ds->w;
-    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1) * d, &nd->xbuf)) return rc;
-    nd->X = static_cast<const double *>(nd->xbuf->p);
+    DatasetPtr nd;
+    if (int rc = dataset_like(ctx, ds, true, nd)) return rc;
     if (n > 0) {
         BufRef abl;
         if (int rc = upload_abl(ctx, d, a_host, nullptr, nullptr, &abl)) return rc;
@@ -2419,50 +2470,39 @@ extern "C" int ppca_dataset_fill_masked(ppca_ctx *ctx, ppca_dataset *ds, ppca_da
     return PPCA_OK;
 }
 
+// One column's row of the host M-step that the whitened / scaled families share (FAModel and FAMix: per component; TPPCAModel), in the
+// units of the solve: S_j a = cross_j on a copy of the packed S_j (S: scratch of k (k + 1) / 2), where a pivot <= 0 keeps `old`; then
+// the contractions of the NEW row that the mean shift and the noise take: a . first (U_j, or the t sweep's V_j), a . cross_j, a' S_j a.
+struct MstepRow {
+    bool solved;
+    double af, ac, asa;
+};
+static MstepRow mstep_row(int k, const double *Sj, const double *cr, const double *first, const double *old, double *S, double *a) {
+    MstepRow r{false, 0.0, 0.0, 0.0};
+    for (int e = 0; e < k * (k + 1) / 2; ++e) S[e] = Sj[e];
+    for (int b = 0; b < k; ++b) a[b] = cr[b];
+    r.solved = chol_packed(S, k);
+    if (r.solved)
+        chol_solve_packed(S, k, a);
+    else
+        for (int b = 0; b < k; ++b) a[b] = old[b];
+    for (int b = 0; b < k; ++b) {
+        r.af += a[b] * first[b];
+        r.ac += a[b] * cr[b];
+        double row = 0.0;
+        for (int c = 0; c < k; ++c) row += Sj[c <= b ? tri(b, c) : tri(c, b)] * a[c];
+        r.asa += a[b] * row;
+    }
+    return r;
+}
+
 extern "C" int ppca_fa_finalize_host(int32_t d, int32_t k, const double *noise, const double *transform, const double *mean,
                                      const double *stats, const double *sq, const double *min_noise, double *noise_out,
                                      double *transform_out, double *mean_out) {
     if (d < 1 || k < 0 || !noise || !mean || !stats || !sq || !noise_out || !mean_out || (k > 0 && (!transform || !transform_out)))
         return fail(PPCA_ERR_INVALID, "null argument");
-    if (k == 0) {  // state size 0 = one zero column, as ppca_em_finalize_host
-        std::vector<double> c0((size_t)d, 0.0), c1((size_t)d, 0.0);
-        return ppca_fa_finalize_host(d, 1, noise, c0.data(), mean, stats, sq, min_noise, noise_out, c1.data(), mean_out);
-    }
-    const StatsLayout L(d, k);
-    std::vector<double> S((size_t)L.kp), a((size_t)k);
-    for (int j = 0; j < d; ++j) {
-        const double s = noise[j];
-        if (!(s > 0.0) || !std::isfinite(s)) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
-        const double *Sj = stats + L.S + (int64_t)j * L.kp, *cr = stats + L.cross + (int64_t)j * k, *Uj = stats + L.U + (int64_t)j * k;
-        const double tot = stats[L.totals + j];
-        // 1. the whitened row: S_j a = cross_j; a pivot <= 0 keeps the old row c_j / s_j
-        for (int e = 0; e < L.kp; ++e) S[e] = Sj[e];
-        for (int b = 0; b < k; ++b) a[b] = cr[b];
-        const bool solved = chol_packed(S.data(), k);
-        if (solved)
-            chol_solve_packed(S.data(), k, a.data());
-        else
-            for (int b = 0; b < k; ++b) a[b] = transform[(int64_t)j * k + b] / s;
-        // 2. the whitened mean moves by delta, with the NEW row
-        double au = 0.0, ac = 0.0, asa = 0.0;
-        for (int b = 0; b < k; ++b) {
-            au += a[b] * Uj[b];
-            ac += a[b] * cr[b];
-            double row = 0.0;
-            for (int c = 0; c < k; ++c) row += Sj[c <= b ? tri(b, c) : tri(c, b)] * a[c];
-            asa += a[b] * row;
-        }
-        const double delta = tot > 0.0 ? (stats[L.sumx + j] - au) / tot : 0.0;
-        // 3. the whitened noise, full form (the row may have been kept)
-        double v = tot > 0.0 ? (sq[j] - 2.0 * ac + asa - delta * delta * tot) / tot : 0.0;
-        const double pt = (tot > 0.0 && std::isfinite(v) && v > 0.0) ? std::sqrt(v) : 1.0;
-        // 4. back to the columns' units (a kept row and an unmoved mean are copied, not rescaled twice)
-        for (int b = 0; b < k; ++b) transform_out[(int64_t)j * k + b] = solved ? s * a[b] : transform[(int64_t)j * k + b];
-        mean_out[j] = delta == 0.0 ? mean[j] : s * (mean[j] / s + delta);
-        const double floor_j = min_noise ? min_noise[j] : 0.0;
-        noise_out[j] = std::max(s * pt, floor_j);
-    }
-    return PPCA_OK;
+    // (the mixture with one component and no scale: the pooled residual over the pooled weight is the column's own)
+    return ppca_famix_finalize_host(d, k, 1, noise, transform, mean, stats, sq, nullptr, min_noise, noise_out, transform_out, mean_out);
 }
 
 extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, const double *noise, const double *transform,
@@ -2473,8 +2513,7 @@ extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32
     if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
     if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
     if (int rc = check_path(d, k == 0 ? 1 : k)) return rc;
-    for (int j = 0; j < d; ++j)
-        if (!(noise[j] > 0.0) || !std::isfinite(noise[j])) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+    if (int rc = check_noise(noise, d)) return rc;
     USE_CTX(ctx);
     // the whitened model PPCAModel(1, A, mean~) and the whitening vectors a = 1 / s, b = mean / s
     std::vector<double> inv((size_t)d), mw((size_t)d), A((size_t)d * k), sums((size_t)3 * d);
@@ -2483,21 +2522,17 @@ extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32
         mw[j] = mean[j] / noise[j];
         for (int b = 0; b < k; ++b) A[(int64_t)j * k + b] = transform[(int64_t)j * k + b] / noise[j];
     }
-    struct Held {  // released on every return path; the whitened copy goes back to the context's block cache
-        ppca_dataset *y = nullptr;
-        ppca_model *m = nullptr;
-        ~Held() {
-            ppca_dataset_free(y);
-            ppca_model_free(m);
-        }
-    } held;
-    if (int rc = ppca_dataset_scale_columns(ctx, ds, inv.data(), mw.data(), nullptr, &held.y, sums.data(), nullptr)) return rc;
-    if (int rc = ppca_model_create(ctx, d, k, 1.0, A.data(), mw.data(), &held.m)) return rc;
-    const StatsLayout L(d, held.m->k);
+    ppca_dataset *y_raw = nullptr;
+    if (int rc = ppca_dataset_scale_columns(ctx, ds, inv.data(), mw.data(), nullptr, &y_raw, sums.data(), nullptr)) return rc;
+    const DatasetPtr y(y_raw);  // (the whitened copy goes back to the context's block cache)
+    ppca_model *m_raw = nullptr;
+    if (int rc = ppca_model_create(ctx, d, k, 1.0, A.data(), mw.data(), &m_raw)) return rc;
+    const ModelPtr m(m_raw);
+    const StatsLayout L(d, m->k);
     if (int rc = ensure(ctx->stats, ctx->stats_cap, sizeof(double) * (size_t)L.len)) return rc;
     double *stats = static_cast<double *>(ctx->stats->p);
     ctx->stats_llk_at = -1;  // (the llk in the buffer is the whitened model's: ppca_em_last_llk does not apply)
-    if (int rc = ppca_em_accumulate(ctx, held.y, held.m, stats)) return rc;
+    if (int rc = ppca_em_accumulate(ctx, y.get(), m.get(), stats)) return rc;
     std::vector<double> h((size_t)L.len);
     HIP_TRY(hipMemcpyAsync(h.data(), stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2515,7 +2550,7 @@ extern "C" int ppca_fa_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32
 // ------------------------------------------------------------------ masked k-means
 static int kmeans_check(const ppca_ctx *ctx, const ppca_dataset *ds, const double *scale_host, int32_t n_clusters) {
     if (n_clusters < 1 || n_clusters > MIX_MAX) return fail(PPCA_ERR_UNSUPPORTED, "n_clusters must lie in [1, %d]", MIX_MAX);
-    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    if (int rc = check_same_device(ds, ctx)) return rc;
     if (scale_host)
         for (int j = 0; j < ds->d; ++j)
             if (!std::isfinite(scale_host[j])) return fail(PPCA_ERR_INVALID, "scale[%d] is not a finite number", j);
@@ -2551,9 +2586,10 @@ extern "C" int ppca_dataset_kmeans_step(ppca_ctx *ctx, ppca_dataset *ds, const d
     const bool rows_lab = labels || blocks || (sums_host && !fused), rows_dist = dist || blocks;
     const int grid = kmeans_ctx_grid(ctx, n, K);
     const int64_t plen = (sums_host ? (int64_t)slen : 0) + 1;  // [K][2][d] | inertia
-    BufRef cen, part, lab, dst;
+    BufRef cen, lab, dst;
+    Partials part;
     if (int rc = dev_alloc(sizeof(double) * ((size_t)K * d + d), &cen)) return rc;
-    if (int rc = dev_alloc(sizeof(double) * ((size_t)grid + 1) * plen, &part)) return rc;
+    if (int rc = part.alloc(grid, plen)) return rc;
     if (rows_lab)
         if (int rc = dev_alloc(sizeof(int32_t) * (size_t)n, &lab)) return rc;
     if (rows_dist)
@@ -2561,7 +2597,7 @@ extern "C" int ppca_dataset_kmeans_step(ppca_ctx *ctx, ppca_dataset *ds, const d
     std::vector<double> h((size_t)K * d + d, 1.0), out((size_t)plen, 0.0);
     std::memcpy(h.data(), centers_host, sizeof(double) * (size_t)K * d);
     if (scale_host) std::memcpy(h.data() + (size_t)K * d, scale_host, sizeof(double) * d);
-    double *mu = static_cast<double *>(cen->p), *p = static_cast<double *>(part->p), *red = p + (size_t)grid * plen;
+    double *mu = static_cast<double *>(cen->p), *p = part.p;
     const double *a_dev = scale_host ? mu + (size_t)K * d : nullptr;
     int32_t *lab_dev = lab ? static_cast<int32_t *>(lab->p) : nullptr;
     double *dist_dev = dst ? static_cast<double *>(dst->p) : nullptr;
@@ -2581,8 +2617,8 @@ extern "C" int ppca_dataset_kmeans_step(ppca_ctx *ctx, ppca_dataset *ds, const d
                 HIP_TRY(launch_kmeans_update(ds->X, ds->d, ds->w, n, d, mu + (size_t)k0 * d, std::min(KMEANS_KB_MAX, K - k0), k0, lab_dev, p,
                                              plen, grid, ctx->stream));
     }
-    HIP_TRY(launch_reduce_partials(p, grid, plen, red, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out.data(), red, sizeof(double) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(part.reduce(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out.data(), part.red, sizeof(double) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
     if (labels)  // (host or device destinations, as ppca_llk's per-sample output)
         HIP_TRY(hipMemcpyAsync(labels, lab_dev, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, ctx->stream));
     if (dist) HIP_TRY(hipMemcpyAsync(dist, dist_dev, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
@@ -2700,7 +2736,7 @@ extern "C" int ppca_dataset_column_moments_multi(ppca_ctx *ctx, ppca_dataset *ds
     if (!ctx || !ds || !sums_host) return fail(PPCA_ERR_INVALID, "null argument");
     if ((e_host == nullptr) == (e_dev == nullptr)) return fail(PPCA_ERR_INVALID, "exactly one of e_host and e_dev must be given");
     if (n_comp < 1 || n_comp > MIX_MAX) return fail(PPCA_ERR_INVALID, "n_comp must lie in [1, %d]", MIX_MAX);
-    if (ds->ctx->device != ctx->device) return fail(PPCA_ERR_INVALID, "dataset and context live on different devices");
+    if (int rc = check_same_device(ds, ctx)) return rc;
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int d = ds->d;
@@ -2709,11 +2745,12 @@ extern "C" int ppca_dataset_column_moments_multi(ppca_ctx *ctx, ppca_dataset *ds
     if (n == 0) return PPCA_OK;
     // every device block first: [a | b], the weights (when they come from the host), the partials + their sum
     const int grid = moments_multi_grid(n, n_comp, ctx->n_cu);
-    BufRef ab, ew, part;
+    BufRef ab, ew;
+    Partials part;
     if (int rc = dev_alloc(sizeof(double) * ((size_t)d + (size_t)n_comp * d), &ab)) return rc;
     if (e_host)
         if (int rc = dev_alloc(sizeof(double) * (size_t)n_comp * n, &ew)) return rc;
-    if (int rc = dev_alloc(sizeof(double) * ((size_t)grid + 1) * len, &part)) return rc;
+    if (int rc = part.alloc(grid, (int64_t)len)) return rc;
     std::vector<double> h((size_t)d + (size_t)n_comp * d, 0.0);
     if (a_host) std::memcpy(h.data(), a_host, sizeof(double) * d);
     if (b_host) std::memcpy(h.data() + d, b_host, sizeof(double) * (size_t)n_comp * d);
@@ -2723,10 +2760,9 @@ extern "C" int ppca_dataset_column_moments_multi(ppca_ctx *ctx, ppca_dataset *ds
         HIP_TRY(hipMemcpyAsync(ew->p, e_host, sizeof(double) * (size_t)n_comp * n, hipMemcpyHostToDevice, ctx->stream));
         e_dev = static_cast<const double *>(ew->p);
     }
-    double *p = static_cast<double *>(part->p), *red = p + (size_t)grid * len;
-    HIP_TRY(launch_column_moments_multi(ds->X, ds->d, n, d, e_dev, n_comp, a_host ? abp : nullptr, abp + d, p, grid, ctx->stream));
-    HIP_TRY(launch_reduce_partials(p, grid, (int64_t)len, red, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(sums_host, red, sizeof(double) * len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(launch_column_moments_multi(ds->X, ds->d, n, d, e_dev, n_comp, a_host ? abp : nullptr, abp + d, part.p, grid, ctx->stream));
+    HIP_TRY(part.reduce(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sums_host, part.red, sizeof(double) * len, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (h and e_host are read until here)
     return PPCA_OK;
 }
@@ -2744,41 +2780,28 @@ extern "C" int ppca_famix_finalize_host(int32_t d, int32_t k, int32_t n_comp, co
     const StatsLayout L(d, k);
     for (int c = 0; c < n_comp; ++c)
         if (scale && !(scale[c] >= 0.0 && std::isfinite(scale[c]))) return fail(PPCA_ERR_INVALID, "scale[%d] is not a finite number >= 0", c);
-    std::vector<double> S((size_t)L.kp), a((size_t)k);
+    if (int rc = check_noise(noise, d)) return rc;
+    std::vector<double> S((size_t)L.kp), a((size_t)k), old((size_t)k);
     for (int j = 0; j < d; ++j) {
         const double s = noise[j];
-        if (!(s > 0.0) || !std::isfinite(s)) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
         double num = 0.0, den = 0.0;  // the residual sum of squares and the weight of column j, all components pooled
         for (int c = 0; c < n_comp; ++c) {
             const double *st = stats + (int64_t)c * L.len, *tr = transforms + ((int64_t)c * d + j) * k;
             const double *Sj = st + L.S + (int64_t)j * L.kp, *cr = st + L.cross + (int64_t)j * k, *Uj = st + L.U + (int64_t)j * k;
             const double tot = st[L.totals + j], mean = means[(int64_t)c * d + j];
             // 1. the whitened row of component c: S_cj a = cross_cj; a pivot <= 0 keeps the old row c_cj / s_j
-            for (int e = 0; e < L.kp; ++e) S[e] = Sj[e];
-            for (int b = 0; b < k; ++b) a[b] = cr[b];
-            const bool solved = chol_packed(S.data(), k);
-            if (solved)
-                chol_solve_packed(S.data(), k, a.data());
-            else
-                for (int b = 0; b < k; ++b) a[b] = tr[b] / s;
+            for (int b = 0; b < k; ++b) old[b] = tr[b] / s;
+            const MstepRow r = mstep_row(k, Sj, cr, Uj, old.data(), S.data(), a.data());
             // 2. its whitened mean moves by delta, with the NEW row
-            double au = 0.0, ac = 0.0, asa = 0.0;
-            for (int b = 0; b < k; ++b) {
-                au += a[b] * Uj[b];
-                ac += a[b] * cr[b];
-                double row = 0.0;
-                for (int e = 0; e < k; ++e) row += Sj[e <= b ? tri(b, e) : tri(e, b)] * a[e];
-                asa += a[b] * row;
-            }
-            const double delta = tot > 0.0 ? (st[L.sumx + j] - au) / tot : 0.0;
+            const double delta = tot > 0.0 ? (st[L.sumx + j] - r.af) / tot : 0.0;
             // 3. its share of the pooled sums, brought to the common scale of the components
             const double sc = scale ? scale[c] : 1.0;
             if (tot > 0.0) {
-                num += sc * (sq[(int64_t)c * d + j] - 2.0 * ac + asa - delta * delta * tot);
+                num += sc * (sq[(int64_t)c * d + j] - 2.0 * r.ac + r.asa - delta * delta * tot);
                 den += sc * tot;
             }
             // 4. back to the columns' units (a kept row and an unmoved mean are copied, not rescaled twice)
-            for (int b = 0; b < k; ++b) transforms_out[((int64_t)c * d + j) * k + b] = solved ? s * a[b] : tr[b];
+            for (int b = 0; b < k; ++b) transforms_out[((int64_t)c * d + j) * k + b] = r.solved ? s * a[b] : tr[b];
             means_out[(int64_t)c * d + j] = delta == 0.0 ? mean : s * (mean / s + delta);
         }
         const double v = den > 0.0 ? num / den : 0.0;
@@ -2808,63 +2831,56 @@ extern "C" int ppca_famix_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, in
     if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
     if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
     if (int rc = check_path(d, k == 0 ? 1 : k)) return rc;
-    for (int j = 0; j < d; ++j)
-        if (!(noise[j] > 0.0) || !std::isfinite(noise[j])) return fail(PPCA_ERR_INVALID, "noise[%d] is not a positive finite number", j);
+    if (int rc = check_noise(noise, d)) return rc;
     USE_CTX(ctx);
     const int nm = n_comp;
     const int64_t n = ds->n;
     const int ki = k == 0 ? 1 : k;
     const StatsLayout L(d, ki);
-    const int64_t len = L.len, mlen = model_len(d, ki), sums_at = (int64_t)nm * len, llk_at = sums_at + nm, total = llk_at + 1;
+    const int64_t len = L.len, sums_at = (int64_t)nm * len, llk_at = sums_at + nm, total = llk_at + 1;
     const size_t sweep_len = (size_t)nm * 3 * d;
-    // the whitened models PPCAModel(1, A_c, mean~_c) as device buffers, and the whitening vector 1 / s
-    std::vector<double> inv((size_t)d), mw((size_t)nm * d), hm((size_t)nm * mlen, 0.0), tot((size_t)3 * d);
+    // the images of the whitened models PPCAModel(1, A_c, mean~_c), and the whitening vector 1 / s
+    std::vector<double> inv((size_t)d), mw((size_t)nm * d), A((size_t)d * k), tot((size_t)3 * d);
+    std::vector<std::vector<double>> hm;
     for (int j = 0; j < d; ++j) inv[j] = 1.0 / noise[j];
     for (int c = 0; c < nm; ++c) {
-        double *m = hm.data() + (size_t)c * mlen;
-        m[0] = 1.0;
-        m[1] = 1.0;  // sigma, sigma^2, ln sigma = 0
         for (int j = 0; j < d; ++j) {
-            for (int b = 0; b < k; ++b) m[MODEL_HDR + (int64_t)j * ki + b] = transforms[((int64_t)c * d + j) * k + b] / noise[j];
-            mw[(size_t)c * d + j] = m[MODEL_HDR + (int64_t)d * ki + j] = means[(int64_t)c * d + j] / noise[j];
+            for (int b = 0; b < k; ++b) A[(int64_t)j * k + b] = transforms[((int64_t)c * d + j) * k + b] / noise[j];
+            mw[(size_t)c * d + j] = means[(int64_t)c * d + j] / noise[j];
         }
+        hm.push_back(model_image(1.0, A.data(), mw.data() + (size_t)c * d, d, k, ki));
     }
-    struct Held {  // released on every return path; the whitened copy goes back to the context's block cache
-        ppca_dataset *y = nullptr;
-        std::vector<ppca_model *> m;
-        ~Held() {
-            ppca_dataset_free(y);
-            for (ppca_model *p : m) ppca_model_free(p);
-        }
-    } held;
+    std::vector<ModelPtr> held;    // the whitened models: released on every return path
+    std::vector<ppca_model *> wm;  // ... as the array the mixture passes take
     // every device block of the step, before its first launch: the K whitened models, mix_step_blocks' list for the llk sweeps and
     // component passes (the whitened copy has the shape of ds), then the step's own
     for (int c = 0; c < nm; ++c) {
         ppca_model *m = nullptr;
         if (int rc = ppca_model_alloc(ctx, d, k, &m)) return rc;
-        held.m.push_back(m);
+        held.emplace_back(m);
+        wm.push_back(m);
     }
     const int sgrid = moments_multi_grid(n, nm, ctx->n_cu);
     MixAux ax;
     if (int rc = mix_aux(ctx, nm, ax)) return rc;
     if (int rc = ensure(ctx->mixpack, ctx->mixpack_cap, sizeof(double) * (size_t)total)) return rc;
-    if (int rc = mix_step_blocks(ctx, ds, held.m.data(), nm)) return rc;
-    BufRef ew, bdev, spart;
+    if (int rc = mix_step_blocks(ctx, ds, wm.data(), nm)) return rc;
+    BufRef ew, bdev;
+    Partials spart;
     if (int rc = dev_alloc(sizeof(double) * (size_t)nm * n, &ew)) return rc;
     if (int rc = dev_alloc(sizeof(double) * (size_t)nm * d, &bdev)) return rc;
-    if (int rc = dev_alloc(sizeof(double) * ((size_t)sgrid + 1) * sweep_len, &spart)) return rc;
+    if (int rc = spart.alloc(sgrid, (int64_t)sweep_len)) return rc;
     // 1. whiten; tot_j = sum_i w_i m_ij for the Jacobian term of the llk
-    if (int rc = ppca_dataset_scale_columns(ctx, ds, inv.data(), nullptr, nullptr, &held.y, tot.data(), nullptr)) return rc;
-    for (int c = 0; c < nm; ++c) {
-        touch(held.m[c]);
-        HIP_TRY(hipMemcpyAsync(held.m[c]->p(), hm.data() + (size_t)c * mlen, sizeof(double) * (size_t)mlen, hipMemcpyHostToDevice, ctx->stream));
-    }
+    ppca_dataset *y_raw = nullptr;
+    if (int rc = ppca_dataset_scale_columns(ctx, ds, inv.data(), nullptr, nullptr, &y_raw, tot.data(), nullptr)) return rc;
+    const DatasetPtr y(y_raw);  // (the whitened copy goes back to the context's block cache)
+    for (int c = 0; c < nm; ++c) HIP_TRY(model_upload(ctx, wm[c], hm[c]));
     HIP_TRY(hipMemcpyAsync(bdev->p, mw.data(), sizeof(double) * mw.size(), hipMemcpyHostToDevice, ctx->stream));
     // 2. responsibilities u_ic = ln w_i + log r_ic, the mixture llk, 3. the shifts
     double *pack = static_cast<double *>(ctx->mixpack->p), *aux = ax.shift, *work = static_cast<double *>(ctx->work->p);
     BufRef llk, u, lse;
-    if (int rc = mix_posteriors(ctx, held.y, held.m.data(), log_weights, nm, llk, u, lse, nullptr)) return rc;
-    HIP_TRY(launch_reduce_sum(static_cast<double *>(lse->p), held.y->w, n, pack + llk_at, work, ctx->stream));
+    if (int rc = mix_posteriors(ctx, y.get(), wm.data(), log_weights, nm, llk, u, lse, nullptr)) return rc;
+    HIP_TRY(launch_reduce_sum(static_cast<double *>(lse->p), y->w, n, pack + llk_at, work, ctx->stream));
     const double *ud = static_cast<const double *>(u->p);
     for (int c = 0; c < nm; ++c) HIP_TRY(launch_reduce_max(ud + (size_t)c * n, n, aux + c, work, ctx->stream));
     HIP_TRY(launch_mix_shift(aux, nm, ctx->stream));
@@ -2872,19 +2888,18 @@ extern "C" int ppca_famix_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, in
     ctx->stats_llk_at = -1;
     double *ewp = static_cast<double *>(ew->p);
     for (int c = 0; c < nm; ++c) {
-        if (int rc = mix_component_enqueue(ctx, held.y, held.m[c], ud + (size_t)c * n, aux + c, pack + (size_t)c * len, pack + sums_at + c, nullptr))
+        if (int rc = mix_component_enqueue(ctx, y.get(), wm[c], ud + (size_t)c * n, aux + c, pack + (size_t)c * len, pack + sums_at + c, nullptr))
             return rc;
         HIP_TRY(launch_exp_shift(ud + (size_t)c * n, aux + c, n, ewp + (size_t)c * n, ctx->stream));
     }
     // 5. sq_cj on Y
-    double *sp = static_cast<double *>(spart->p), *sred = sp + (size_t)sgrid * sweep_len;
-    HIP_TRY(launch_column_moments_multi(held.y->X, held.y->d, n, d, ewp, nm, nullptr, static_cast<const double *>(bdev->p), sp, sgrid, ctx->stream));
-    HIP_TRY(launch_reduce_partials(sp, sgrid, (int64_t)sweep_len, sred, ctx->stream));
+    HIP_TRY(launch_column_moments_multi(y->X, y->d, n, d, ewp, nm, nullptr, static_cast<const double *>(bdev->p), spart.p, sgrid, ctx->stream));
+    HIP_TRY(spart.reduce(ctx->stream));
     // 6. new log-weights; everything to the host
     HIP_TRY(launch_mix_logweights(pack + sums_at, aux, pack + llk_at, nm, ax.out, ctx->stream));
     std::vector<double> h((size_t)total), hs(sweep_len), hshift((size_t)nm), hlw((size_t)nm + 1);
     HIP_TRY(hipMemcpyAsync(h.data(), pack, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hs.data(), sred, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), spart.red, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(hshift.data(), aux, sizeof(double) * hshift.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(hlw.data(), ax.out, sizeof(double) * hlw.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2942,7 +2957,7 @@ static double t_log_norm(double a, double h) {
 
 extern "C" int ppca_t_tables_host(int32_t d, double dof, double *lg_out, double *g_out) {
     if (d < 0 || !lg_out || !g_out) return fail(PPCA_ERR_INVALID, "null argument");
-    if (!(dof > 0.0) || !std::isfinite(dof)) return fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+    if (int rc = check_dof(dof)) return rc;
     for (int m = 0; m <= d; ++m) {
         lg_out[m] = t_log_norm(0.5 * dof, 0.5 * m);
         g_out[m] = digamma_minus_log(0.5 * (dof + m));
@@ -2952,23 +2967,23 @@ extern "C" int ppca_t_tables_host(int32_t d, double dof, double *lg_out, double 
 
 static int t_check(const ppca_dataset *ds, const ppca_model *model, double dof) {
     if (int rc = check_pair(ds, model)) return rc;
-    if (model->zero_state || !robust_covers(model->d, model->k))
-        return fail(PPCA_ERR_UNSUPPORTED, "the Student-t sweep covers state sizes 1 .. %d and output sizes 1 .. %d (got k=%d, d=%d)",
-                    ROBUST_MAX_K, ROBUST_MAX_D, model->k_user(), model->d);
-    if (!(dof > 0.0) || !std::isfinite(dof)) return fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+    if (int rc = check_t_covers(model->d, model->k_user())) return rc;  // (a zero-state model runs with one zero column: not covered)
+    if (int rc = check_dof(dof)) return rc;
     return PPCA_OK;
 }
 
 // What a sweep keeps alive until the caller's synchronisation: the host side of its asynchronous copies and its device scratch.
 struct TSweep {
     std::vector<double> tabs, res;  // [lg | g] as uploaded; the reduced [column sums | 4 scalars] as downloaded
-    BufRef tabs_dev, llks, states, part;
+    BufRef tabs_dev, llks, states;
+    Partials part;
     int64_t plen = 0;
 };
 
 // Enqueues the sweep over the whole dataset by row chunks (the posterior pass into scratch, then the streaming kernel) and the copy of
 // the reduced sums into sw.res; no synchronisation.  Y (nullable): n x d on the device; u, maha, ell (nullable): n doubles each on the
-// device.  The chunks bound the scratch at 1 GiB as ppca_loo_predictive's do; the per-row outputs do not depend on them.
+// device.  Row chunks as ppca_loo_predictive's (chunk_rows): the per-row outputs do not depend on them, the last bits of the column sums,
+// accumulated chunk after chunk, do.
 static int t_sweep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, double dof, double *Y, bool sums, double *u, double *maha,
                    double *ell, TSweep &sw) {
     const int64_t n = ds->n;
@@ -2981,35 +2996,25 @@ static int t_sweep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, dou
     if (int rc = ppca_t_tables_host(d, dof, sw.tabs.data(), sw.tabs.data() + d + 1)) return rc;
     if (int rc = dev_alloc(sizeof(double) * sw.tabs.size(), &sw.tabs_dev)) return rc;
     HIP_TRY(hipMemcpyAsync(sw.tabs_dev->p, sw.tabs.data(), sizeof(double) * sw.tabs.size(), hipMemcpyHostToDevice, ctx->stream));
-    const int64_t chunk = std::max<int64_t>(1024, std::min<int64_t>(n, ((int64_t)1 << 30) / ((int64_t)sizeof(double) * (k + 1))));
+    const int64_t chunk = chunk_rows(n, (int64_t)sizeof(double) * (k + 1));
     const size_t rows = (size_t)std::min(chunk, n);
     const int grid_max = robust_grid((int64_t)rows, d, k, ctx->n_cu);
     if (int rc = dev_alloc(sizeof(double) * rows, &sw.llks)) return rc;
     if (int rc = dev_alloc(sizeof(double) * rows * k, &sw.states)) return rc;
-    if (int rc = dev_alloc(sizeof(double) * ((size_t)grid_max + 1) * (size_t)sw.plen, &sw.part)) return rc;
+    if (int rc = sw.part.alloc(grid_max, sw.plen)) return rc;
     double *llks = static_cast<double *>(sw.llks->p), *states = static_cast<double *>(sw.states->p);
-    double *part = static_cast<double *>(sw.part->p), *red = part + (size_t)grid_max * sw.plen;
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        ppca_dataset sl = loo_slice(ds, r0, chunk);
+        ppca_dataset sl = row_slice(ds, r0, chunk);
         if (int rc = run_post(ctx, &sl, model, llks, states, nullptr, nullptr, 0, nullptr)) return rc;
         const int grid = robust_grid(sl.n, d, k, ctx->n_cu);
         HIP_TRY(launch_robust_sweep(sl.X, sl.d, sl.w, sl.n, d, k, model->p(), llks, states, static_cast<const double *>(sw.tabs_dev->p), dof,
                                     Y ? Y + r0 * d : nullptr, so, u ? u + r0 : nullptr, maha ? maha + r0 : nullptr, ell ? ell + r0 : nullptr,
-                                    part, grid, ctx->stream));
-        HIP_TRY(launch_reduce_partials(part, grid, sw.plen, red, ctx->stream, r0 > 0 ? 1 : 0));
+                                    sw.part.p, grid, ctx->stream));
+        HIP_TRY(sw.part.reduce(ctx->stream, r0 > 0 ? 1 : 0, grid));
     }
-    HIP_TRY(hipMemcpyAsync(sw.res.data(), red, sizeof(double) * sw.res.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sw.res.data(), sw.part.red, sizeof(double) * sw.res.size(), hipMemcpyDeviceToHost, ctx->stream));
     return PPCA_OK;
 }
-
-// Waits for the stream on every way out of a scope whose host buffers asynchronous copies still read or write.
-struct TStreamGuard {
-    hipStream_t s;
-    bool armed = true;
-    ~TStreamGuard() {
-        if (armed) (void)hipStreamSynchronize(s);
-    }
-};
 
 extern "C" int ppca_t_estep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, double dof, ppca_dataset **scaled_out,
                             double *col_sums_host, double *u, double *maha, double *llks, double *scalars_host) {
@@ -3019,9 +3024,9 @@ extern "C" int ppca_t_estep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *m
     USE_CTX(ctx);
     const int64_t n = ds->n;
     const int d = ds->d, k = model->k;
-    std::unique_ptr<ppca_dataset> nd;
+    DatasetPtr nd;
     if (scaled_out)
-        if (int rc = posterior_out(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
+        if (int rc = dataset_like(ctx, ds, true, nd)) return rc;  // the input weights carried over, as ppca_reconstruct does
     BufRef ub, mb, lb;
     const size_t nb = sizeof(double) * (size_t)std::max<int64_t>(n, 1);
     if (u)
@@ -3031,7 +3036,7 @@ extern "C" int ppca_t_estep(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *m
     if (llks)
         if (int rc = dev_alloc(nb, &lb)) return rc;
     TSweep sw;
-    TStreamGuard guard{ctx->stream};
+    StreamGuard guard{ctx->stream};
     if (int rc = t_sweep(ctx, ds, model, dof, nd ? static_cast<double *>(nd->xbuf->p) : nullptr, col_sums_host != nullptr,
                          ub ? static_cast<double *>(ub->p) : nullptr, mb ? static_cast<double *>(mb->p) : nullptr,
                          lb ? static_cast<double *>(lb->p) : nullptr, sw))
@@ -3053,7 +3058,7 @@ extern "C" int ppca_t_finalize_host(int32_t d, int32_t k, double sigma, const do
                                     const double *col_sums, double *sigma_out, double *transform_out, double *mean_out) {
     if (d < 1 || k < 1 || !transform || !mean || !stats || !col_sums || !sigma_out || !transform_out || !mean_out)
         return fail(PPCA_ERR_INVALID, "null argument");
-    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(PPCA_ERR_INVALID, "sigma is not a positive finite number");
+    if (int rc = check_sigma(sigma)) return rc;
     const StatsLayout L(d, k);
     const double *V = col_sums, *A = col_sums + (int64_t)d * k, *T = A + d, *sq = T + d;
     std::vector<double> S((size_t)L.kp), a((size_t)k);
@@ -3061,24 +3066,11 @@ extern "C" int ppca_t_finalize_host(int32_t d, int32_t k, double sigma, const do
     for (int j = 0; j < d; ++j) {
         const double *Sj = stats + L.S + (int64_t)j * L.kp, *cr = stats + L.cross + (int64_t)j * k, *Vj = V + (int64_t)j * k;
         // 1. the row: S_j a = cross_j; a pivot <= 0 keeps the old row
-        for (int e = 0; e < L.kp; ++e) S[e] = Sj[e];
-        for (int b = 0; b < k; ++b) a[b] = cr[b];
-        if (chol_packed(S.data(), k))
-            chol_solve_packed(S.data(), k, a.data());
-        else
-            for (int b = 0; b < k; ++b) a[b] = transform[(int64_t)j * k + b];
+        const MstepRow r = mstep_row(k, Sj, cr, Vj, transform + (int64_t)j * k, S.data(), a.data());
         // 2. the mean moves by delta, with the NEW row
-        double av = 0.0, ac = 0.0, asa = 0.0;
-        for (int b = 0; b < k; ++b) {
-            av += a[b] * Vj[b];
-            ac += a[b] * cr[b];
-            double row = 0.0;
-            for (int c = 0; c < k; ++c) row += Sj[c <= b ? tri(b, c) : tri(c, b)] * a[c];
-            asa += a[b] * row;
-        }
-        const double delta = T[j] > 0.0 ? (A[j] - av) / T[j] : 0.0;
+        const double delta = T[j] > 0.0 ? (A[j] - r.af) / T[j] : 0.0;
         // 3. the pooled noise, full form (the row may have been kept)
-        num += sq[j] - 2.0 * ac + asa - delta * delta * T[j];
+        num += sq[j] - 2.0 * r.ac + r.asa - delta * delta * T[j];
         den += stats[L.totals + j];
         for (int b = 0; b < k; ++b) transform_out[(int64_t)j * k + b] = a[b];
         mean_out[j] = mean[j] + delta;
@@ -3094,49 +3086,33 @@ extern "C" int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_
     if (!ctx || !ds || !transform || !mean || !sigma_out || !transform_out || !mean_out) return fail(PPCA_ERR_INVALID, "null argument");
     if (d < 1 || k < 0) return fail(PPCA_ERR_INVALID, "invalid shape d=%d k=%d", d, k);
     if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
-    if (!robust_covers(d, k))
-        return fail(PPCA_ERR_UNSUPPORTED, "the Student-t sweep covers state sizes 1 .. %d and output sizes 1 .. %d (got k=%d, d=%d)",
-                    ROBUST_MAX_K, ROBUST_MAX_D, k, d);
-    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(PPCA_ERR_INVALID, "sigma is not a positive finite number");
-    if (!(dof > 0.0) || !std::isfinite(dof)) return fail(PPCA_ERR_INVALID, "dof must be a positive finite number");
+    if (int rc = check_t_covers(d, k)) return rc;
+    if (int rc = check_sigma(sigma)) return rc;
+    if (int rc = check_dof(dof)) return rc;
     if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
     USE_CTX(ctx);
-    struct Held {  // released on every return path; the scaled copy goes back to the context's block cache
-        ppca_dataset *y = nullptr;
-        ppca_model *m = nullptr, *m0 = nullptr;
-        ~Held() {
-            ppca_dataset_free(y);
-            ppca_model_free(m);
-            ppca_model_free(m0);
-        }
-    } held;
     // the model (sigma, C, mean) of the sweep and (sigma, C, 0) of the EM pass on the centred, scaled rows: uploaded without a wait
     // (hm, hm0 are read until the synchronisation below)
-    if (int rc = ppca_model_alloc(ctx, d, k, &held.m)) return rc;
-    if (int rc = ppca_model_alloc(ctx, d, k, &held.m0)) return rc;
-    std::vector<double> hm((size_t)model_len(d, k), 0.0), hm0;
-    hm[0] = sigma;
-    hm[1] = sigma * sigma;
-    hm[2] = std::log(sigma);
-    std::memcpy(hm.data() + MODEL_HDR, transform, sizeof(double) * (size_t)d * k);
-    hm0 = hm;
-    std::memcpy(hm.data() + MODEL_HDR + (size_t)d * k, mean, sizeof(double) * d);
+    ppca_model *m_raw = nullptr, *m0_raw = nullptr;
+    if (int rc = ppca_model_alloc(ctx, d, k, &m_raw)) return rc;
+    const ModelPtr m(m_raw);
+    if (int rc = ppca_model_alloc(ctx, d, k, &m0_raw)) return rc;
+    const ModelPtr m0(m0_raw);
+    const std::vector<double> zero((size_t)d, 0.0), hm = model_image(sigma, transform, mean, d, k, k),
+                              hm0 = model_image(sigma, transform, zero.data(), d, k, k);
+    DatasetPtr y;  // (the scaled copy goes back to the context's block cache)
     TSweep sw;
-    TStreamGuard guard{ctx->stream};
-    touch(held.m);
-    touch(held.m0);
-    HIP_TRY(hipMemcpyAsync(held.m->p(), hm.data(), sizeof(double) * hm.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(held.m0->p(), hm0.data(), sizeof(double) * hm0.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = check_pair(ds, held.m)) return rc;
-    std::unique_ptr<ppca_dataset> nd;
-    if (int rc = posterior_out(ctx, ds, true, nd)) return rc;
-    held.y = nd.release();
-    if (int rc = t_sweep(ctx, ds, held.m, dof, static_cast<double *>(held.y->xbuf->p), true, nullptr, nullptr, nullptr, sw)) return rc;
+    StreamGuard guard{ctx->stream};
+    HIP_TRY(model_upload(ctx, m.get(), hm));
+    HIP_TRY(model_upload(ctx, m0.get(), hm0));
+    if (int rc = check_pair(ds, m.get())) return rc;
+    if (int rc = dataset_like(ctx, ds, true, y)) return rc;
+    if (int rc = t_sweep(ctx, ds, m.get(), dof, static_cast<double *>(y->xbuf->p), true, nullptr, nullptr, nullptr, sw)) return rc;
     const StatsLayout L(d, k);
     if (int rc = ensure(ctx->stats, ctx->stats_cap, sizeof(double) * (size_t)L.len)) return rc;
     double *stats = static_cast<double *>(ctx->stats->p);
     ctx->stats_llk_at = -1;  // (the llk in the buffer is the scaled rows' Gaussian one: ppca_em_last_llk does not apply)
-    if (int rc = ppca_em_accumulate(ctx, held.y, held.m0, stats)) return rc;
+    if (int rc = ppca_em_accumulate(ctx, y.get(), m0.get(), stats)) return rc;
     std::vector<double> h((size_t)L.len);
     HIP_TRY(hipMemcpyAsync(h.data(), stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
     guard.armed = false;

@@ -2,6 +2,7 @@
 declared, ppca_fa_finalize_host -- the FA M-step on host buffers -- agrees with a dense numpy restatement in original units
 (tests/fa_restatement.py), and FAModel's host-side logic (validation, serialisation, canonical form, whitening) holds."""
 import ctypes as C
+import io
 import os
 import pickle
 import re
@@ -197,9 +198,17 @@ def test_famodel_dump_load_and_pickle_round_trip():
     import ppca_rs_amd as p
 
     m = _model()
+    m = p.FAModel(m.noise, m.transform, np.where(m.mean > 0.5, -0.0, m.mean))  # (a sign bit that == does not see)
+    fields = ("noise", "transform", "mean")
     for back in (p.FAModel.load(m.dump()), pickle.loads(pickle.dumps(m))):
         assert isinstance(back, p.FAModel)
-        assert np.array_equal(back.noise, m.noise) and np.array_equal(back.transform, m.transform) and np.array_equal(back.mean, m.mean)
+        assert all(getattr(back, f).tobytes() == getattr(m, f).tobytes() and getattr(back, f).shape == getattr(m, f).shape for f in fields)
+    z = np.load(io.BytesIO(m.dump()), allow_pickle=False)
+    assert z.files == ["kind"] + list(fields) and str(z["kind"]) == "ppca_rs_amd.FAModel"
+    assert all(z[f].dtype == np.float64 and z[f].tobytes() == getattr(m, f).tobytes() for f in fields)
+    with pytest.raises(Exception) as err:
+        p.FAModel.load(p.TPPCAModel(1.0, np.ones((3, 1)), np.zeros(3), 4.0).dump())  # another of the library's own containers
+    assert type(err.value) is Exception and str(err.value) == "not an FAModel container: ppca_rs_amd.TPPCAModel"
     with pytest.raises(Exception):
         p.FAModel.load(p.PPCAModel(1.0, np.ones((3, 1)), np.zeros(3)).dump())  # another kind of container
     with pytest.raises(Exception):

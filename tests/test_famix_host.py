@@ -1,7 +1,9 @@
 """CPU-only: the surface of the mixture of factor analysers (FAMix, FAMixTrainer, Dataset._column_moments_multi; the three C-ABI entry
 points behind them) is exported and declared, ppca_famix_finalize_host -- the M-step on host buffers -- agrees with a dense numpy
-restatement in original units (tests/famix_restatement.py), and FAMix's host-side logic (validation, serialisation, canonical form,
-whitening) holds."""
+restatement in original units (tests/famix_restatement.py) and, with one component and no scale, IS ppca_fa_finalize_host byte for
+byte; FAMix's host-side logic (validation, serialisation, canonical form, whitening) holds; and the loop that the five trainers share
+prints each trainer's line and, when quiet, reads no log-likelihood back."""
+import io
 import os
 import pickle
 import re
@@ -153,6 +155,49 @@ def test_famix_finalize_host_with_one_component_is_the_fa_finalisation(hiplib, c
             _assert_close(_finalize(hiplib, psi, [cs[q]], [mus[q]], st[None], s2[None], scale, None), (po, [co], [mo]), 1e-13)
 
 
+@pytest.mark.parametrize("d,k", [(1, 1), (5, 0), (7, 3), (33, 10), (64, 16)])
+def test_fa_finalize_host_is_famix_finalize_host_with_one_component_byte_for_byte(hiplib, d, k):
+    """ppca_fa_finalize_host against ppca_famix_finalize_host(n_comp = 1, scale = NULL) on the same buffers: noise, transform and mean
+    agree in every byte.  Random SPD S_j; where d > 2 column 1 is unobserved (all of its statistics zero) and S of column 2 is negated (the
+    old row is kept); with and without a noise floor; with the sq the statistics imply and with sq = 0, where the variance comes out
+    negative and the noise must stay as it was (or at its floor)."""
+    from ppca_rs_amd import _lib
+
+    rng = np.random.default_rng(100 * d + k)
+    ki = max(k, 1)  # (state size 0: the statistics of one zero column)
+    psi, c, mu = rng.uniform(0.2, 3.0, d), np.ascontiguousarray(rng.standard_normal((d, k))), rng.standard_normal(d)
+    g = rng.standard_normal((d, ki, ki + 2))
+    tot = rng.uniform(50.0, 90.0, d)
+    mom = [rng.standard_normal((d, ki)), tot[:, None, None] * (g @ g.transpose(0, 2, 1)) / (ki + 2), rng.standard_normal((d, ki)),
+           tot * rng.uniform(-1.0, 1.0, d), tot, None]  # (|delta| <= 1: the variance under sq_fit stays positive)
+    if d > 2:
+        for a in mom[:4]:
+            a[1] = 0.0
+        tot[1] = 0.0
+        mom[1][2] = -mom[1][2]
+    stats = _pack(mom)
+    assert stats.shape == (hiplib.ppca_stats_len(d, k),)
+    sq_fit = tot * rng.uniform(2.0, 5.0, d) + 4.0 * np.abs(mom[0]).sum(axis=1)
+    for sq in (sq_fit, np.zeros(d)):
+        for floor in (None, rng.uniform(0.1, 2.5, d)):
+            fa = np.empty(d), np.empty((d, k)), np.empty(d)
+            mix = np.empty(d), np.empty((1, d, k)), np.empty((1, d))
+            _lib.check(hiplib.ppca_fa_finalize_host(d, k, _lib.ptr(psi), _lib.ptr(c), _lib.ptr(mu), _lib.ptr(stats), _lib.ptr(sq),
+                                                    _lib.ptr(floor), *(_lib.ptr(o) for o in fa)))
+            _lib.check(hiplib.ppca_famix_finalize_host(d, k, 1, _lib.ptr(psi), _lib.ptr(c), _lib.ptr(mu), _lib.ptr(stats), _lib.ptr(sq), None,
+                                                       _lib.ptr(floor), *(_lib.ptr(o) for o in mix)))
+            for got, want in zip(fa, mix):
+                assert got.tobytes() == want.tobytes()
+            if d > 2:
+                assert np.array_equal(fa[1][2], c[2]) and np.array_equal(fa[1][1], c[1]) and fa[2][1] == mu[1]  # kept rows, unmoved mean
+                assert fa[0][1] == max(psi[1], 0.0 if floor is None else floor[1])
+            if sq is not sq_fit:
+                assert np.array_equal(fa[0], psi if floor is None else np.maximum(psi, floor))
+            elif floor is None:  # (the step did something; column 2, its S negated, may keep its noise)
+                moved = np.flatnonzero(tot > 0.0)
+                assert np.all(fa[0][moved[moved != 2]] != psi[moved[moved != 2]])
+
+
 def test_famix_finalize_host_scale_undoes_a_factor_on_a_component(hiplib, case):
     """Component c's statistics and sq multiplied by t with scale_c = 1 / t: the result does not move (1e-12)."""
     psi, cs, mus, moms, stats, sq, t = case
@@ -219,11 +264,17 @@ def test_famix_dump_load_and_pickle_round_trip():
     import ppca_rs_amd as p
 
     m = _mix()
+    m = p.FAMix(m.noise, m.transforms, np.where(m.means > 1.0, -0.0, m.means), m.log_weights)  # (a sign bit that == does not see)
+    fields = ("noise", "transforms", "means", "log_weights")
     for back in (p.FAMix.load(m.dump()), pickle.loads(pickle.dumps(m))):
         assert isinstance(back, p.FAMix)
-        assert all(np.array_equal(getattr(back, f), getattr(m, f)) for f in ("noise", "transforms", "means", "log_weights"))
-    with pytest.raises(Exception):
+        assert all(getattr(back, f).tobytes() == getattr(m, f).tobytes() and getattr(back, f).shape == getattr(m, f).shape for f in fields)
+    z = np.load(io.BytesIO(m.dump()), allow_pickle=False)
+    assert z.files == ["kind"] + list(fields) and str(z["kind"]) == "ppca_rs_amd.FAMix"
+    assert all(z[f].dtype == np.float64 and z[f].tobytes() == getattr(m, f).tobytes() for f in fields)
+    with pytest.raises(Exception) as err:
         p.FAMix.load(p.FAModel(np.ones(3), np.ones((3, 1)), np.zeros(3)).dump())  # another kind of container
+    assert type(err.value) is Exception and str(err.value) == "not an FAMix container: ppca_rs_amd.FAModel"
     with pytest.raises(Exception):
         p.FAMix.load(b"not a container")
 
@@ -254,3 +305,92 @@ def test_famix_whitened_components_and_canonical_form_keep_the_shapes():
     assert np.array_equal(fm.noise, np.full(7, 0.5)) and np.array_equal(fm.transforms, m.transforms) and np.array_equal(fm.log_weights, iso.log_weights)
     with pytest.raises(ValueError):
         p.FAMix.from_ppca_mix(p.PPCAMix([p.PPCAModel(0.5, m.transforms[0], m.means[0]), p.PPCAModel(0.6, m.transforms[1], m.means[1])], [0.0, 0.0]))
+
+
+# --------------------------------------------------------------------------- the loop of the five trainers
+class _StubDataset:
+    def __len__(self):
+        return 10
+
+    def column_stats(self):
+        return None, None, np.array([4.0, 9.0])
+
+
+class _StubModel:
+    """Records what a trainer calls; the llk of generation g is -50 (g + 1)."""
+    n_parameters = 7
+    _estimated = False
+
+    def __init__(self, calls, gen=0):
+        self.calls, self.gen = calls, gen
+
+    def _next(self, name, args):
+        self.calls.append((name,) + args)
+        return _StubModel(self.calls, self.gen + 1)
+
+    def iterate(self, dataset, *args):
+        return self._next("iterate", args)
+
+    def iterate_with_prior(self, dataset, *args):
+        return self._next("iterate_with_prior", args)
+
+    def iterate_with_llk(self, dataset, *args):
+        return self._next("iterate_with_llk", args), -50.0 * (self.gen + 1)
+
+    def to_canonical(self):
+        self.calls.append(("to_canonical",))
+        return self
+
+
+TRAINERS = [("PPCATrainer", "PPCA", dict(state_size=2)), ("PPCAMixTrainer", "PPCA mix", dict(n_models=2, state_size=2)),
+            ("FATrainer", "FA", dict(state_size=2)), ("FAMixTrainer", "FA mix", dict(n_models=2, state_size=2)),
+            ("TPPCATrainer", "t-PPCA", dict(state_size=2, estimate_dof=True))]
+
+
+@pytest.mark.parametrize("name,label,kwargs", TRAINERS)
+def test_trainer_prints_its_line_and_quiet_reads_no_llk(capsys, name, label, kwargs):
+    """Each trainer over a stub model and dataset (n = 10, 7 parameters, llk -50 then -100): the exact printed lines for every metric,
+    the extra argument each hands to its model's step (the prior; the floor ratio x the columns' standard deviation; estimate_dof), the
+    parameter TPPCATrainer counts for a dof that is about to be estimated, and with quiet=True `iterate` alone (`iterate_with_prior`
+    alone for the PPCA trainers given a prior), nothing printed."""
+    import ppca_rs_amd as p
+
+    trainer = getattr(p, name)(_StubDataset())
+    n_par = 8 if name == "TPPCATrainer" else 7
+    fa, ppca = name in ("FATrainer", "FAMixTrainer"), name in ("PPCATrainer", "PPCAMixTrainer")
+    extra = (None,) if ppca else (True,) if name == "TPPCATrainer" else None
+    want = {"llk": [-50.0 / 10, -100.0 / 10], "aic": [2.0 * (n_par + 50.0) / 10, 2.0 * (n_par + 100.0) / 10],
+            "bic": [(-50.0 - n_par * np.log(10)) / 10, (-100.0 - n_par * np.log(10)) / 10]}
+    assert want["llk"] == [-5.0, -10.0]
+    for metric in ("llk", "aic", "bic"):
+        calls = []
+        out = trainer.train(start=_StubModel(calls), n_iters=2, metric=metric, **kwargs)
+        assert out.gen == 2 and [c[0] for c in calls] == ["iterate_with_llk", "iterate_with_llk", "to_canonical"]
+        assert capsys.readouterr().out == "".join(f"Masked {label} iteration {i + 1}: {metric}={want[metric][i]}\n" for i in range(2))
+        if fa:
+            assert all(len(c) == 2 and np.array_equal(c[1], 1e-3 * np.array([2.0, 3.0])) for c in calls[:2])
+        else:
+            assert calls[:2] == [("iterate_with_llk",) + extra] * 2
+    assert capsys.readouterr().out == ""
+    calls = []
+    out = trainer.train(start=_StubModel(calls), n_iters=3, quiet=True, **kwargs)
+    assert out.gen == 3 and [c[0] for c in calls] == ["iterate"] * 3 + ["to_canonical"] and capsys.readouterr().out == ""
+    if fa:
+        assert all(np.array_equal(c[1], 1e-3 * np.array([2.0, 3.0])) for c in calls[:3])
+    else:
+        assert calls[:3] == [("iterate",) + (() if ppca else extra)] * 3
+    if ppca:
+        calls, prior = [], object()
+        trainer.train(start=_StubModel(calls), prior=prior, n_iters=2, quiet=True, **kwargs)
+        assert calls == [("iterate_with_prior", prior)] * 2 + [("to_canonical",)] and capsys.readouterr().out == ""
+        calls = []
+        trainer.train(start=_StubModel(calls), prior=prior, n_iters=1, **kwargs)
+        assert calls == [("iterate_with_llk", prior), ("to_canonical",)]
+        assert capsys.readouterr().out == f"Masked {label} iteration 1: aic={2.0 * (7 + 50.0) / 10}\n"
+    if name == "TPPCATrainer":  # a dof that is not estimated, or was estimated before: no extra parameter
+        trainer.train(start=_StubModel([]), n_iters=1, state_size=2)
+        assert capsys.readouterr().out == f"Masked t-PPCA iteration 1: aic={2.0 * (7 + 50.0) / 10}\n"
+        again = _StubModel([])
+        again._estimated = True
+        trainer.train(start=again, n_iters=1, **kwargs)
+        assert capsys.readouterr().out == f"Masked t-PPCA iteration 1: aic={2.0 * (7 + 50.0) / 10}\n"

@@ -2,6 +2,7 @@
 (tests/tppca_restatement.py), the restatement's own properties (its two forms of delta and ln det agree; the t log-likelihood never
 decreases; the t fit survives contamination that the Gaussian limit does not), and TPPCAModel's host-side surface."""
 import ctypes as C
+import io
 import math
 import os
 import pickle
@@ -183,8 +184,21 @@ def test_model_host_surface(P):
     for back in (P.TPPCAModel.load(m.dump()), pickle.loads(pickle.dumps(m))):
         assert back.dof == 4.0 and back.isotropic_noise == 0.5 and np.array_equal(back.transform, c) and np.array_equal(back.mean, mu)
         assert back.n_parameters == m.n_parameters
+    mu0 = np.where(mu > 0.5, -0.0, mu)  # (a sign bit that == does not see)
+    e = P.TPPCAModel(0.1 + 0.2, c, mu0, 1.0 / 3.0, _estimated_dof=True)
+    for back in (P.TPPCAModel.load(e.dump()), pickle.loads(pickle.dumps(e))):
+        assert isinstance(back, P.TPPCAModel) and back._estimated is True and (back.dof, back.isotropic_noise) == (1.0 / 3.0, 0.1 + 0.2)
+        assert back.transform.tobytes() == c.tobytes() and back.mean.tobytes() == mu0.tobytes() and back.transform.shape == c.shape
+    assert pickle.loads(pickle.dumps(m))._estimated is False
+    z = np.load(io.BytesIO(e.dump()), allow_pickle=False)
+    assert z.files == ["kind", "isotropic_noise", "transform", "mean", "dof", "estimated_dof"] and str(z["kind"]) == "ppca_rs_amd.TPPCAModel"
+    assert all(z[f].dtype == np.float64 for f in ("isotropic_noise", "transform", "mean", "dof")) and z["estimated_dof"].dtype == np.bool_
+    assert z["transform"].tobytes() == c.tobytes() and z["mean"].tobytes() == mu0.tobytes() and float(z["dof"]) == 1.0 / 3.0
     with pytest.raises(Exception):
         P.TPPCAModel.load(P.PPCAModel(0.5, c, mu).dump())
+    with pytest.raises(Exception) as err:
+        P.TPPCAModel.load(P.FAModel(np.ones(7), c, mu).dump())  # another of the library's own containers
+    assert type(err.value) is Exception and str(err.value) == "not a TPPCAModel container: ppca_rs_amd.FAModel"
 
 
 def test_dof_root_matches_the_restatement(P):
