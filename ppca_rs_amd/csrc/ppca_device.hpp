@@ -160,6 +160,11 @@ __device__ __forceinline__ void static_for(F &&f) {
     static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// Keeps a value -- and with it the load that produced it -- alive up to this point without doing anything with it: an empty
+// statement that names the register as an input.  (For loads issued only to bring lines nearer; place it where the wave's
+// vector-memory queue has drained past the load anyway, since the compiler waits for the value here.)
+__device__ __forceinline__ void keep_alive(unsigned v) { asm volatile("" ::"v"(v)); }
+
 __device__ __forceinline__ d4_t mfma(double a, double b, d4_t c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }

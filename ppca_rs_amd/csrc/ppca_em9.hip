@@ -84,6 +84,17 @@ constexpr int E9_FLUSH_GROUPS = 100;
 //  - the second digit pair {5,4} is requested with {7,6} during the previous tile's P4a.  On round 4's layout that only moved the
 //    wait (first half of the Gram 2.40 -> 2.12 k cycles per tile, b loop 2.70 -> 2.87 k: 100.7 against 100.8 it/s); on layout B,
 //    whose b loop waits for 16 instead of 48 loads, + 0.3 % (with nt row loads 104.2-104.4 against 103.2-103.4).
+//  - the Gram's digit pairs {3,2} and {1,0} (sixteen 1 KB loads per wave, wanted BEHIND the b loop) are requested one load per step
+//    of the b loop, behind the step's request for C, and no longer in two blocks of eight between the Gram halves in front of it.
+//    A wave has one in-order vmcnt: with the table queued in front, the loop's waits for its C operands -- vmcnt(4) from the fifth
+//    step on -- also waited for all sixteen table loads ~450 cycles after their issue.  Now the steady wait is vmcnt(9) and no wait
+//    for C covers a table load younger than four steps; the last table loads land under the int8 MFMAs behind the loop.  Five
+//    interleaved runs each: 106.0-106.1 against 104.1-104.3 EM it/s (two loads per step in steps 0-7: 105.6-105.8).  Measured in the
+//    same session and NOT kept: the next tile's pairs {7,6}, {5,4} requested behind P4a's row requests instead of in front of them
+//    (100.6-100.8 behind the loop, 98.8 two per k-step: the first Gram half then stands waiting for its pairs) and a touch of the
+//    rows of tile rel + 2 at the top of phase beta (one nt dword per 128-byte line through the tile's clamped descriptor: 94.1-94.2,
+//    the solver's loads and the column waves' trip grew from 0.26 / 2.5 k to 1.1 / 5.1 k cycles per tile);
+//    profiles/em9_load_order/README.md.
 //  - both roles run at the default wave priority, and a wave that polls a role barrier sleeps one s_sleep(1) per look.
 constexpr int E9_X_AUX = 2;  // cache policy of the row loads of X: nt (L2-served: the rows are read once and would only push the digit table and the
                              // third column group of C out of the 32 KB L1).  Measured on layout B, two rounds interleaved: 103.9-104.1 against
@@ -717,17 +728,18 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     i4_t qbA[2][4];
     i4_t qbB[2][4];  // digits {5,4} requested with {7,6} during the previous tile's P4a (round 5): requested at the top of P2 they
                      // were ~600 cycles old when the second digit pair wanted them -- an L2 round trip is longer
-    auto load_pair = [&](i4_t(&dst)[2][4], int sl0) {
+    // load i of the eight (digit u = i / 4, k-chunk kc = i % 4) of the digit pair {sl0 + 1, sl0}
+    auto load_pair_part = [&](i4_t(&dst)[2][4], int sl0, int i) {
         int qbase = wave * QS * 4 * 1024;
         asm volatile("" : "+s"(qbase));
+        const int u = i >> 2, kc = i & 3;
+        typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+        const u4_t v = __builtin_amdgcn_raw_buffer_load_b128(qrsrc, lane_entry * 16 + kc * 1024, qbase + (sl0 + u) * 4096, E9_Q_AUX);
+        dst[u][kc] = i4_t{(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
+    };
+    auto load_pair = [&](i4_t(&dst)[2][4], int sl0) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int kc = 0; kc < 4; ++kc) {
-                typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-                const u4_t v = __builtin_amdgcn_raw_buffer_load_b128(qrsrc, lane_entry * 16 + kc * 1024, qbase + (sl0 + u) * 4096, E9_Q_AUX);
-                dst[u][kc] = i4_t{(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
-            }
+        for (int i = 0; i < 8; ++i) load_pair_part(dst, sl0, i);
     };
     // ---- P1: one tile = RPW rows per front wave.  The finite-test ballots ARE the mask words (word 2 h + e of a row,
     // bit l <-> dim 128 h + 2 l + e; qprep orders the digit table to match); each lane also shifts its own bit of every
@@ -948,9 +960,7 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                             af[rt2][kc][u] = (int)((((bits >> (4 * u)) & 0xFu) * 0x00204081u) & 0x01010101u);
                     }
                 group(qbA, true);   // digits {7,6}: requested during the previous tile's P4a
-                load_pair(qbA, 2);
                 group(qbB, false);  // digits {5,4}
-                load_pair(qbB, 0);
             }
             E9_FINE(15)  // "-": mask bytes + digit pairs {7,6}, {5,4}
             {
@@ -969,6 +979,11 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
                 static_for<NQ>([&](auto q_tag) {
                     constexpr int q = decltype(q_tag)::value;
                     if constexpr (q + LAC < NQ) cload(std::integral_constant<int, q + LAC>{});
+                    // digit pairs {3,2} and {1,0}, wanted behind the loop: one of their sixteen loads per step, BEHIND the step's C
+                    // request, so that no wait for C covers a table load younger than LAC steps (both register sets are free)
+                    static_assert(NQ == 16, "one table load per step of the b loop");
+                    if constexpr (q < 8) load_pair_part(qbA, 2, q);
+                    else load_pair_part(qbB, 0, q - 8);
                     if constexpr (q + LAX < NQ) {
                         xload(std::integral_constant<int, q + LAX>{});
                         cload_lds(std::integral_constant<int, q + LAX>{});
