@@ -539,7 +539,7 @@ typedef struct ppca_generic_trace {
     int32_t valid;    /* 0 until a pass of this context has gone through the split pipeline */
     int32_t em;       /* 1 = EM statistics pass, 0 = output pass (llk, states, covariances, reconstructions) */
     int32_t fused16;  /* 1 = an EM pass handed on to the two-kernel pass of k = 11..16, d <= 256: nothing below is filled */
-    int32_t int8;     /* 1 = the int8-sliced contractions (0: PPCA_GENERIC_FP64=1 or its like pinned the fp64 products) */
+    int32_t int8;     /* 1 = the int8-sliced contractions (0: PPCA_GENERIC_FP64=1 pinned the fp64 products) */
     int32_t d, k, n_cu, chunks;
     int64_t n, chunk_rows; /* rows of the pass; rows of a full chunk */
     /* int8 GEMM launches, in launch order.  role: 0 = Gram, 1 = statistics product as ONE launch (nsplit > 1: cut along the samples),
@@ -558,7 +558,7 @@ typedef struct ppca_generic_trace {
     int32_t skinny_launches, skinny_nt, skinny_slices, skinny_gy;
     int64_t skinny_rps;
     /* per-sample solver of the FIRST chunk (the largest).  solver: 1 lane, 2 lane (one wave per SIMD, k >= 13), 3 batched blocked
-     * (solve4), 4 one sample per wave on the MFMA, 5 workgroup per matrix, 6 LDS broadcast, 7 register broadcast, 8 LDS resident;
+     * (solve4), 4 one sample per wave on the MFMA (k = 65 .. 128); 5 - 8 stood for solvers since retired and are not reused;
      * solver_nb: 16 x 16 blocks per side (3, 4) or k (1, 2); a workgroup takes solver_batch samples per iteration of its loop */
     int32_t solver, solver_nb, solver_launches;
     int64_t solver_grid, solver_batch, solver_rows;

@@ -1,22 +1,27 @@
-// ppca_generic.hip -- split pipeline for shapes the fused kernel does not cover
-// (d > 256 or k > 10, up to k = 64; BASELINE config 4: d = 1024, k = 64).
+// ppca_generic.hip -- split pipeline for the shapes the fused kernels do not cover: d > 256 or k > 10, up to k = GENERIC_MAX_K
+// (128).  BASELINE config 4: d = 1024, k = 64.  (The EM pass of 11 <= k <= 16, d <= 256 is handed on to ppca_em16.hip; every output
+// pass of those shapes runs here.)
 //
 // Same mathematics as pass_kernel (ppca_kernels.hip) and the same reference items
 // (ppca/src/ppca_model.rs:195-208 infer_one, :281-358 M-step sweeps, :142-149 llk), but
 // the k x k per-sample state no longer fits registers and the d x k(k+1)/2 statistics no
-// longer fit one workgroup, so the pass is cut into dense contractions over sample chunks:
-//   Q        = vech(c_j c_j^T)                      (d x k')            qtab_kernel
-//   G | b    = Mask . Q  |  X~ . C                  (chunk x (k'+k))    gemm_kernel  (fp64 MFMA)
-//   solve    : per sample, one wave: Cholesky in LDS, z, M^-1 -> w P, w z, llk   solve_kernel
-//   S, U, totals += Mask^T . [wP | wz | w]          (d x (k'+k+1))      gemm_kernel
-//   cross, sumx  += X~^T  . [wz | w]                (d x (k+1))         gemm_kernel
-// Chunk results are accumulated in chunk order (deterministic).  Correctness first: the
-// GEMM is a plain LDS-staged 64x64 tile kernel on v_mfma_f64_16x16x4_f64.
+// longer fit one workgroup, so the pass is cut into stages over chunks of samples (gen_chunk: ~1.5 GB of per-sample
+// workspace, at most 2^20 rows; k' = k(k+1)/2):
+//   per model  Q = vech(c_j c_j^T) (d x k'), its int8 digit planes and the Gram guard   qtab_kernel, gen_rmin_kernel, gen_qdigits_kernel
+//   prep       xx_i, m_i, the mask bytes in both orientations and b = X~ . C in ONE pass over the chunk's rows: gen_prep_kernel
+//              (k <= 64; beyond: rowstats_kernel, gen_maskbytes_kernel and gemm_kernel<1>, one pass each)
+//   G          = Mask . Q (chunk x k'), int8-sliced with exact integer accumulation: i8gemm_kernel
+//   solve      per sample: z, M^-1 -> w P, w z, llk.  k <= 16: one lane per sample (solve_lane_kernel); 17 .. 64: several samples
+//              per wave, blocked on the fp64 MFMA (ppca_solve4.hip); 65 .. 128: one sample per wave, blocked (solve_mfma_kernel<5..8>)
+//   S          += Mask^T . wP (d x k'): digit planes of the chunk's wP (gen_wdigits_*), then i8gemm_kernel
+//   U, totals, cross, sumx += Mask^T | X~^T . [wz | w] (d x (k+1)): skinny_xt_kernel (k + 1 <= 80; beyond: gemm_kernel<2>, <3>)
+//   outputs    reconstructions / covariance diagonals from the states: recon2_kernel (k <= 64), recon_kernel beyond
+// Both int8-sliced contractions sit behind dynamic-range guards decided on the device (per model for G, per chunk for S): the
+// fp64-MFMA product (gemm_kernel<0>, <2>) is enqueued behind each and returns at once unless the guard tripped;
+// PPCA_GENERIC_FP64=1 pins the fp64 products.  Chunk results are accumulated in chunk order (deterministic).
 #include <algorithm>
 #include <vector>
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
 #include "ppca_internal.hpp"
 #include "ppca_solve.hpp"
@@ -41,15 +46,6 @@ void trace_solver(int kind, int nb, int64_t grid, int64_t batch, int64_t rows) {
     t->solver = kind; t->solver_nb = nb; t->solver_grid = grid; t->solver_batch = batch; t->solver_rows = rows;
 }
 }  // namespace
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_g_impl(F &&f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for_g(F &&f) {
-    static_for_g_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 __device__ __forceinline__ double gwave_sum(double v) {
 #pragma unroll
@@ -861,7 +857,6 @@ struct I8GemmArgs {
     // side (j fastest), then the next row block, then the next K-slice.  ncb / nrb: column / row blocks of the product.
     int xcd_map;
     int ncb, nrb;
-    int tile_rows;     // 0: the launcher's choice; 128: the 128-row tile (two workgroups per CU)
 };
 
 // KB = bytes of K per staged step (64 or 128: whole 128-byte lines per row at 128); rows padded by 16 B in LDS.
@@ -1271,7 +1266,7 @@ __global__ __launch_bounds__(2 * TM, 2) void i8gemm_kernel(I8GemmArgs g) {  // t
     }
 }
 
-// ------------------------------------------------------------------ wave-level SPD tools (runtime k <= 64)
+// ------------------------------------------------------------------ wave-level SPD tools (runtime k <= 64): the finalisation's row systems
 // Matrix in LDS, row-major with leading dimension LD; lane r owns row r.  Plain (non-volatile) LDS
 // pointers so the inner loops can be unrolled and their loads batched; lanes exchange data through LDS
 // only at the explicit wave_sync() points (LDS operations of one wave execute in issue order; the fence
@@ -1332,113 +1327,10 @@ __device__ double wave_chol_solve(const double *Mw, int k, int LD, int lane, dou
     return v;
 }
 
-// Uw[a][c] = (M^-1)_{ac}; lane c owns column c (two triangular solves per column, lanes independent:
-// Mw is read-only here and each lane touches only its own column of Uw, so no wave_sync is needed).
-__device__ void wave_chol_inverse(const double *Mw, double *Uw, int k, int LD, int lane) {
-    const int c = lane < k ? lane : k - 1;
-    double *ucol = Uw + c;
-    for (int a = 0; a < k; ++a) {
-        double s0 = (a == c) ? 1.0 : 0.0, s1 = 0.0;
-        const double *mrow = Mw + a * LD;
-        int t = 0;
-#pragma unroll 4
-        for (; t + 2 <= a; t += 2) {  // two partial sums: shorter dependency chains
-            s0 -= mrow[t] * ucol[t * LD];
-            s1 -= mrow[t + 1] * ucol[(t + 1) * LD];
-        }
-        if (t < a) s0 -= mrow[t] * ucol[t * LD];
-        if (lane < k) ucol[a * LD] = (a >= c) ? (s0 + s1) * mrow[a] : 0.0;
-    }
-    for (int a = k - 1; a >= 0; --a) {
-        double s0 = ucol[a * LD], s1 = 0.0;
-        int t = a + 1;
-#pragma unroll 4
-        for (; t + 2 <= k; t += 2) {
-            s0 -= Mw[t * LD + a] * ucol[t * LD];
-            s1 -= Mw[(t + 1) * LD + a] * ucol[(t + 1) * LD];
-        }
-        if (t < k) s0 -= Mw[t * LD + a] * ucol[t * LD];
-        if (lane < k) ucol[a * LD] = (s0 + s1) * Mw[a * LD + a];
-    }
-}
-
-// ------------------------------------------------------------------ per-sample solve
-// (SolveArgs: ppca_solve.hpp)
-
-__global__ __launch_bounds__(128) void solve_kernel(SolveArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double gsm[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int k = a.k, kp = k * (k + 1) / 2, LD = k | 1;
-    double *Mw = gsm + (size_t)wave * (2 * k * LD + 64);
-    double *Uw = Mw + k * LD;
-    double *zw = Uw + k * LD;
-    const double s2 = a.model[1], lnsig = a.model[2];
-    const int64_t stride = (int64_t)gridDim.x * 2;
-    for (int64_t i = (int64_t)blockIdx.x * 2 + wave; i < a.n; i += stride) {
-        double *g = a.G + i * kp;
-        double *bz = a.Bz + i * (k + 1);
-        wave_sync();  // previous sample's reads of Mw/Uw/zw are done
-        for (int e = lane; e < kp; e += 64) {
-            int r = 0;
-            while ((r + 1) * (r + 2) / 2 <= e) ++r;
-            int c = e - r * (r + 1) / 2;
-            Mw[r * LD + c] = g[e] + (r == c ? s2 : 0.0);
-        }
-        const double bv = lane < k ? bz[lane] : 0.0;
-        double logdet, quad;
-        wave_cholesky(Mw, k, LD, lane, logdet);
-        const double z = wave_chol_solve(Mw, k, LD, lane, bv, quad);
-        if (lane < k) zw[lane] = z;
-        const double zz = gwave_sum(lane < k ? z * z : 0.0);
-        wave_chol_inverse(Mw, Uw, k, LD, lane);
-        wave_sync();  // zw and Uw columns are read across lanes below
-        const double tr = gwave_sum(lane < k ? Uw[lane * LD + lane] : 0.0);
-        const double wgt = a.w ? a.w[i] : 1.0;
-        const double xx = a.xx[i];
-        const int m = (int)a.mc[i];
-        const double lk = sample_llk(xx, quad, logdet, s2, lnsig, m, k);
-        if (a.em) {
-            // w P = w (z z^T + s2 M^-1), packed; lane c writes column c of every row a >= c
-            if (lane < k) {
-                for (int r = lane; r < k; ++r) g[r * (r + 1) / 2 + lane] = wgt * (zw[r] * z + s2 * Uw[r * LD + lane]);
-                bz[lane] = wgt * z;
-            }
-            if (lane == 0) {
-                bz[k] = wgt;
-                double *sc = a.sc + i * 4;
-                sc[0] = m > 0 ? wgt * s2 * ((double)k - s2 * tr) : 0.0;
-                sc[1] = m > 0 ? wgt * (xx - quad - s2 * zz) : 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = m > 0 ? 1.0 : 0.0;
-            }
-        } else {
-            if (lane < k) {
-                bz[lane] = z;  // unweighted state for the reconstruction pass
-                if (a.states) a.states[i * k + lane] = z;
-                for (int r = 0; r < k; ++r) {
-                    const double sv = s2 * Uw[r * LD + lane];
-                    if (a.covs) a.covs[(i * k + r) * k + lane] = sv;
-                    if (r >= lane) g[r * (r + 1) / 2 + lane] = sv;  // Sigma packed, for covariance diagonals
-                }
-            }
-            if (lane == 0) {
-                double *sc = a.sc + i * 4;
-                sc[0] = 0.0;
-                sc[1] = 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = 0.0;
-                if (a.llks) a.llks[i] = lk;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------ state sizes 65 .. GENERIC_MAX_K (round 5): one WORKGROUP per matrix
-// The reference bounds the state size nowhere (ppca_model.rs:51-70, output_covariance.rs:57-70); rounds 1-4 refused k > 64 (a
-// wave's 64 lanes owned the rows of M).  A correct path without a performance claim: 256 threads, thread r < k owns row r of
-// M in LDS (k x (k | 1) doubles: 132 KB at k = 128), __syncthreads() where the wave forms have wave_sync().  The Cholesky
-// factor is inverted IN PLACE (row r of T = L^-1 from rows < r of T and row r of L), and M^-1 = T^T T is formed entry by entry
-// on the way out, so one matrix is all the LDS the solve needs.  Same I/O contract as solve_kernel.
+// ------------------------------------------------------------------ workgroup-level SPD tools (k = 65 .. GENERIC_MAX_K): the finalisation's row systems
+// Beyond k = 64 a wave's lanes no longer own the rows of the matrix: 256 threads, thread r < k owns row r of M in LDS
+// (k x (k | 1) doubles: 132 KB at k = 128), __syncthreads() where the wave forms have wave_sync().  Correct, no performance claim:
+// the M-step solves d systems, not one per sample.
 __device__ bool blk_cholesky(double *M, int k, int LD, int tid, double &logdet) {
     bool ok = true;
     double mant = 1.0;
@@ -1495,110 +1387,7 @@ __device__ double blk_chol_solve(const double *M, int k, int LD, int tid, double
     __syncthreads();
     return quad;
 }
-// L (strict lower triangle, 1 / L_pp on the diagonal) -> T = L^-1 in place
-__device__ void blk_tri_inverse(double *M, int k, int LD, int tid) {
-    for (int r = 1; r < k; ++r) {
-        double v = 0.0;
-        if (tid < r) {
-            double s0 = 0.0;
-            for (int t = tid; t < r; ++t) s0 += M[r * LD + t] * (t == tid ? M[t * LD + t] : M[t * LD + tid]);
-            v = -s0 * M[r * LD + r];
-        }
-        __syncthreads();  // everyone has read row r of L
-        if (tid < r) M[r * LD + tid] = v;
-        __syncthreads();
-    }
-}
-__device__ __forceinline__ double blk_sum(double v, double *red, int tid) {
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    return red[0];
-}
-__global__ __launch_bounds__(256) void solve_big_kernel(SolveArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double gsm[];
-    const int tid = threadIdx.x;
-    const int k = a.k, kp = k * (k + 1) / 2, LD = k | 1;
-    double *M = gsm, *vs = M + (size_t)k * LD, *zs = vs + k, *red = zs + k;
-    const double s2 = a.model[1], lnsig = a.model[2];
-    for (int64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
-        double *g = a.G + i * kp;
-        double *bz = a.Bz + i * (k + 1);
-        __syncthreads();  // the previous sample's reads of M / vs / zs are done
-        for (int r = tid; r < k; r += 256)
-            for (int c = 0; c <= r; ++c) M[r * LD + c] = g[r * (r + 1) / 2 + c] + (r == c ? s2 : 0.0);
-        if (tid < k) vs[tid] = bz[tid];
-        double logdet;
-        blk_cholesky(M, k, LD, tid, logdet);
-        const double quad = blk_chol_solve(M, k, LD, tid, vs, red);
-        const double z = tid < k ? vs[tid] : 0.0;
-        if (tid < k) zs[tid] = z;
-        const double zz = blk_sum(z * z, red, tid);
-        blk_tri_inverse(M, k, LD, tid);
-        // (M^-1)_rc = sum_{t >= r} T_tr T_tc for r >= c; the diagonal first, for the trace
-        double trp = 0.0;
-        if (tid < k) {
-            double s0 = 0.0;
-            for (int t = tid; t < k; ++t) s0 += M[t * LD + tid] * M[t * LD + tid];
-            trp = s0;
-        }
-        const double tr = blk_sum(trp, red, tid);
-        const double wgt = a.w ? a.w[i] : 1.0;
-        const double xx = a.xx[i];
-        const int m = (int)a.mc[i];
-        const double lk = sample_llk(xx, quad, logdet, s2, lnsig, m, k);
-        for (int e = tid; e < kp; e += 256) {
-            int r = 0;
-            while ((r + 1) * (r + 2) / 2 <= e) ++r;
-            const int c = e - r * (r + 1) / 2;
-            double s0 = 0.0;
-            for (int t = r; t < k; ++t) s0 += M[t * LD + r] * M[t * LD + c];
-            if (a.em) {
-                g[e] = wgt * (zs[r] * zs[c] + s2 * s0);  // w P = w (z z^T + s2 M^-1), packed
-            } else {
-                const double sv = s2 * s0;
-                g[e] = sv;  // Sigma packed, for the covariance diagonals
-                if (a.covs) {
-                    a.covs[(i * k + r) * k + c] = sv;
-                    a.covs[(i * k + c) * k + r] = sv;
-                }
-            }
-        }
-        if (tid < k) {
-            bz[tid] = a.em ? wgt * z : z;
-            if (!a.em && a.states) a.states[i * k + tid] = z;
-        }
-        if (tid == 0) {
-            double *sc = a.sc + i * 4;
-            if (a.em) {
-                bz[k] = wgt;
-                sc[0] = m > 0 ? wgt * s2 * ((double)k - s2 * tr) : 0.0;
-                sc[1] = m > 0 ? wgt * (xx - quad - s2 * zz) : 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = m > 0 ? 1.0 : 0.0;
-            } else {
-                sc[0] = 0.0;
-                sc[1] = 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = 0.0;
-                if (a.llks) a.llks[i] = lk;
-            }
-        }
-    }
-}
 static size_t solve_big_lds(int k) { return sizeof(double) * ((size_t)k * (k | 1) + 2 * (size_t)k + 256); }
-static hipError_t launch_solve_big(const SolveArgs &a, int n_cu, hipStream_t s) {
-    const size_t lds = solve_big_lds(a.k);
-    if (hipError_t e = ensure_dynamic_lds<solve_big_kernel>(lds); e != hipSuccess) return e;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(a.n, (int64_t)n_cu));
-    trace_solver(5, a.k, grid, 1, a.n);
-    hipLaunchKernelGGL(solve_big_kernel, dim3(grid), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
 // finalisation's row systems at k > 64: one workgroup per dimension
 __global__ __launch_bounds__(256) void gen_rowsolve_big_kernel(const double *stats, const double *min, double *mout, int d, int k, double tau) {
     extern __shared__ __attribute__((aligned(16))) double gsm[];
@@ -1623,10 +1412,11 @@ __global__ __launch_bounds__(256) void gen_rowsolve_big_kernel(const double *sta
 }
 
 // ------------------------------------------------------------------ per-sample solve, one LANE per sample (k <= 16)
-// The blocked / broadcast solvers below give a whole wave to one sample: right at k = 64, a 70-fold waste at k = 11
-// (13 k cycles per sample and wave: 6.4 ms of a 16 ms chunk one step outside the fused kernel).  Up to k = 16 the
+// (SolveArgs: ppca_solve.hpp)
+// The blocked solvers give a wave to one or a few samples: right at k = 64, a 70-fold waste at k = 11 (13 k cycles per sample
+// and wave: 6.4 ms of a 16 ms chunk one step outside the fused kernel).  Up to k = 16 the
 // packed Cholesky factor (136 doubles) fits a lane's registers, so the fused kernel's per-sample code (Posterior<K>,
-// ppca_small.hpp) runs here as it does there: 64 samples per wave instruction.  Same I/O contract as solve_kernel.
+// ppca_small.hpp) runs here as it does there: 64 samples per wave instruction.
 template <int K, bool EM>
 __device__ __forceinline__ void solve_lane_body(const SolveArgs &a) {
     constexpr int KP = K * (K + 1) / 2;
@@ -1710,342 +1500,18 @@ static hipError_t launch_solve_lane(const SolveArgs &a, int n_cu, hipStream_t s)
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------ register-resident per-sample solve
-// One wave per sample, no LDS: lane r keeps row r of M = G + s2 I (padded to KPAD with an identity block)
-// in registers, lane c keeps column c of M^-1.  Every quantity the lanes share -- pivots, the L_cp of the
-// trailing update, the L_at of the triangular solves, b_a, z_a -- is wave-uniform and is broadcast with
-// v_readlane into a scalar operand of the FMA, so the O(k^3) loops are straight-line register code.
-template <int KPAD>
-__global__ __launch_bounds__(256) void solve_reg_kernel(SolveArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int k = a.k, kp = k * (k + 1) / 2;
-    const double s2 = a.model[1], lnsig = a.model[2];
-    auto bcast = [&](double v, int src) {
-        const long long b = __double_as_longlong(v);
-        const int lo = __builtin_amdgcn_readlane((int)b, src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-        return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < a.n; i += stride) {
-        double *g = a.G + i * kp;
-        double *bz = a.Bz + i * (k + 1);
-        const bool live = lane < k;
-        double row[KPAD];
-        {
-            const double *grow = g + (live ? lane * (lane + 1) / 2 : 0);
-#pragma unroll
-            for (int t = 0; t < KPAD; ++t) {
-                double v = (t == lane) ? 1.0 : 0.0;            // identity padding
-                if (live && t <= lane) v = grow[t] + (t == lane ? s2 : 0.0);
-                row[t] = v;                                      // entries above the diagonal are never read
-            }
-        }
-        const double bv = live ? bz[lane] : 0.0;
-        // Cholesky, right-looking; diagonal slots keep 1 / L_pp
-        double mant = 1.0;
-        int ex = 0;
-#pragma unroll
-        for (int p = 0; p < KPAD; ++p) {
-            const double piv = bcast(row[p], p);
-            const double rinv = 1.0 / sqrt(piv);
-            int e;
-            mant *= frexp(piv, &e);
-            ex += e;
-            row[p] = (lane == p) ? rinv : row[p] * rinv;
-#pragma unroll
-            for (int c = p + 1; c < KPAD; ++c) row[c] -= row[p] * bcast(row[p], c);  // lanes < c touch unused slots
-        }
-        const double logdet = log(mant) + (double)ex * LN_2;
-        // column `lane` of M^-1: L u = e_lane, L^T x = u; L_at is uniform -> scalar operand
-        double u[KPAD];
-#pragma unroll
-        for (int r = 0; r < KPAD; ++r) {
-            double sacc = (r == lane) ? 1.0 : 0.0;
-#pragma unroll
-            for (int t = 0; t < r; ++t) sacc -= bcast(row[t], r) * u[t];
-            u[r] = sacc * bcast(row[r], r);
-        }
-#pragma unroll
-        for (int r = KPAD - 1; r >= 0; --r) {
-            double sacc = u[r];
-#pragma unroll
-            for (int t = r + 1; t < KPAD; ++t) sacc -= bcast(row[r], t) * u[t];
-            u[r] = sacc * bcast(row[r], r);
-        }
-        // z_c = sum_a (M^-1)_{ac} b_a (symmetry: lane c holds column c), quad = b^T z
-        double z = 0.0, diag = 0.0;
-#pragma unroll
-        for (int r = 0; r < KPAD; ++r) {
-            z += u[r] * bcast(bv, r);
-            diag = (r == lane) ? u[r] : diag;
-        }
-        const double quad = gwave_sum(live ? bv * z : 0.0);
-        const double zz = gwave_sum(live ? z * z : 0.0);
-        const double tr = gwave_sum(live ? diag : 0.0);
-        const double wgt = a.w ? a.w[i] : 1.0;
-        const double xx = a.xx[i];
-        const int m = (int)a.mc[i];
-        const double lk = sample_llk(xx, quad, logdet, s2, lnsig, m, k);
-        if (a.em) {
-#pragma unroll
-            for (int r = 0; r < KPAD; ++r) {
-                const double zr = bcast(z, r);
-                if (live && r >= lane && r < k) g[r * (r + 1) / 2 + lane] = wgt * (zr * z + s2 * u[r]);
-            }
-            if (live) bz[lane] = wgt * z;
-            if (lane == 0) {
-                bz[k] = wgt;
-                double *sc = a.sc + i * 4;
-                sc[0] = m > 0 ? wgt * s2 * ((double)k - s2 * tr) : 0.0;
-                sc[1] = m > 0 ? wgt * (xx - quad - s2 * zz) : 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = m > 0 ? 1.0 : 0.0;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < KPAD; ++r) {
-                const double sv = s2 * u[r];
-                if (live && r < k) {
-                    if (a.covs) a.covs[(i * k + r) * k + lane] = sv;
-                    if (r >= lane) g[r * (r + 1) / 2 + lane] = sv;  // Sigma packed, for covariance diagonals
-                }
-            }
-            if (live) {
-                bz[lane] = z;  // unweighted state for the reconstruction pass
-                if (a.states) a.states[i * k + lane] = z;
-            }
-            if (lane == 0) {
-                double *sc = a.sc + i * 4;
-                sc[0] = 0.0;
-                sc[1] = 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = 0.0;
-                if (a.llks) a.llks[i] = lk;
-            }
-        }
-    }
-}
-
-
-// ------------------------------------------------------------------ per-sample solve, LDS-broadcast form
-// As solve_reg_kernel (lane r keeps row r of M in registers, lane c column c of M^-1), but the wave-uniform operand
-// of every multiply-add -- L_cp in the trailing update, L_rt in the triangular solves -- comes from ONE uniform LDS
-// read (all lanes, same address: a broadcast) of the factor the lanes publish column by column, instead of two
-// v_readlane + the SGPR hazard wait per operand: the O(k^3) loops become "ds_read + v_fma" pairs that the LDS pipe
-// and the fp64 pipe run side by side.  A wave's LDS operations execute in order, so a column is readable right after
-// it is stored; no barrier.
-// op i of a flattened column-oriented substitution on a KxK factor: unknown t scaled (r == t) or unknown r updated
-// with unknown t; (lt, lr) = where its factor entry lives in Lm
-struct SubOp {
-    int t, r, lt, lr;
-};
-__host__ __device__ constexpr SubOp sub_op(int K, int i, bool fwd) {
-    if (fwd) {
-        int t = 0;
-        while (i >= K - t) {  // column t has 1 + (K - 1 - t) ops
-            i -= K - t;
-            ++t;
-        }
-        return SubOp{t, t + i, t, t + i};
-    }
-    int t = K - 1;
-    while (i >= 1 + t) {  // column t has 1 + t ops
-        i -= 1 + t;
-        --t;
-    }
-    if (i == 0) return SubOp{t, t, t, t};
-    return SubOp{t, i - 1, i - 1, t};
-}
-
-template <int KPAD>
-__global__ __launch_bounds__(256) void solve_bc_kernel(SolveArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double gsm[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *Lm = gsm + (size_t)wave * KPAD * KPAD;  // Lm[p][r] = L_rp (p <= r); Lm[p][p] = 1 / L_pp
-    const int k = a.k, kp = k * (k + 1) / 2;
-    const double s2 = a.model[1], lnsig = a.model[2];
-    auto bcast = [&](double v, int src) {
-        const long long b = __double_as_longlong(v);
-        const int lo = __builtin_amdgcn_readlane((int)b, src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-        return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < a.n; i += stride) {
-        double *g = a.G + i * kp;
-        double *bz = a.Bz + i * (k + 1);
-        const bool live = lane < k;
-        double row[KPAD];
-        {
-            const double *grow = g + (live ? lane * (lane + 1) / 2 : 0);
-#pragma unroll
-            for (int t = 0; t < KPAD; ++t) {
-                double v = (t == lane) ? 1.0 : 0.0;            // identity padding
-                if (live && t <= lane) v = grow[t] + (t == lane ? s2 : 0.0);
-                row[t] = v;
-            }
-        }
-        const double bv = live ? bz[lane] : 0.0;
-        double mant = 1.0;
-        int ex = 0;
-        constexpr int CH = 8;
-        static_for_g<KPAD>([&](auto p_tag) {
-            constexpr int p = decltype(p_tag)::value;
-            const double piv = bcast(row[p], p);
-            const double rinv = 1.0 / sqrt(piv);
-            int e;
-            mant *= frexp(piv, &e);
-            ex += e;
-            row[p] = (lane == p) ? rinv : row[p] * rinv;
-            if (lane < KPAD) Lm[p * KPAD + lane] = row[p];
-            // row[c] -= L_lane,p * L_cp for c > p (lanes < c touch unused slots); the uniform operands arrive in groups
-            // of CH, the next group requested before the current one is consumed (fenced: hipcc otherwise hoists
-            // every read of the kernel to the top and spills them)
-            constexpr int NC = KPAD - 1 - p;
-            if constexpr (NC > 0) {
-                constexpr int NGC = (NC + CH - 1) / CH;
-                double bc[3][CH];
-                auto request = [&](auto g_tag) {
-                    constexpr int g = decltype(g_tag)::value;
-#pragma unroll
-                    for (int q = 0; q < CH; ++q) {
-                        const int o = g * CH + q;
-                        bc[g % 3][q] = Lm[p * KPAD + p + 1 + (o < NC ? o : NC - 1)];
-                    }
-                };
-                request(std::integral_constant<int, 0>{});
-                if constexpr (NGC > 1) request(std::integral_constant<int, 1>{});
-                static_for_g<NGC>([&](auto g_tag) {
-                    constexpr int g = decltype(g_tag)::value;
-                    if constexpr (g + 2 < NGC) request(std::integral_constant<int, g + 2>{});
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int q = 0; q < CH; ++q) {
-                        const int o = g * CH + q;
-                        if (o < NC) row[p + 1 + o] -= row[p] * bc[g % 3][q];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-            }
-        });
-        const double logdet = log(mant) + (double)ex * LN_2;
-        // column `lane` of M^-1: L u = e_lane, then L^T x = u
-        // column-oriented substitutions (once an unknown is final, the updates of all the others are independent),
-        // each flattened into ONE stream of (uniform LDS operand, multiply-add) pairs -- the factor is static by now, so
-        // the operand requests run a fixed distance (two groups of GP) ahead of their use across column boundaries:
-        //   forward:  for t = 0 ..:      u_t *= 1/L_tt;  u_r -= L_rt u_t  (r > t)     operands Lm[t][t], Lm[t][r]
-        //   backward: for t = K-1 .. 0:  u_t *= 1/L_tt;  u_r -= L_tr u_t  (r < t)     operands Lm[t][t], Lm[r][t]
-        double u[KPAD];
-#pragma unroll
-        for (int r = 0; r < KPAD; ++r) u[r] = (r == lane) ? 1.0 : 0.0;
-        constexpr int NOPS = KPAD + KPAD * (KPAD - 1) / 2, GP = 8, NG = (NOPS + GP - 1) / GP;
-        auto stream = [&](auto fwd_tag) {
-            constexpr bool FWD = decltype(fwd_tag)::value;
-            double ring[3][GP];
-            auto request = [&](auto g_tag) {
-                constexpr int g = decltype(g_tag)::value;
-                static_for_g<GP>([&](auto q_tag) {
-                    constexpr int i = g * GP + decltype(q_tag)::value;
-                    constexpr SubOp op = sub_op(KPAD, i < NOPS ? i : NOPS - 1, FWD);
-                    ring[g % 3][decltype(q_tag)::value] = Lm[op.lt * KPAD + op.lr];
-                });
-            };
-            request(std::integral_constant<int, 0>{});
-            if constexpr (NG > 1) request(std::integral_constant<int, 1>{});
-            static_for_g<NG>([&](auto g_tag) {
-                constexpr int g = decltype(g_tag)::value;
-                if constexpr (g + 2 < NG) request(std::integral_constant<int, g + 2>{});
-                __builtin_amdgcn_sched_barrier(0);
-                static_for_g<GP>([&](auto q_tag) {
-                    constexpr int i = g * GP + decltype(q_tag)::value;
-                    if constexpr (i < NOPS) {
-                        constexpr SubOp op = sub_op(KPAD, i, FWD);
-                        const double v = ring[g % 3][decltype(q_tag)::value];
-                        if constexpr (op.r == op.t) u[op.t] *= v;
-                        else u[op.r] -= v * u[op.t];
-                    }
-                });
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        };
-        stream(std::true_type{});
-        stream(std::false_type{});
-        double z = 0.0, diag = 0.0;
-#pragma unroll
-        for (int r = 0; r < KPAD; ++r) {
-            z += u[r] * bcast(bv, r);
-            diag = (r == lane) ? u[r] : diag;
-        }
-        const double quad = gwave_sum(live ? bv * z : 0.0);
-        const double zz = gwave_sum(live ? z * z : 0.0);
-        const double tr = gwave_sum(live ? diag : 0.0);
-        const double wgt = a.w ? a.w[i] : 1.0;
-        const double xx = a.xx[i];
-        const int m = (int)a.mc[i];
-        const double lk = sample_llk(xx, quad, logdet, s2, lnsig, m, k);
-        if (a.em) {
-#pragma unroll
-            for (int r = 0; r < KPAD; ++r) {
-                const double zr = bcast(z, r);
-                if (live && r >= lane && r < k) g[r * (r + 1) / 2 + lane] = wgt * (zr * z + s2 * u[r]);
-            }
-            if (live) bz[lane] = wgt * z;
-            if (lane == 0) {
-                bz[k] = wgt;
-                double *sc = a.sc + i * 4;
-                sc[0] = m > 0 ? wgt * s2 * ((double)k - s2 * tr) : 0.0;
-                sc[1] = m > 0 ? wgt * (xx - quad - s2 * zz) : 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = m > 0 ? 1.0 : 0.0;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < KPAD; ++r) {
-                const double sv = s2 * u[r];
-                if (live && r < k) {
-                    if (a.covs) a.covs[(i * k + r) * k + lane] = sv;
-                    if (r >= lane) g[r * (r + 1) / 2 + lane] = sv;
-                }
-            }
-            if (live) {
-                bz[lane] = z;
-                if (a.states) a.states[i * k + lane] = z;
-            }
-            if (lane == 0) {
-                double *sc = a.sc + i * 4;
-                sc[0] = 0.0;
-                sc[1] = 0.0;
-                sc[2] = wgt * lk;
-                sc[3] = 0.0;
-                if (a.llks) a.llks[i] = lk;
-            }
-        }
-    }
-}
-
-template <int KPAD>
-static hipError_t launch_solve_bc(const SolveArgs &a, int grid, hipStream_t s) {
-    const size_t lds = sizeof(double) * 4 * KPAD * KPAD;
-    if (hipError_t e = lds > 65536 ? ensure_dynamic_lds<solve_bc_kernel<KPAD>>(lds) : hipSuccess; e != hipSuccess) return e;
-    trace_solver(6, KPAD / 16, grid, 4, a.n);
-    hipLaunchKernelGGL((solve_bc_kernel<KPAD>), dim3(grid), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-
-
-// ------------------------------------------------------------------ per-sample solve on the fp64 MFMA (blocked)
+// ------------------------------------------------------------------ per-sample solve on the fp64 MFMA (blocked), k = 65 .. 128
 // One wave per sample, M = G + s2 I (padded with an identity block to n = 16 NB) in the wave's LDS area, inverted IN
 // PLACE by the three classical blocked sweeps over 16 x 16 blocks -- every block product is four v_mfma_f64_16x16x4:
 //   potrf   for j: L_jj = chol(A_jj), T_jj = L_jj^-1 (kept in the diagonal block); L_ij = A_ij T_jj^T (i > j);
 //           A_il -= L_ij L_lj^T (j < l <= i)
 //   trtri   W = L^-1: for j descending, i descending: W_ij = -(sum_{t=j+1..i} W_it L_tj) T_jj      (W_ii = T_ii)
 //   lauum   M^-1 = W^T W: for i, for l <= i (l = i last): R_il = sum_{t >= i} W_ti^T W_tl
-// 52 block products at NB = 4 (13 k MFMA cycles) against ~6 k dependent v_readlane / LDS-broadcast multiply-adds per
-// sample of the lane-per-row forms above.  The 16 x 16 diagonal blocks are factored and inverted by the lanes
-// themselves (lane = row, four redundant copies, uniform LDS reads for the shared operands).  Outputs leave through
-// the packed index (coalesced), z = M^-1 b by symmetric row reads.
-// (round 6) NB = 5 .. 8: state sizes 65 .. 128 (the reference bounds k nowhere, ppca_model.rs:51-70).  Round 5 gave them one
-// WORKGROUP per matrix with a __syncthreads() per column (solve_big_kernel: 1.2 s per million systems at k = 65); the blocked form
-// needs nothing but LDS -- 36 KB (NB = 5) to 76 KB (NB = 8: blocks unpadded) per sample, so 4 / 3 / 2 / 2 waves per CU.
+// The 16 x 16 diagonal blocks are factored and inverted by the lanes themselves (lane = row, four redundant copies, uniform
+// LDS reads for the shared operands).  Outputs leave through the packed index (coalesced), z = M^-1 b by symmetric row reads.
+// NB = 5 .. 8 (the reference bounds k nowhere, ppca_model.rs:51-70): the form needs nothing but LDS -- 36 KB (NB = 5) to 76 KB
+// (NB = 8: blocks unpadded) per sample, so 4 / 3 / 2 / 2 waves per CU.  The body is written for any NB; 17 <= k <= 64 is
+// ppca_solve4.hip's (several samples per wave), which is why no instantiation below 5 exists (solve_mfma_waves keeps their rows).
 constexpr int solve_ld(int nb) { return nb == 8 ? 16 : 18; }
 constexpr int solve_mfma_waves(int nb) { return nb <= 3 ? 4 : nb == 4 ? 3 : nb == 5 ? 4 : nb == 6 ? 3 : 2; }
 template <int NB>
@@ -2314,97 +1780,34 @@ template <int NB>
 __global__ __launch_bounds__(256) void solve_mfma_kernel(SolveArgs a) {
     solve_mfma_body<NB>(a);
 }
-// the same capped at 256 registers: two workgroups per CU, two waves per SIMD (the default)
-template <int NB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void solve_mfma_occ2_kernel(SolveArgs a) {
-    solve_mfma_body<NB>(a);
-}
 
 template <int NB>
 static hipError_t launch_solve_mfma(const SolveArgs &a, int n_cu, hipStream_t s) {
+    static_assert(NB >= 5 && NB <= 8, "k = 65 .. 128; smaller state sizes have the lane solver and ppca_solve4.hip");
     constexpr int N = 16 * NB, W = solve_mfma_waves(NB);
-    const size_t lds = sizeof(double) * W * (NB * (NB + 1) / 2 * 16 * solve_ld(NB) + 2 * N);
-    // PPCA_SOLVE_OCC2=0: one workgroup per CU with the whole register file (A/B runs; the form of rounds 2-3)
-    static const bool occ2 = NB <= 4 && [] {
-        const char *e = getenv("PPCA_SOLVE_OCC2");
-        return !(e && atoi(e) == 0);
-    }();
-    int grid = (int)std::min<int64_t>((a.n + W - 1) / W, (int64_t)n_cu * (occ2 ? 2 : 1));
+    const size_t lds = sizeof(double) * W * (NB * (NB + 1) / 2 * 16 * solve_ld(NB) + 2 * N);  // (> 64 KB at every NB here)
+    int grid = (int)std::min<int64_t>((a.n + W - 1) / W, (int64_t)n_cu);
     if (grid < 1) grid = 1;
     trace_solver(4, NB, grid, W, a.n);
-    if (lds > 65536) {
-        if (hipError_t e = ensure_dynamic_lds<solve_mfma_kernel<NB>>(lds); e != hipSuccess) return e;
-        if constexpr (NB <= 4) {
-            if (hipError_t e = ensure_dynamic_lds<solve_mfma_occ2_kernel<NB>>(lds); e != hipSuccess) return e;
-        }
-    }
-    if constexpr (NB <= 4) {
-        if (occ2) {
-            hipLaunchKernelGGL((solve_mfma_occ2_kernel<NB>), dim3(grid), dim3(64 * W), lds, s, a);
-            return hipGetLastError();
-        }
-    }
+    if (hipError_t e = ensure_dynamic_lds<solve_mfma_kernel<NB>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((solve_mfma_kernel<NB>), dim3(grid), dim3(64 * W), lds, s, a);
     return hipGetLastError();
 }
 static hipError_t launch_solve(const SolveArgs &a, int n_cu, hipStream_t s) {
-    if (a.k > 64) {
-        static const bool big = [] {  // PPCA_SOLVE_BIG=1: the workgroup-per-matrix solver of round 5 (A/B runs)
-            const char *e = getenv("PPCA_SOLVE_BIG");
-            return e && atoi(e) == 1;
-        }();
-        if (big) return launch_solve_big(a, n_cu, s);
-        if (a.k <= 80) return launch_solve_mfma<5>(a, n_cu, s);
-        if (a.k <= 96) return launch_solve_mfma<6>(a, n_cu, s);
-        if (a.k <= 112) return launch_solve_mfma<7>(a, n_cu, s);
-        return launch_solve_mfma<8>(a, n_cu, s);
-    }
-    int grid = (int)std::min<int64_t>((a.n + 3) / 4, (int64_t)n_cu);
-    if (grid < 1) grid = 1;
-    static const bool reg = [] {  // PPCA_GENERIC_REG_SOLVE=1: the v_readlane-broadcast form (A/B runs)
-        const char *e = getenv("PPCA_GENERIC_REG_SOLVE");
-        return e && atoi(e) == 1;
-    }();
-    static const int form = [] {  // PPCA_GENERIC_SOLVE = mfma (default) | bc (LDS-broadcast, lane per row)
-        const char *e = getenv("PPCA_GENERIC_SOLVE");
-        return (e && e[0] == 'b') ? 1 : 0;
-    }();
-    static const bool lane_ok = [] {  // PPCA_GENERIC_LANE_SOLVE=0: the wave-per-sample forms at every k (A/B runs)
-        const char *e = getenv("PPCA_GENERIC_LANE_SOLVE");
-        return !(e && atoi(e) == 0);
-    }();
-    if (lane_ok && a.k <= 16) {
-        switch (a.k) {
+    switch (a.k) {
 #define PPCA_LANE_CASE(KK) \
     case KK:               \
         return launch_solve_lane<KK>(a, n_cu, s);
-            PPCA_LANE_CASE(1) PPCA_LANE_CASE(2) PPCA_LANE_CASE(3) PPCA_LANE_CASE(4) PPCA_LANE_CASE(5) PPCA_LANE_CASE(6)
-            PPCA_LANE_CASE(7) PPCA_LANE_CASE(8) PPCA_LANE_CASE(9) PPCA_LANE_CASE(10) PPCA_LANE_CASE(11) PPCA_LANE_CASE(12)
-            PPCA_LANE_CASE(13) PPCA_LANE_CASE(14) PPCA_LANE_CASE(15) PPCA_LANE_CASE(16)
+        PPCA_LANE_CASE(1) PPCA_LANE_CASE(2) PPCA_LANE_CASE(3) PPCA_LANE_CASE(4) PPCA_LANE_CASE(5) PPCA_LANE_CASE(6)
+        PPCA_LANE_CASE(7) PPCA_LANE_CASE(8) PPCA_LANE_CASE(9) PPCA_LANE_CASE(10) PPCA_LANE_CASE(11) PPCA_LANE_CASE(12)
+        PPCA_LANE_CASE(13) PPCA_LANE_CASE(14) PPCA_LANE_CASE(15) PPCA_LANE_CASE(16)
 #undef PPCA_LANE_CASE
-        }
     }
-    static const bool batched = [] {  // PPCA_SOLVE4=0: one sample per wave (solve_mfma_body; the form of rounds 2-4, A/B runs)
-        const char *e = getenv("PPCA_SOLVE4");
-        return !(e && atoi(e) == 0);
-    }();
-    if (!reg && form == 0 && batched && solve4_covers(a.k)) return launch_solve4(a, n_cu, s);
-    if (!reg && form == 0) {
-        if (a.k <= 16) return launch_solve_mfma<1>(a, n_cu, s);
-        if (a.k <= 32) return launch_solve_mfma<2>(a, n_cu, s);
-        if (a.k <= 48) return launch_solve_mfma<3>(a, n_cu, s);
-        return launch_solve_mfma<4>(a, n_cu, s);
-    }
-    if (!reg) {
-        if (a.k <= 16) return launch_solve_bc<16>(a, grid, s);
-        if (a.k <= 32) return launch_solve_bc<32>(a, grid, s);
-        return launch_solve_bc<64>(a, grid, s);
-    }
-    trace_solver(7, (a.k + 15) / 16, grid, 4, a.n);
-    if (a.k <= 16) hipLaunchKernelGGL((solve_reg_kernel<16>), dim3(grid), dim3(256), 0, s, a);
-    else if (a.k <= 32) hipLaunchKernelGGL((solve_reg_kernel<32>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((solve_reg_kernel<64>), dim3(grid), dim3(256), 0, s, a);
-    return hipGetLastError();
+    if (solve4_covers(a.k)) return launch_solve4(a, n_cu, s);  // 17 .. 64
+    if (a.k <= 80) return launch_solve_mfma<5>(a, n_cu, s);
+    if (a.k <= 96) return launch_solve_mfma<6>(a, n_cu, s);
+    if (a.k <= 112) return launch_solve_mfma<7>(a, n_cu, s);
+    return launch_solve_mfma<8>(a, n_cu, s);
 }
 
 // strided column sum of sc[n][4] (+ sum of weights) into scal[8]; one block, deterministic
@@ -2482,8 +1885,8 @@ __global__ void recon_kernel(const double *X, int64_t ldx, int64_t n, int d, int
     out[idx] = o;
 }
 
-// The same outputs with the work laid out for the machine (round 3, late; recon_kernel above is kept for A/B runs,
-// PPCA_GENERIC_RECON=naive): a thread owns one DIMENSION (its row of C in registers, zero-padded to KPAD columns) and
+// The same outputs with the work laid out for the machine (round 3, late; recon_kernel above serves k > 64, where a row of C
+// no longer fits a thread's registers): a thread owns one DIMENSION (its row of C in registers, zero-padded to KPAD columns) and
 // walks the samples of its block; everything per sample -- the state z, the packed Sigma -- is wave-uniform and comes
 // through scalar loads, so an element costs its multiply-adds and one coalesced store (plus the load of x where the
 // mode looks at it: smooth does not).  The naive kernel re-read C, z and Sigma per ELEMENT and divided a 64-bit index:
@@ -2724,23 +2127,9 @@ static hipError_t launch_i8gemm_t(const I8GemmArgs &g, dim3 grid, hipStream_t s)
     return hipGetLastError();
 }
 
-// The 256-row tile also for the statistics product when it has >= 1024 rows (d >= 1024): its B operand -- the digit planes of wP,
-// 8 bytes per entry like the fp64 values they stand for -- is re-read once per row block, so half as many row blocks halve the
-// dominant operand traffic (config 4: 234.8 -> 222.6 ms).  PPCA_I8GEMM_S256=0: off.
-static bool i8gemm_s256() {
-    static const bool v = [] {
-        const char *e = getenv("PPCA_I8GEMM_S256");
-        return !(e && atoi(e) == 0);
-    }();
-    return v;
-}
 // role: what the product is, for the dispatch trace only (ppca_generic_trace::i8_role)
 static hipError_t launch_i8gemm(const I8GemmArgs &g, hipStream_t s, int role) {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
-    static const int tm = [] {  // PPCA_I8GEMM_TM=128: the 4-wave tile everywhere (A/B runs)
-        const char *e = getenv("PPCA_I8GEMM_TM");
-        return (e && atoi(e) == 128) ? 128 : 256;
-    }();
     static const bool nobuf = [] {  // PPCA_I8GEMM_PTR=1: operands by pointer arithmetic (A/B runs; the form for >= 2 GiB)
         const char *e = getenv("PPCA_I8GEMM_PTR");
         return e && atoi(e) == 1;
@@ -2749,25 +2138,23 @@ static hipError_t launch_i8gemm(const I8GemmArgs &g, hipStream_t s, int role) {
     const bool buf = !nobuf && g.K % 64 == 0 && (g.ksplit % 64) == 0 && g.M * g.lda < (int64_t(1) << 31) &&
                      GQS * g.plane < (int64_t(1) << 31);
     hipError_t e;
-    const bool s256 = i8gemm_s256();
-    // XCD-aware tile order (round 5; PPCA_I8GEMM_XCD=0: the plain 2-D order of rounds 1-4).  Measured at config 4's shape
+    I8GemmArgs h = g;
+    // The 256-row tile (one workgroup per CU) from 1024 rows on: a chunk's Gram (one row per sample), and the statistics product
+    // at d >= 1024: its B operand -- the digit planes of wP, 8 bytes per entry like the fp64 values they stand for -- is re-read
+    // once per row block, so half as many row blocks halve the dominant operand traffic (config 4: 234.8 -> 222.6 ms).
+    const bool tall = g.M >= 1024;
+    const int tmr = tall ? 256 : 128;
+    h.ncb = (int)((g.N + 31) / 32);
+    h.nrb = (int)((g.M + tmr - 1) / tmr);
+    const int nz = g.ksplit > 0 ? g.nsplit : 1;
+    // XCD-aware tile order (round 5; before: the plain 2-D order).  Measured at config 4's shape
     // (profiles/r05/traffic_cfg4*.json): in the plain order the statistics product fetched its B stripes -- the digit planes of
     // wP, 1.45 GB per chunk -- once per ROW BLOCK, because the four row blocks of a column block (linear ids x, x + 65, x + 130,
     // x + 195) land on four different XCDs, i.e. four L2s: 190 KB of fabric traffic per sample and EM step in this kernel, 65 KB
     // in the XCD-aware order (the whole pipeline: 304 -> 179 KB per sample).  The launch itself gains only 5 % (1.94 -> 1.84 ms: its
     // K loop is not bound by that traffic); with fewer than two column blocks per XCD the order would idle XCDs
     // (d = 512, k = 10, two column blocks: 12.4 against 8.8 ms per iteration), so it needs >= 16.
-    static const bool xcd = [] {
-        const char *e = getenv("PPCA_I8GEMM_XCD");
-        return !(e && atoi(e) == 0);
-    }();
-    I8GemmArgs h = g;
-    const bool tall = tm == 256 && g.tile_rows != 128 && ((g.ksplit == 0 && g.M >= 4096) || (s256 && g.M >= 1024));  // (the Gram: one row per sample; S at d >= 1024)
-    const int tmr = tall ? 256 : 128;
-    h.ncb = (int)((g.N + 31) / 32);
-    h.nrb = (int)((g.M + tmr - 1) / tmr);
-    const int nz = g.ksplit > 0 ? g.nsplit : 1;
-    h.xcd_map = (xcd && h.ncb >= 16) ? 1 : 0;
+    h.xcd_map = h.ncb >= 16 ? 1 : 0;
     dim3 grid((unsigned)h.ncb, (unsigned)h.nrb, (unsigned)nz);
     if (h.xcd_map) grid = dim3((unsigned)(8 * ((h.ncb + 7) / 8) * h.nrb * nz), 1u, 1u);
     if (ppca_generic_trace *t = t_trace) {
@@ -2784,15 +2171,6 @@ static hipError_t launch_i8gemm(const I8GemmArgs &g, hipStream_t s, int role) {
                            g.nsplit - 1, g.guard);
     }
     return hipGetLastError();
-}
-
-// PPCA_GENERIC_SKINNY=0: the two skinny statistics products through gemm_kernel<2> / <3> at every k (A/B runs)
-static bool skinny_ok() {
-    static const bool v = [] {
-        const char *e = getenv("PPCA_GENERIC_SKINNY");
-        return !(e && atoi(e) == 0);
-    }();
-    return v;
 }
 
 // PPCA_GENERIC_FP64=1: both large contractions on the fp64 MFMA always (A/B runs)
@@ -2846,29 +2224,12 @@ static hipError_t launch_gemm(GemmArgs g, hipStream_t s, int n_cu = 256, double 
     return hipGetLastError();
 }
 
-static size_t solve_lds(int k) { return sizeof(double) * 2 * (size_t)(2 * k * (k | 1) + 64); }
-
-// each device gets the attribute once, at the size of the largest k (64) this kernel serves
-static hipError_t set_solve_lds(int k) {
-    if (solve_lds(k) <= 65536) return hipSuccess;
-    return ensure_dynamic_lds<solve_kernel>(solve_lds(64));
-}
-
 #define GTRY(expr)                        \
     do {                                  \
         hipError_t _e = (expr);           \
         if (_e != hipSuccess) return _e;  \
     } while (0)
 
-// E-step + statistics of all rows into stats (overwritten).  post == true: only the solve outputs.
-// PPCA_GENERIC_PREP=0: rowstats_kernel, gen_maskbytes_kernel and gemm_kernel<1> as three passes over X (A/B runs)
-static bool prep_enabled() {
-    static const bool v = [] {
-        const char *e = getenv("PPCA_GENERIC_PREP");
-        return !(e && atoi(e) == 0);
-    }();
-    return v;
-}
 // PPCA_EM16=0: the split pipeline below also for 11 <= k <= 16, d <= 256 (A/B runs against ppca_em16.hip)
 static bool em16_enabled() {
     static const bool v = [] {
@@ -2943,6 +2304,7 @@ static hipError_t run_em16(const double *X, int64_t ldx, const double *w, int64_
     return hipSuccess;
 }
 
+// em: E-step + statistics of all rows into stats (overwritten); otherwise only the solve outputs (scal8, llks, states, covs, recon).
 static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int64_t n, int d, int k,
                               const double *model, bool em, double *stats,
                               double *scal8, double *llks, double *states, double *covs, double *recon, int recon_mode,
@@ -2959,12 +2321,8 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
     const double *mean = model + MODEL_HDR + (int64_t)d * k;
     const double *Cm = model + MODEL_HDR;
     // (round 6) k = 65 .. 128 run the int8-sliced contractions too (their tables, guards and the int8 GEMM are not bound in k; only the
-    // fused pre-solve pass is: those sizes take the three separate passes) -- PPCA_GENERIC_BIG_FP64=1: the fp64 contractions of round 5
-    static const bool big_fp64 = [] {
-        const char *e = getenv("PPCA_GENERIC_BIG_FP64");
-        return e && atoi(e) == 1;
-    }();
-    const bool i8 = generic_i8() && (k <= 64 || !big_fp64);
+    // fused pre-solve pass is: those sizes take the three separate passes)
+    const bool i8 = generic_i8();
     if (trace) trace->int8 = i8 ? 1 : 0;
     if (em && i8 && em16_enabled() && em16_covers(d, k)) {
         if (trace) trace->fused16 = 1;
@@ -2981,7 +2339,6 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
             GTRY(hipGetLastError());
         }
     }
-    if (k <= 64) GTRY(set_solve_lds(k));
     if (em) GTRY(hipMemsetAsync(stats, 0, sizeof(double) * (size_t)L.len, s));
     for (int64_t r0 = 0; r0 < n; r0 += W.chunk) {
         const int64_t nc = std::min(W.chunk, n - r0);
@@ -2990,7 +2347,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
         GemmArgs g{};
         g.X = Xc; g.ldx = ldx; g.mean = mean;
         const int64_t ncpad = pad64(nc);
-        const bool prep = prep_enabled() && k <= 64;
+        const bool prep = k <= 64;  // (gen_prep_kernel keeps all of C's column tiles in LDS: NT <= 4)
         if (prep) {  // row statistics, mask bytes and b = X~ C in one pass over the chunk's rows
             const dim3 pg((unsigned)(ncpad / 64));
             if (k <= 16) hipLaunchKernelGGL((gen_prep_kernel<1>), pg, dim3(256), prep_lds(1), s, Xc, ldx, nc, d, W.dpad, W.npad, model, k, W.A, W.AT, W.xx, W.mc, W.Bz, i8 ? 1 : 0);
@@ -3014,11 +2371,6 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
             // G = Mask . Q on the int8 MFMA (exact integer accumulation) unless the guard raised flags[0]
             I8GemmArgs q{};
             q.A = W.A; q.lda = W.dpad; q.Bt = W.BtQ; q.ldb = W.dpad; q.plane = kp * (int64_t)W.dpad;
-            static const int gram_tile = [] {  // PPCA_I8GEMM_GRAM_TM=128: the Gram product on 128-row tiles (A/B runs)
-                const char *e = getenv("PPCA_I8GEMM_GRAM_TM");
-                return (e && atoi(e) == 128) ? 128 : 0;
-            }();
-            q.tile_rows = gram_tile;
             q.M = nc; q.N = kp; q.K = W.dpad; q.scale = W.scaleQ; q.out = W.G; q.ldo = kp; q.accumulate = 0;
             q.guard = W.flags;
             GTRY(launch_i8gemm(q, s, 0));
@@ -3041,15 +2393,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
         a.states = states ? states + r0 * k : nullptr;
         a.covs = covs ? covs + r0 * (int64_t)k * k : nullptr;
         a.need_sigma = (covs || (recon && recon_mode >= 2)) ? 1 : 0;
-        if (getenv("PPCA_GENERIC_LDS_SOLVE")) {  // the LDS-resident variant, kept for A/B runs
-            int sgrid = (int)std::min<int64_t>((nc + 1) / 2, (int64_t)n_cu);
-            if (sgrid < 1) sgrid = 1;
-            trace_solver(8, (k + 15) / 16, sgrid, 2, nc);
-            hipLaunchKernelGGL(solve_kernel, dim3(sgrid), dim3(128), solve_lds(k), s, a);
-            GTRY(hipGetLastError());
-        } else {
-            GTRY(launch_solve(a, n_cu, s));
-        }
+        GTRY(launch_solve(a, n_cu, s));
         double *scal = em ? stats + L.scalars : scal8;
         {
             const int sb = (int)((nc + SCAL_ROWS - 1) / SCAL_ROWS);
@@ -3106,7 +2450,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                 bool launched = false;
                 {   // a grid a little above the tiles the chip runs at once spends a nearly empty extra round
                     // (two 128-row workgroups fit a CU, one 256-row workgroup: launch_i8gemm picks the tile as below)
-                    const bool t256 = q.M >= 1024 && i8gemm_s256();
+                    const bool t256 = q.M >= 1024;
                     const int64_t tmr = t256 ? 256 : 128, nrb = (q.M + tmr - 1) / tmr, ncb = (q.N + 31) / 32;
                     const int64_t tiles = nrb * ncb, slots = (t256 ? 1 : 2) * (int64_t)n_cu;
                     const int64_t cb_round = slots / nrb;                       // column blocks one full round of the chip takes
@@ -3162,8 +2506,8 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
             GTRY(launch_gemm<2>(g, s, n_cu, W.part, W.part_cap));
             g.guard = nullptr;
             hipError_t serr = hipSuccess;
-            if (skinny_ok() && launch_skinny_xt(Xc, ldx, nc, d, k, mean, W.Bz, stats, L, W.part, W.part_cap, n_cu, s, &serr)) {
-                GTRY(serr);  // both skinny products in one pass over the chunk's rows (k + 1 <= 32 columns)
+            if (launch_skinny_xt(Xc, ldx, nc, d, k, mean, W.Bz, stats, L, W.part, W.part_cap, n_cu, s, &serr)) {
+                GTRY(serr);  // both skinny products in one pass over the chunk's rows (k + 1 <= 80 columns)
             } else {
                 // [U | totals] += Mask^T . [wz | w]
                 g.B = W.Bz; g.ldb = k + 1; g.N = k + 1;
@@ -3174,11 +2518,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
                 GTRY(launch_gemm<3>(g, s, n_cu, W.part, W.part_cap));
             }
         } else if (recon) {
-            static const bool naive = [] {  // PPCA_GENERIC_RECON=naive: one thread per output element (A/B runs)
-                const char *e = getenv("PPCA_GENERIC_RECON");
-                return e && e[0] == 'n';
-            }();
-            if (naive || k > 64) {
+            if (k > 64) {  // one thread per output element: recon2_kernel keeps a row of C in registers, KPAD <= 64
                 if (t_trace && r0 == 0) t_trace->recon_kind = 1;
                 const int64_t tot = nc * d;
                 hipLaunchKernelGGL(recon_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, Xc, ldx, nc, d, k,
@@ -3218,7 +2558,7 @@ static hipError_t generic_run(const double *X, int64_t ldx, const double *w, int
 // otherwise -1 and *flag_dev points at the guard flag (0 = int8-sliced, non-zero = fp64) the digit kernels just wrote.
 // ws: a workspace of generic_workspace_bytes(d, k, 1).
 hipError_t generic_gram_guard(int d, int k, const double *model, void *ws, hipStream_t s, const int **flag_dev, int *forced) {
-    if (!generic_i8() || (k > 64 && getenv("PPCA_GENERIC_BIG_FP64") && atoi(getenv("PPCA_GENERIC_BIG_FP64")) == 1)) {
+    if (!generic_i8()) {
         *forced = 1;
         return hipSuccess;
     }
@@ -3256,7 +2596,7 @@ hipError_t generic_post(const double *X, int64_t ldx, const double *w, int64_t n
 
 hipError_t generic_finalize(int k, int d, const double *stats, const double *model_in, double *model_out, double tau,
                             int has_ig, double alpha, double beta, int n_cu, hipStream_t s) {
-    if (k > 64) {  // one workgroup per dimension (solve_big_kernel's tools)
+    if (k > 64) {  // one workgroup per dimension (blk_cholesky, blk_chol_solve)
         const size_t lds = solve_big_lds(k);
         GTRY(ensure_dynamic_lds<gen_rowsolve_big_kernel>(lds));
         hipLaunchKernelGGL(gen_rowsolve_big_kernel, dim3((unsigned)std::min(d, 4 * n_cu)), dim3(256), lds, s, stats, model_in, model_out, d, k, tau);
@@ -3266,7 +2606,7 @@ hipError_t generic_finalize(int k, int d, const double *stats, const double *mod
     }
     const auto rowsolve_lds = [](int kk) { return sizeof(double) * 2 * (size_t)(kk * (kk | 1) + 64); };
     const size_t lds = rowsolve_lds(k);
-    if (lds > 65536) GTRY(ensure_dynamic_lds<gen_rowsolve_kernel>(rowsolve_lds(64)));  // (k = 64: 67,584 B), as set_solve_lds
+    if (lds > 65536) GTRY(ensure_dynamic_lds<gen_rowsolve_kernel>(rowsolve_lds(64)));  // (k = 64: 67,584 B; once per device, at the largest k)
     int grid = std::min((d + 1) / 2, n_cu * 2);
     hipLaunchKernelGGL(gen_rowsolve_kernel, dim3(grid), dim3(128), lds, s, stats, model_in, model_out, d, k, tau);
     GTRY(hipGetLastError());

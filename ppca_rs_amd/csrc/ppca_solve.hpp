@@ -1,5 +1,6 @@
 // ppca_solve.hpp -- the per-sample solve stage of the split pipeline (ppca_generic.hip): argument block shared by the
-// solver kernels of ppca_generic.hip and the batched blocked solver of ppca_solve4.hip.  Not installed.
+// solver kernels of ppca_generic.hip (one lane per sample, k <= 16; one sample per wave blocked on the fp64 MFMA, k = 65 .. 128)
+// and the batched blocked solver of ppca_solve4.hip.  Not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -675,9 +675,9 @@ def test_full_size_properties(P):
                                             # K-steps (17 over the dimensions, 67 over the samples): the wide request of the ring loop
                                             # walks K-steps in pairs
                                             (4230, 1080, 18, 0.3, False),
-                                            # state sizes beyond 64 (round 5; the reference bounds k nowhere, ppca_model.rs:51-70): fp64
-                                            # contractions + the workgroup-per-matrix solver of ppca_generic.hip, up to the 128 x 128
-                                            # matrix that 160 KB of LDS hold
+                                            # state sizes beyond 64 (the reference bounds k nowhere, ppca_model.rs:51-70): the int8-sliced
+                                            # contractions, one sample per wave on the blocked MFMA solver (solve_mfma_kernel<5..8>) and the
+                                            # workgroup-per-dimension finalisation, up to the 128 x 128 matrix that 160 KB of LDS hold
                                             (150, 90, 65, 0.2, False), (120, 140, 100, 0.3, False), (70, 150, 128, 0.2, False)])
 def test_generic_pipeline_matches_oracle(P, oracle, n, d, k, mp, block):
     """Shapes outside the fused kernel (d > 256 or k > 10) run the split pipeline

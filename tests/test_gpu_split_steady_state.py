@@ -485,6 +485,49 @@ def test_int8_gemm_by_pointer_arithmetic(P, oracle, ctx):
     assert {("tile", 128), ("tile", 256), ("xcd", 1), ("xcd", 0), ("sliced", True)} <= seen, ("branch 9: a form not reached", seen)
 
 
+# ------------------------------------------------------------------ retired switches
+RETIRED_SWITCHES = {  # every variable the split pipeline once read and no longer does, at its non-default value
+    "PPCA_GENERIC_SOLVE": "bc", "PPCA_GENERIC_REG_SOLVE": "1", "PPCA_GENERIC_LDS_SOLVE": "1", "PPCA_GENERIC_LANE_SOLVE": "0",
+    "PPCA_SOLVE4": "0", "PPCA_SOLVE_BIG": "1", "PPCA_SOLVE_OCC2": "0", "PPCA_GENERIC_RECON": "naive", "PPCA_GENERIC_PREP": "0",
+    "PPCA_GENERIC_SKINNY": "0", "PPCA_GENERIC_BIG_FP64": "1", "PPCA_I8GEMM_TM": "128", "PPCA_I8GEMM_GRAM_TM": "128",
+    "PPCA_I8GEMM_S256": "0", "PPCA_I8GEMM_XCD": "0",
+}
+
+
+def test_retired_switches_are_inert(P, oracle, ctx):
+    """A child process under every retired switch of the split pipeline at once, on the smallest shapes at which each used to change
+    the route: the EM statistics and the smoothed reconstruction against the oracle, and the dispatch record shows the default route --
+    d = 300, k = 8: lane solver, the one-pass skinny products, the one pre-solve pass (no gemm_kernel<1>), recon2_kernel;
+    d = 70, k = 32, n = 4200: solve4 on two blocks per side, the Gram on 256-row tiles in the XCD-aware order (528 packed columns = 17
+    column blocks); d = 1024, k = 4: the statistics product on 256-row tiles; d = k = 70: one sample per wave on the MFMA with five blocks
+    per side, the int8 contractions, recon_kernel."""
+    tool = _tool()
+    res = _child("inert", RETIRED_SWITCHES)
+    tr = {}
+    for name in tool.CASES["inert"]:
+        x, w, (s, c, mu) = tool.case_data("inert", name)
+        d, k = c.shape
+        tr[name] = t, ts = json.loads(str(res[name + "_trace"])), json.loads(str(res[name + "_trace_smooth"]))
+        print("inert", name, {a: t[a] for a in ("solver", "solver_nb", "int8", "skinny_launches")}, t["i8gemm"], t["gemm"], "recon", ts["recon_kind"])
+        assert t["valid"] == 1 and t["em"] == 1 and (t["d"], t["k"], t["n"]) == (d, k, len(x)) and ts["em"] == 0, (name, t, ts)
+        _assert_stats(res[name + "_stats"], oracle.stats(x, s, c, mu, w), d, k, ("inert", name))
+        err = _rel(res[name + "_smooth"], oracle.reconstruct(x, s, c, mu, "smooth"))
+        print("inert", name, "smooth %.2e" % err)
+        assert err < TOL_RECON, (name, err)
+    t, ts = tr["lane"]
+    assert t["solver"] == LANE and ts["solver"] == LANE, t
+    assert t["skinny_launches"] == 1 and not [g for g in t["gemm"] if g["amode"] == 1] and ts["recon_kind"] == 2, (t, ts)
+    t, ts = tr["solve4"]
+    gram = [g for g in t["i8gemm"] if g["role"] == 0]
+    assert t["solver"] == SOLVE4 and t["solver_nb"] == 2 and ts["solver"] == SOLVE4, t
+    assert len(gram) == 1 and gram[0]["tile_rows"] == 256 and gram[0]["xcd_map"] == 1, t
+    t, ts = tr["tall"]
+    stat = [g for g in t["i8gemm"] if g["role"] == 1]
+    assert len(stat) == 1 and stat[0]["tile_rows"] == 256, t
+    t, ts = tr["mfma"]
+    assert t["solver"] == MFMA and t["solver_nb"] == 5 and t["int8"] == 1 and ts["solver"] == MFMA and ts["recon_kind"] == 1, (t, ts)
+
+
 # ------------------------------------------------------------------ the output passes of k = 11..16 at d <= 256
 @pytest.mark.parametrize("k,d", [(11, 256), (12, 64), (13, 200), (14, 255), (15, 100), (16, 200)])
 def test_output_passes_of_the_two_kernel_shapes(P, oracle, ctx, k, d):

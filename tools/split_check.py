@@ -11,6 +11,8 @@ wrote with the oracle (and, for the addressing form, bit for bit with a second c
     MODE chunks  under PPCA_GEN_CHUNK=16448: three chunks of more than 16 384 rows, once with weights that grow by 2^20 from chunk to
                  chunk (every column of a later chunk is cut a second time, by a grid capped along the rows) and once with ordinary
                  weights (every chunk weighs the same in the sums); the scalars and outputs of an output pass across chunks
+    MODE inert   under every RETIRED switch of the split pipeline at its non-default value (the test holds the list): the smallest
+                 shapes at which each of them used to change the route; one EM statistics pass and one smooth pass each
 
 Writes, per case NAME: NAME_stats (ppca_stats_raw), NAME_trace (ppca_generic_last_trace of that pass, as JSON) and what the mode adds.
 The inputs are not written: case_data() makes them again from the case's seed."""
@@ -27,6 +29,8 @@ CASES = {
     "ptr": {"sliced": (11, 8192 + 37, 300, 4, True), "xcd": (12, 1500, 70, 33, False), "tall": (13, 1300, 1100, 20, True)},
     "fp64": {"k4": (21, 2100, 300, 4, True), "k20": (23, 2100, 70, 20, True), "k40": (22, 2100, 70, 40, False)},
     "chunks": {"grow": (31, 2 * 16448 + 16400, 260, 3, True), "flat": (32, 2 * 16448 + 16400, 260, 3, True)},
+    "inert": {"lane": (41, 600, 300, 8, True), "solve4": (42, 4200, 70, 32, False), "tall": (43, 600, 1024, 4, True),
+              "mfma": (44, 300, 70, 70, True)},
 }
 CHUNK = 16448
 
@@ -61,10 +65,10 @@ def main():
         st = np.empty(_lib.lib().ppca_stats_len(d, k))
         _lib.check(_lib.lib().ppca_stats_raw(ctx.handle, ds._h, mod._device(ctx).h, _lib.ptr(st)))
         out[name + "_stats"], out[name + "_trace"] = st, json.dumps(ctx.generic_trace())
-        if mode != "ptr":
+        if mode in ("fp64", "chunks"):
             out[name + "_llks"], out[name + "_llk"] = mod.llks(ds), mod.llk(ds)
             out[name + "_trace_llk"] = json.dumps(ctx.generic_trace())
-        if mode == "chunks":
+        if mode in ("chunks", "inert"):
             out[name + "_smooth"] = mod.smooth(ds).numpy()
             out[name + "_trace_smooth"] = json.dumps(ctx.generic_trace())
         if mode == "fp64":
