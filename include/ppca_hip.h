@@ -401,6 +401,51 @@ int ppca_t_finalize_host(int32_t d, int32_t k, double sigma, const double *trans
 int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, double sigma, const double *transform, const double *mean,
                    double dof, double *sigma_out, double *transform_out, double *mean_out, double *llk_in, double *q_out);
 
+/* --------------------------------------------------- PPCA with a known precision per entry */
+/* An extension with no reference counterpart (weighted / heteroscedastic PCA: Bailey's EMPCA, Delchambre's weighted PCA):
+ *   x_ij = mean_j + c_j . z_i + eps_ij,   z_i ~ N(0, I_k),   eps_ij ~ N(0, sigma^2 / p_ij)
+ * with p_ij > 0 the KNOWN precision of entry (i, j) relative to sigma^2; p = 1 everywhere is the model of ppca_llk / ppca_infer.  A
+ * model is an ordinary ppca_model; the precisions are `prec`, a ppca_dataset of the same n and d as ds (its own row weights are
+ * ignored; another shape: PPCA_ERR_INVALID).  Entry (i, j) is observed iff x_ij is finite and p_ij is finite and > 0: p_ij NaN or 0
+ * means not observed, whatever x_ij holds.  A precision < 0 or = +inf is an error: the sweep counts them next to its scalars and the
+ * call returns PPCA_ERR_INVALID after its own synchronisation, with no output written.  For row i with observed set O (m entries),
+ * x~ = x - mean and the dataset's row weight w_i:
+ *   G_i = sum_O p_ij c_j c_j^T     b_i = sum_O p_ij x~_ij c_j     M_i = sigma^2 I + G_i
+ *   z_i = M_i^-1 b_i               Sigma_i = sigma^2 M_i^-1
+ *   ell_i = -1/2 [ (sum_O p_ij x~_ij^2 - b_i^T M_i^-1 b_i) / sigma^2 + ln det M_i + (m - k) ln sigma^2 + m ln 2 pi - sum_O ln p_ij ]
+ * A row with m = 0 has ell_i = 0 and z_i = 0.  Statistics of one E-step, per column j (ppca_h_stats_len(d, k) = d (2 k + k (k + 1) / 2 + 4)
+ * doubles, in this order):
+ *   cross_j = sum_i w_i p_ij x~_ij z_i  (d x k)            S_j = sum_i w_i p_ij (Sigma_i + z_i z_i^T)  (d x k (k + 1) / 2, lower-packed)
+ *   V_j = sum_i w_i p_ij z_i  (d x k)                      A_j = sum_i w_i p_ij x~_ij  (d)             T_j = sum_i w_i p_ij  (d)
+ *   sq_j = sum_i w_i p_ij x~_ij^2  (d)                     cnt_j = sum_i w_i m_ij  (d; m_ij = 1 where observed)
+ * Covers 1 <= k <= 16 and 1 <= d <= 1024 (PPCA_ERR_UNSUPPORTED beyond, before any launch).  Everything is fp64 on v_mfma_f64_16x16x4:
+ * a sweep over X and P forms [G | b] of 16 rows per wave against the table [vech(c c^T) | C] and solves one row per lane; the
+ * statistics are a second read of X and P against the rows' records [w z | w | w (Sigma + z z^T)], which pass through at most 1 GiB of
+ * scratch (row chunks; PPCA_H_CHUNK=rows in the environment forces a chunk length).  Per-workgroup partials added in a fixed order (no
+ * float atomics); ell_i, z_i and Sigma_i depend on their row alone, not on the grid, the chunks or a slice's offset. */
+int64_t ppca_h_stats_len(int32_t d, int32_t k);
+/* The E-step.  Every output is nullable; at least one must be given.  llks (n), states (n x k), covs (n x k x k): host or device
+ * destinations, as ppca_llk's per-sample output.  stats_host: the statistics above.  scalars_host: 4 doubles, sum w | sum w ell |
+ * rows with an observed entry | the count of bad precisions (0 whenever the call succeeds).  An empty dataset gives zeros. */
+int ppca_h_estep(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, const ppca_model *model, double *llks, double *states, double *covs,
+                 double *stats_host, double *scalars_host);
+/* mode 0 (smooth): out_ij = mean_j + c_j . z_i everywhere; mode 1 (extrapolate): x_ij, bit-exact, where entry (i, j) is observed by
+ * the rule above, mean_j + c_j . z_i elsewhere.  A new dataset carrying the weights of ds. */
+int ppca_h_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, const ppca_model *model, int32_t mode, ppca_dataset **out);
+/* The ECM M-step on host buffers (no GPU needed), in the block order of ppca_t_finalize_host, all from one E-step, so that the
+ * log-likelihood cannot decrease.  stats: ppca_h_estep's.  Per column j:
+ *   1. c_j = solution of S_j a = cross_j by the Cholesky row solve; a pivot <= 0 keeps the old row
+ *   2. delta_j = (A_j - c_j . V_j) / T_j with the NEW c_j (0 if T_j = 0); mean_j += delta_j
+ *   3. sigma^2 = sum_j (sq_j - 2 c_j . cross_j + c_j^T S_j c_j - delta_j^2 T_j) / sum_j cnt_j -- the weighted COUNT of observed entries,
+ *      not the sum of their precisions; a non-finite or non-positive value keeps the old sigma
+ * Not the reference's EM step (the caveat of ppca_fa_finalize_host and ppca_t_finalize_host).  Outputs may not alias inputs. */
+int ppca_h_finalize_host(int32_t d, int32_t k, double sigma, const double *transform, const double *mean, const double *stats,
+                         double *sigma_out, double *transform_out, double *mean_out);
+/* One ECM iteration on a single GPU: model upload, sweep, statistics contraction, one synchronisation, ppca_h_finalize_host.  llk_in
+ * (nullable): the log-likelihood of the INPUT model, sum_i w_i ell_i, a by-product of the sweep. */
+int ppca_h_em_step(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, int32_t d, int32_t k, double sigma, const double *transform,
+                   const double *mean, double *sigma_out, double *transform_out, double *mean_out, double *llk_in);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration

@@ -1523,6 +1523,213 @@ class TPPCATrainer:
                            n_parameters=lambda m: m.n_parameters + (1 if estimate_dof and not m._estimated else 0))
 
 
+# --------------------------------------------------------------------------- PPCA with a known precision per entry
+class HPPCAModel:
+    """Masked PPCA with a KNOWN precision per entry (weighted / heteroscedastic PCA): x_ij = mean_j + c_j . z_i + eps_ij with
+    z_i ~ N(0, I) and eps_ij ~ N(0, isotropic_noise^2 / p_ij), p_ij > 0 given with the data -- an entry that is a mean over n_ij
+    readings, or comes with an error bar, enters at its own noise level instead of at full weight or not at all (an extension with no
+    reference counterpart; include/ppca_hip.h).  With every precision 1 this is PPCAModel.
+
+    Every pass takes (dataset, precisions): `precisions` is a Dataset, or an array, of the dataset's shape.  An entry is observed iff
+    its value is finite and its precision is finite and > 0; a precision of NaN or 0 masks the entry whatever its value; a negative or
+    +inf precision raises PPCAError (PPCA_ERR_INVALID).  An iteration is an ECM step (transform, then mean, then noise, each given the
+    ones before it, all from one E-step), not the reference's EM step.  LIMITS: state sizes 1 .. 16, output sizes 1 .. 1024.
+    """
+
+    MAX_STATE_SIZE, MAX_OUTPUT_SIZE = 16, 1024
+
+    def __init__(self, isotropic_noise: float, transform, mean, *, ctx=None):
+        base = PPCAModel(isotropic_noise, transform, mean, ctx=ctx)  # (the checks of transform and mean are PPCAModel's)
+        if not (np.isfinite(base._sigma) and base._sigma > 0.0):
+            raise ValueError("isotropic_noise must be a positive finite number")
+        d, k = base.output_size, base.state_size
+        if k < 1 or k > self.MAX_STATE_SIZE or d < 1 or d > self.MAX_OUTPUT_SIZE:
+            raise ValueError(f"the per-entry-precision sweep covers state sizes 1 .. {self.MAX_STATE_SIZE} and output sizes 1 .. "
+                             f"{self.MAX_OUTPUT_SIZE} (got k={k}, d={d})")
+        self._base, self._ctx = base, ctx
+
+    # -- getters ----------------------------------------------------------------
+    @property
+    def isotropic_noise(self) -> float:
+        return self._base._sigma
+
+    @property
+    def transform(self) -> np.ndarray:
+        return self._base._c.copy()
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self._base._mean.copy()
+
+    @property
+    def output_size(self) -> int:
+        return self._base.output_size
+
+    @property
+    def state_size(self) -> int:
+        return self._base.state_size
+
+    @property
+    def n_parameters(self) -> int:
+        return self._base.n_parameters
+
+    def __repr__(self) -> str:
+        return f"HPPCAModel(isotropic_noise={self._base._sigma}, transform=array({self._base._c}), mean=array({self._base._mean}))"
+
+    # -- construction -------------------------------------------------------------
+    @staticmethod
+    def init(state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "HPPCAModel":
+        """The start of PPCAModel.init (same seed, same draw; method="pca": its spectral start through PPCAModel.from_moments, which
+        ignores the precisions)."""
+        if state_size < 1:
+            raise ValueError("state_size must be >= 1")
+        return HPPCAModel.from_ppca(PPCAModel.init(state_size, dataset, seed=seed, method=method))
+
+    @staticmethod
+    def from_ppca(model: PPCAModel) -> "HPPCAModel":
+        return HPPCAModel(model._sigma, model._c, model._mean, ctx=model._ctx)
+
+    def gaussian(self) -> PPCAModel:
+        """PPCAModel with the same sigma, C and mean (every precision 1)."""
+        return self._base
+
+    def to_canonical(self) -> "HPPCAModel":
+        """The rotation of PPCAModel.to_canonical on C; sigma and mean are untouched."""
+        b = self._base.to_canonical()
+        return HPPCAModel(b._sigma, b._c, b._mean, ctx=self._ctx)
+
+    def sample(self, precisions, seed: Optional[int] = None, *, ctx=None) -> Dataset:
+        """Host-side numpy (like TPPCAModel.sample): one row per row of `precisions` (an array or a Dataset, N x output_size),
+        mean + C z + isotropic_noise eps / sqrt(p) -- every entry at the noise level its precision gives; NaN where the precision
+        is NaN or 0."""
+        p = precisions.numpy() if isinstance(precisions, Dataset) else np.asarray(precisions, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.output_size:
+            raise ValueError(f"precisions must be (N, {self.output_size}); got {p.shape}")
+        if (p < 0).any() or np.isposinf(p).any():
+            raise ValueError("a precision is negative or +inf")
+        rng = np.random.default_rng(seed)
+        n, d, k = p.shape[0], self.output_size, self.state_size
+        on = np.isfinite(p) & (p > 0)
+        rows = rng.standard_normal((n, k)) @ self._base._c.T
+        eps = rng.standard_normal((n, d))
+        x = self._base._mean + rows + self._base._sigma * eps / np.sqrt(np.where(on, p, 1.0))
+        x[~on] = np.nan
+        return Dataset(x, ctx=ctx or self._ctx)
+
+    # -- passes ---------------------------------------------------------------------
+    def _pair(self, dataset: Dataset, precisions) -> Dataset:
+        """`precisions` as a Dataset on the dataset's context, shapes checked."""
+        n, d = len(dataset), dataset._d
+        if d != self.output_size:
+            raise ValueError(f"dataset has {d} dimensions but the model has output size {self.output_size}")
+        if not isinstance(precisions, Dataset):
+            p = np.ascontiguousarray(precisions, dtype=np.float64)
+            if p.shape != (n, d):
+                raise ValueError(f"precisions have shape {p.shape} but the dataset is {n} x {d}")
+            precisions = Dataset(p, ctx=dataset._ctx)
+        return precisions
+
+    def _estep(self, dataset: Dataset, precisions, *, llks: bool = False, states: bool = False, covs: bool = False, stats: bool = False,
+               scalars: bool = False):
+        """ppca_h_estep: (llks, states, covs, statistics, scalars), None where not asked for."""
+        prec = self._pair(dataset, precisions)
+        ctx, n, d, k = dataset._ctx, len(dataset), self.output_size, self.state_size
+        ll = np.empty(n) if llks else None
+        st = np.empty((n, k)) if states else None
+        cv = np.empty((n, k, k)) if covs else None
+        ss = np.empty(int(lib().ppca_h_stats_len(d, k))) if stats else None
+        sc = np.empty(4) if scalars else None
+        check(lib().ppca_h_estep(ctx.handle, dataset._h, prec._h, self._base._device(ctx).h, ptr(ll), ptr(st), ptr(cv), ptr(ss), ptr(sc)))
+        return ll, st, cv, ss, sc
+
+    def llks(self, dataset: Dataset, precisions) -> np.ndarray:
+        """Per-sample log-density of the observed entries (0 for a row without any)."""
+        return self._estep(dataset, precisions, llks=True)[0]
+
+    def llk(self, dataset: Dataset, precisions) -> float:
+        """Weighted log-likelihood."""
+        return float(self._estep(dataset, precisions, scalars=True)[4][1])
+
+    def infer(self, dataset: Dataset, precisions) -> InferredFA:
+        """Posterior means z_i = M_i^-1 b_i and covariances sigma^2 M_i^-1 of the latent states."""
+        _, st, cv, _, _ = self._estep(dataset, precisions, states=True, covs=True)
+        return InferredFA(st, cv)
+
+    def _recon(self, dataset: Dataset, precisions, mode: int) -> Dataset:
+        prec = self._pair(dataset, precisions)
+        ctx = dataset._ctx
+        h = C.c_void_p()
+        check(lib().ppca_h_reconstruct(ctx.handle, dataset._h, prec._h, self._base._device(ctx).h, mode, C.byref(h)))
+        return Dataset._wrap(h, ctx)
+
+    def smooth(self, dataset: Dataset, precisions) -> Dataset:
+        """C z + mean for every dimension."""
+        return self._recon(dataset, precisions, 0)
+
+    def extrapolate(self, dataset: Dataset, precisions) -> Dataset:
+        """Observed values kept (observed: finite value, finite precision > 0), the others replaced by C z + mean."""
+        return self._recon(dataset, precisions, 1)
+
+    def _iterate(self, dataset: Dataset, precisions, want_llk: bool):
+        if len(dataset) == 0:
+            raise ValueError("dataset is empty")
+        prec = self._pair(dataset, precisions)
+        ctx, d, k = dataset._ctx, self.output_size, self.state_size
+        s_out, c_out, m_out, llk = C.c_double(0.0), np.empty((d, k)), np.empty(d), C.c_double(0.0)
+        check(lib().ppca_h_em_step(ctx.handle, dataset._h, prec._h, d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean),
+                                   C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
+        return HPPCAModel(s_out.value, c_out, m_out, ctx=self._ctx), (llk.value if want_llk else None)
+
+    def iterate(self, dataset: Dataset, precisions) -> "HPPCAModel":
+        """One ECM iteration: the log-likelihood cannot decrease."""
+        return self._iterate(dataset, precisions, False)[0]
+
+    def iterate_with_llk(self, dataset: Dataset, precisions):
+        """(next model, log-likelihood of THIS model) from the same pass."""
+        return self._iterate(dataset, precisions, True)
+
+    # -- serialisation (own npz container) ----------------------------------------------
+    def dump(self) -> bytes:
+        return _npz_dump("ppca_rs_amd.HPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean)
+
+    @staticmethod
+    def load(data: bytes) -> "HPPCAModel":
+        return _npz_load(data, "ppca_rs_amd.HPPCAModel", "a HPPCAModel",
+                         lambda z: HPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"]))
+
+    def __getstate__(self):
+        return self.dump()
+
+    def __setstate__(self, state):
+        self.__dict__.update(HPPCAModel.load(state).__dict__)
+
+    def __getnewargs__(self):
+        return (self.isotropic_noise, self.transform, self.mean)
+
+
+@dataclass
+class HPPCATrainer:
+    """EM driver of HPPCAModel.  train returns (model, metrics): the canonical model after n_iters iterations and one TrainMetrics per
+    iteration, of the model that ENTERED it (the log-likelihood is a by-product of the iteration's sweep)."""
+
+    dataset: Dataset
+    precisions: object
+
+    def train(self, *, state_size: int, n_iters: int = 10, start: Optional[HPPCAModel] = None, init: str = "random",
+              seed: Optional[int] = None, quiet: bool = True, metric: Literal["aic", "bic", "llk"] = "aic"):
+        ds = self.dataset
+        model = start or HPPCAModel.init(state_size, ds, seed=seed, method=init)
+        prec = model._pair(ds, self.precisions)  # (uploaded once)
+        metrics: List[TrainMetrics] = []
+        for idx in range(n_iters):
+            new_model, llk = model.iterate_with_llk(ds, prec)
+            metrics.append(_metrics(llk, model.n_parameters, len(ds)))
+            if not quiet:
+                print(f"Masked H-PPCA iteration {idx + 1}: {metric}={getattr(metrics[-1], metric)}")
+            model = new_model
+        return model.to_canonical(), metrics
+
+
 # --------------------------------------------------------------------------- mixture
 def _log_softmax(v: np.ndarray) -> np.ndarray:
     v = np.asarray(v, dtype=np.float64)

@@ -3123,3 +3123,201 @@ extern "C" int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_
     if (q_out) *q_out = sc[0] > 0.0 ? sc[2] / sc[0] : 0.0;
     return PPCA_OK;
 }
+
+// ------------------------------------------------------------------ heteroscedastic PPCA
+static int check_h_covers(int d, int k) {  // k: the caller's state size (0 is not covered)
+    if (hetero_covers(d, k)) return PPCA_OK;
+    return fail(PPCA_ERR_UNSUPPORTED, "the per-entry-precision sweep covers state sizes 1 .. %d and output sizes 1 .. %d (got k=%d, d=%d)",
+                HETERO_MAX_K, HETERO_MAX_D, k, d);
+}
+
+extern "C" int64_t ppca_h_stats_len(int32_t d, int32_t k) { return hetero_stats_len(d, k); }
+
+static int h_check(const ppca_dataset *ds, const ppca_dataset *prec, const ppca_model *model) {
+    if (!ds || !prec || !model) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_h_covers(model->d, model->k_user())) return rc;
+    if (int rc = check_pair(ds, model)) return rc;
+    if (prec->n != ds->n || prec->d != ds->d)
+        return fail(PPCA_ERR_INVALID, "the precisions (%lld x %d) and the dataset (%lld x %d) differ in shape", (long long)prec->n, prec->d,
+                    (long long)ds->n, ds->d);
+    if (prec->ctx->device != ds->ctx->device) return fail(PPCA_ERR_INVALID, "precisions and dataset live on different devices");
+    return PPCA_OK;
+}
+
+// Rows of a chunk: the record, the posterior mean and the log-density of a row are its scratch (chunk_rows: under 1 GiB).
+// PPCA_H_CHUNK=rows forces a chunk length (tests: several chunks at small N).
+static int64_t h_chunk_rows(int64_t n, int k) {
+    int64_t c = chunk_rows(n, (int64_t)sizeof(double) * (hetero_nrp(k) + k + 1));
+    if (const char *e = getenv("PPCA_H_CHUNK")) {
+        const long long v = atoll(e);
+        if (v > 0) c = v;
+    }
+    return c;
+}
+
+// What a sweep keeps alive until the caller's synchronisation.
+struct HSweep {
+    std::vector<double> res;  // the reduced [statistics (slen) | sum w | sum w ell | non-empty rows | bad precisions] as downloaded
+    BufRef tab, rec, states;
+    Partials part, scal;
+    int64_t slen = 0;
+    double bad() const { return res[(size_t)slen + 3]; }
+};
+
+static int h_bad_precisions(const HSweep &sw) {
+    return fail(PPCA_ERR_INVALID, "%.0f precisions are negative or +inf (a precision is > 0 and finite; 0 or NaN marks an entry as not observed)",
+                sw.bad());
+}
+
+// Enqueues the E-step sweep over the whole dataset by row chunks -- and per chunk, as asked for, the statistics contraction and the
+// reconstruction -- then the copy of the reduced sums into sw.res; no synchronisation.  llks (n), states (n x k), covs (n x k x k),
+// recon (n x d; recon_mode 0 smooth, 1 extrapolate): device destinations, nullable.  The per-row outputs do not depend on the chunks;
+// the last bits of the statistics, accumulated chunk after chunk, do.
+static int h_sweep(ppca_ctx *ctx, const ppca_dataset *ds, const ppca_dataset *prec, const ppca_model *model, double *llks, double *states,
+                   double *covs, bool stats, int recon_mode, double *recon, HSweep &sw) {
+    const int64_t n = ds->n;
+    const int d = ds->d, k = model->k;
+    sw.slen = stats ? hetero_stats_len(d, k) : 0;
+    sw.res.assign((size_t)sw.slen + 4, 0.0);
+    if (n <= 0) return PPCA_OK;
+    const int nrp = hetero_nrp(k);
+    if (int rc = dev_alloc(sizeof(double) * (size_t)d * hetero_ntp(k), &sw.tab)) return rc;
+    double *tab = static_cast<double *>(sw.tab->p);
+    HIP_TRY(launch_hetero_table(model->p(), d, k, tab, ctx->stream));
+    const int64_t chunk = h_chunk_rows(n, k);
+    const size_t rows = (size_t)std::min(chunk, n);
+    if (int rc = sw.scal.alloc(hetero_sweep_grid((int64_t)rows, ctx->n_cu), 4)) return rc;
+    double *rec = nullptr, *st_own = nullptr;
+    if (stats) {
+        if (int rc = dev_alloc(sizeof(double) * rows * nrp, &sw.rec)) return rc;
+        rec = static_cast<double *>(sw.rec->p);
+        if (int rc = sw.part.alloc(hetero_stats_plan((int64_t)rows, d, ctx->n_cu).nsplit_max, sw.slen)) return rc;
+    }
+    if (recon && !states) {
+        if (int rc = dev_alloc(sizeof(double) * rows * k, &sw.states)) return rc;
+        st_own = static_cast<double *>(sw.states->p);
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t cn = std::min(chunk, n - r0);
+        const double *X = ds->X + r0 * d, *P = prec->X + r0 * d, *w = ds->w ? ds->w + r0 : nullptr;
+        double *st = states ? states + r0 * k : st_own;
+        const int grid = hetero_sweep_grid(cn, ctx->n_cu);
+        HIP_TRY(launch_hetero_sweep(X, d, P, d, w, cn, d, k, model->p(), tab, llks ? llks + r0 : nullptr, st,
+                                    covs ? covs + r0 * k * k : nullptr, rec, sw.scal.p, grid, ctx->stream));
+        HIP_TRY(sw.scal.reduce(ctx->stream, r0 > 0 ? 1 : 0, grid));
+        if (stats) {
+            const HeteroPlan plan = hetero_stats_plan(cn, d, ctx->n_cu);
+            HIP_TRY(launch_hetero_stats(X, d, P, d, cn, d, k, model->p(), rec, plan, sw.part.p, ctx->stream));
+            HIP_TRY(sw.part.reduce(ctx->stream, r0 > 0 ? 1 : 0, plan.nsplit));
+        }
+        if (recon) HIP_TRY(launch_hetero_recon(X, d, P, d, cn, d, k, model->p(), st, recon_mode, recon + r0 * d, ctx->n_cu, ctx->stream));
+    }
+    if (stats) HIP_TRY(hipMemcpyAsync(sw.res.data(), sw.part.red, sizeof(double) * (size_t)sw.slen, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sw.res.data() + sw.slen, sw.scal.red, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return PPCA_OK;
+}
+
+extern "C" int ppca_h_estep(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, const ppca_model *model, double *llks, double *states,
+                            double *covs, double *stats_host, double *scalars_host) {
+    if (!ctx) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!llks && !states && !covs && !stats_host && !scalars_host) return fail(PPCA_ERR_INVALID, "no output requested");
+    if (int rc = h_check(ds, prec, model)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int k = model->k;
+    BufRef lb, sb, cb;
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+    if (llks)
+        if (int rc = dev_alloc(sizeof(double) * n1, &lb)) return rc;
+    if (states)
+        if (int rc = dev_alloc(sizeof(double) * n1 * k, &sb)) return rc;
+    if (covs)
+        if (int rc = dev_alloc(sizeof(double) * n1 * k * k, &cb)) return rc;
+    HSweep sw;
+    {
+        StreamGuard guard{ctx->stream};
+        if (int rc = h_sweep(ctx, ds, prec, model, lb ? static_cast<double *>(lb->p) : nullptr, sb ? static_cast<double *>(sb->p) : nullptr,
+                             cb ? static_cast<double *>(cb->p) : nullptr, stats_host != nullptr, 0, nullptr, sw))
+            return rc;
+    }  // (the guard's synchronisation is the call's own)
+    if (sw.bad() > 0.0) return h_bad_precisions(sw);  // no output
+    if (n > 0) {  // (host or device destinations, as ppca_llk's per-sample output)
+        if (llks) HIP_TRY(hipMemcpyAsync(llks, lb->p, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        if (states) HIP_TRY(hipMemcpyAsync(states, sb->p, sizeof(double) * (size_t)n * k, hipMemcpyDefault, ctx->stream));
+        if (covs) HIP_TRY(hipMemcpyAsync(covs, cb->p, sizeof(double) * (size_t)n * k * k, hipMemcpyDefault, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (stats_host) std::memcpy(stats_host, sw.res.data(), sizeof(double) * (size_t)sw.slen);
+    if (scalars_host) std::memcpy(scalars_host, sw.res.data() + sw.slen, sizeof(double) * 4);
+    return PPCA_OK;
+}
+
+extern "C" int ppca_h_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, const ppca_model *model, int32_t mode,
+                                  ppca_dataset **out) {
+    if (!ctx || !out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (mode != 0 && mode != 1) return fail(PPCA_ERR_INVALID, "mode must be 0 (smooth) or 1 (extrapolate)");
+    if (int rc = h_check(ds, prec, model)) return rc;
+    USE_CTX(ctx);
+    DatasetPtr nd;
+    if (int rc = dataset_like(ctx, ds, true, nd)) return rc;
+    HSweep sw;
+    {
+        StreamGuard guard{ctx->stream};
+        if (int rc = h_sweep(ctx, ds, prec, model, nullptr, nullptr, nullptr, false, mode, static_cast<double *>(nd->xbuf->p), sw)) return rc;
+    }
+    if (sw.bad() > 0.0) return h_bad_precisions(sw);
+    *out = nd.release();
+    return PPCA_OK;
+}
+
+extern "C" int ppca_h_finalize_host(int32_t d, int32_t k, double sigma, const double *transform, const double *mean, const double *stats,
+                                    double *sigma_out, double *transform_out, double *mean_out) {
+    if (int rc = check_h_covers(d, k)) return rc;
+    if (!transform || !mean || !stats || !sigma_out || !transform_out || !mean_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_sigma(sigma)) return rc;
+    const int kp = k * (k + 1) / 2;
+    const double *cross = stats, *Sall = cross + (int64_t)d * k, *V = Sall + (int64_t)d * kp, *A = V + (int64_t)d * k, *T = A + d, *sq = T + d,
+                 *cnt = sq + d;
+    std::vector<double> S((size_t)kp), a((size_t)k);
+    double num = 0.0, den = 0.0;
+    for (int j = 0; j < d; ++j) {
+        const double *Sj = Sall + (int64_t)j * kp, *cr = cross + (int64_t)j * k, *Vj = V + (int64_t)j * k;
+        // 1. the row: S_j a = cross_j; a pivot <= 0 keeps the old row
+        const MstepRow r = mstep_row(k, Sj, cr, Vj, transform + (int64_t)j * k, S.data(), a.data());
+        // 2. the mean moves by delta, with the NEW row
+        const double delta = T[j] > 0.0 ? (A[j] - r.af) / T[j] : 0.0;
+        // 3. the pooled noise over the weighted COUNT of observed entries, full form (the row may have been kept)
+        num += sq[j] - 2.0 * r.ac + r.asa - delta * delta * T[j];
+        den += cnt[j];
+        for (int b = 0; b < k; ++b) transform_out[(int64_t)j * k + b] = a[b];
+        mean_out[j] = mean[j] + delta;
+    }
+    const double v = num / den;
+    *sigma_out = (std::isfinite(v) && v > 0.0) ? std::sqrt(v) : sigma;
+    return PPCA_OK;
+}
+
+extern "C" int ppca_h_em_step(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, int32_t d, int32_t k, double sigma, const double *transform,
+                              const double *mean, double *sigma_out, double *transform_out, double *mean_out, double *llk_in) {
+    if (int rc = check_h_covers(d, k)) return rc;
+    if (!ctx || !ds || !prec || !transform || !mean || !sigma_out || !transform_out || !mean_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (ds->d != d) return fail(PPCA_ERR_INVALID, "dataset has %d dimensions but the model has output size %d", ds->d, d);
+    if (int rc = check_sigma(sigma)) return rc;
+    if (ds->n == 0) return fail(PPCA_ERR_EMPTY, "dataset is empty");
+    USE_CTX(ctx);
+    ppca_model *m_raw = nullptr;
+    if (int rc = ppca_model_alloc(ctx, d, k, &m_raw)) return rc;
+    const ModelPtr m(m_raw);
+    const std::vector<double> hm = model_image(sigma, transform, mean, d, k, k);  // (read until the synchronisation below)
+    HSweep sw;
+    {
+        StreamGuard guard{ctx->stream};
+        HIP_TRY(model_upload(ctx, m.get(), hm));
+        if (int rc = h_check(ds, prec, m.get())) return rc;
+        if (int rc = h_sweep(ctx, ds, prec, m.get(), nullptr, nullptr, nullptr, true, 0, nullptr, sw)) return rc;
+    }  // (the one synchronisation of the step)
+    if (sw.bad() > 0.0) return h_bad_precisions(sw);
+    if (int rc = ppca_h_finalize_host(d, k, sigma, transform, mean, sw.res.data(), sigma_out, transform_out, mean_out)) return rc;
+    if (llk_in) *llk_in = sw.res[(size_t)sw.slen + 1];
+    return PPCA_OK;
+}

@@ -337,6 +337,35 @@ hipError_t launch_robust_sweep(const double *X, int64_t ldx, const double *w, in
                                const double *llks, const double *states, const double *tabs, double nu, double *Y, bool sums, double *u,
                                double *maha, double *ell, double *part, int grid, hipStream_t s);
 
+// heteroscedastic PPCA (ppca_hetero.hip): a precision p_ij per entry (P: a second n x d array; an entry is
+// observed iff x is finite and p is finite and > 0).  launch_hetero_table: tab (d x hetero_ntp(k)) = [vech(c c^T) | C] of the model,
+// zero-padded to 16-column blocks.  launch_hetero_sweep over the n rows of a chunk: llks (n), states (n x k), covs (n x k x k), rec
+// (n x hetero_nrp(k): the records [w z | w | w (Sigma + z z^T) packed | 0 ..] the statistics kernel reads), all nullable;
+// scal_part[grid][4] = the workgroups' sum w | sum w ell | non-empty rows | precisions that are negative or +inf (reduce with
+// launch_reduce_partials); grid = hetero_sweep_grid(n, n_cu).  launch_hetero_stats: part[p.nsplit][hetero_stats_len(d, k)], the row
+// runs' partials of cross (d x k) | S (d x k') | V (d x k) | A | T | sq | cnt (reduce with launch_reduce_partials over p.nsplit).
+// launch_hetero_recon: out (n x d) = mean + C z (mode 0) or the observed value where observed (mode 1).
+constexpr int HETERO_MAX_K = 16;
+constexpr int HETERO_MAX_D = 1024;
+struct HeteroPlan {
+    int tiles, nsplit, nsplit_max;  // nsplit_max: what nsplit cannot exceed for any n on this device (the size of `part`)
+    int64_t rows_per;
+};
+bool hetero_covers(int d, int k);
+int hetero_ntp(int k);
+int hetero_nrp(int k);
+int64_t hetero_stats_len(int d, int k);
+int hetero_sweep_grid(int64_t n, int n_cu);
+HeteroPlan hetero_stats_plan(int64_t n, int d, int n_cu);
+hipError_t launch_hetero_table(const double *model, int d, int k, double *tab, hipStream_t s);
+hipError_t launch_hetero_sweep(const double *X, int64_t ldx, const double *P, int64_t ldp, const double *w, int64_t n, int d, int k,
+                               const double *model, const double *tab, double *llks, double *states, double *covs, double *rec,
+                               double *scal_part, int grid, hipStream_t s);
+hipError_t launch_hetero_stats(const double *X, int64_t ldx, const double *P, int64_t ldp, int64_t n, int d, int k, const double *model,
+                               const double *rec, const HeteroPlan &p, double *part, hipStream_t s);
+hipError_t launch_hetero_recon(const double *X, int64_t ldx, const double *P, int64_t ldp, int64_t n, int d, int k, const double *model,
+                               const double *states, int mode, double *out, int n_cu, hipStream_t s);
+
 // pairwise second moments (ppca_moments.hip): sums = X~^T diag(w) X~, counts = M^T diag(w) M and (cross
 // nullable) cross = X~^T diag(w) M, d x d row-major each, x~ = x - center on observed entries.  A job = (pair of 64-column tiles,
 // I <= J) x (run of rows); its partials go to part (p.scratch_bytes) and a second kernel adds the runs in order and mirrors the

@@ -15,7 +15,10 @@ the fused step replaces (a labelling call, then ppca_dataset_column_moments_mult
 read of X: the floor), the whole `Dataset.kmeans` (seeding plus iterations), the K moment passes of `from_kmeans`, and one
 ppca_mix_em_step at K components.  `--robust` runs ONLY the legs of Student-t PPCA, in one process: the sweep with and
 without the scaled rows, a whole TPPCAModel.iterate, and the passes they are compared with (PPCAModel.llks, the column-scale pass,
-PPCAModel.iterate)."""
+PPCAModel.iterate).  `--hetero` runs ONLY the legs of PPCA with a precision per entry, in one process, alternating:
+the sweep alone (HPPCAModel.llks), a whole HPPCAModel.iterate, PPCAModel.llks and PPCAModel.iterate on the same rows, and the
+device-to-device copy of X whose rate prices the traffic floor of the iteration (X and P read twice, the records written and read
+once)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -141,6 +144,70 @@ def robust_legs(reps=10):
 
 if "--robust" in sys.argv:
     robust_legs()
+    sys.exit(0)
+
+def hetero_legs(reps=10):
+    """HPPCAModel against PPCAModel on the same rows: precisions log-uniform in [2^-10, 2^10] with 10 % zeros and 5 %
+    NaN, made on the device.  Every repetition timed on its own (median, min, max); the legs alternate."""
+    import torch
+
+    hip = C.CDLL(_lib.LIB_PATH)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipDeviceSynchronize.argtypes = []
+
+    def series(fn):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:8.3f} ms  min {ts.min():8.3f}  max {ts.max():8.3f}  ({reps} repetitions)", flush=True)
+        return med
+
+    torch.manual_seed(7)
+    pt = torch.empty((n, d), dtype=torch.float64, device="cuda").uniform_(-10.0 * np.log(2.0), 10.0 * np.log(2.0)).exp_()
+    u = torch.rand((n, d), device="cuda")
+    pt[u < 0.10] = 0.0
+    pt[(u >= 0.10) & (u < 0.15)] = float("nan")
+    del u
+    torch.cuda.synchronize()
+    prec = P.Dataset.from_device(pt.data_ptr(), n, d, ctx=ctx, keepalive=pt)
+    hm = P.HPPCAModel.from_ppca(m)
+    nd_bytes = 8.0 * n * d
+    spare = torch.empty((n, d), dtype=torch.float64, device="cuda")
+    src_p, dst_p = L.ppca_dataset_device_x(ds._h), spare.data_ptr()
+    def copy():
+        assert hip.hipMemcpy(dst_p, src_p, C.c_size_t(int(nd_bytes)), 3) == 0  # hipMemcpyDeviceToDevice
+        assert hip.hipDeviceSynchronize() == 0
+    legs = [("hipMemcpy device to device (N x d)", copy),
+            ("PPCAModel.llks (llks to the host)", lambda: m.llks(ds)),
+            ("HPPCAModel.llks (the sweep alone, llks to the host)", lambda: hm.llks(ds, prec)),
+            ("PPCAModel.iterate", lambda: m.iterate(ds)),
+            ("HPPCAModel.iterate", lambda: hm.iterate(ds, prec))]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn))
+    reps *= 2
+    med = [report(name, np.concatenate(got[name])) for name, _ in legs]
+    rate = 2 * nd_bytes / med[0] / 1e6  # GB/s of the copy (a read and a write)
+    rec = k * (k + 1) // 2 + k + 1
+    rec_pad = 16 * ((rec + 15) // 16)
+    floor_sweep = 2 * nd_bytes / rate / 1e6
+    floor_iter = (4 * nd_bytes + 2 * 8.0 * n * rec) / rate / 1e6
+    print(f"  copy rate {rate:.0f} GB/s; record {rec} doubles per row ({rec_pad} as stored)")
+    print(f"  sweep: floor (X and P once) {floor_sweep:.3f} ms, achieved fraction {floor_sweep / med[2]:.3f};  sweep / PPCAModel.llks = {med[2] / med[1]:.3f}")
+    print(f"  iterate: floor (X and P twice, records once each way) {floor_iter:.3f} ms, achieved fraction {floor_iter / med[4]:.3f}")
+    print(f"  HPPCAModel.iterate / PPCAModel.iterate = {med[4] / med[3]:.3f}   (the statistics contraction and the rest: {med[4] - med[2]:.3f} ms)")
+
+if "--hetero" in sys.argv:
+    hetero_legs()
     sys.exit(0)
 
 def famix_legs(nm, reps=12):
