@@ -1280,28 +1280,9 @@ static int run_post(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, do
         a.recon = recon_dev;
         a.recon_mode = recon_mode;
         if (int rc = qtab_bind(ctx, model, a)) return rc;
-#ifdef PPCA_PHASE_TIMING
-        BufRef dbg;
-        if (int rc = dev_alloc(sizeof(double) * (size_t)grid * 16, &dbg)) return rc;
-        HIP_TRY(hipMemsetAsync(dbg->p, 0, sizeof(double) * (size_t)grid * 16, ctx->stream));
-        a.dbg = static_cast<double *>(dbg->p);
-#endif
         HIP_TRY(launch_pass_post(model->k, grid, a, ctx->stream));
         qtab_commit(ctx, model, fused_gram_mode() != 1);
         HIP_TRY(launch_reduce_partials(scal, grid, 8, scal + (size_t)grid * 8, ctx->stream));
-#ifdef PPCA_PHASE_TIMING
-        if (!states_dev && !covs_dev && !recon_dev) {
-            std::vector<double> h((size_t)grid * 16);
-            HIP_TRY(hipMemcpyAsync(h.data(), a.dbg, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            double t[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (int g = 0; g < grid; ++g)
-                for (int i = 0; i < 16; ++i) t[i] += h[(size_t)g * 16 + i] / grid;
-            const double tiles = (double)((ds->n + FUSED_TILE - 1) / FUSED_TILE) / grid;
-            fprintf(stderr, "[llk2 cycles/tile, thread 0] stage+issue %.0f  barriers %.0f  contract: masks+b %.0f, gram %.0f, stores %.0f  solver %.0f  loop %.0f  (tiles/WG %.1f)\n",
-                    t[0] / tiles, t[1] / tiles, t[4] / tiles, t[5] / tiles, t[2] / tiles, t[3] / tiles, t[7] / tiles, tiles);
-        }
-#endif
     }
     if (scal_out) *scal_out = scal + (size_t)grid * 8;
     return PPCA_OK;
@@ -1533,7 +1514,7 @@ static bool mix_multi_ok(const ppca_dataset *ds, ppca_model *const *models, int 
         return !(e && atoi(e) == 0);
     }();
     if (!on || nm < 1 || nm > MIX_MAX || ds->n <= 0 || ds->n >= ((int64_t)1 << 31)) return false;
-    if (fused_gram_mode() != 0 || !mix_llk8_available()) return false;
+    if (fused_gram_mode() != 0) return false;
     for (int c = 0; c < nm; ++c)
         if (ppca_path_kind(models[c]->d, models[c]->k) != 1 || models[c]->k != models[0]->k) return false;
     return true;

@@ -1,6 +1,7 @@
 // ppca_device.hpp -- device-side helpers shared by the fused-pass kernels (ppca_kernels.hip, ppca_llk.hip):
 // the LDS layout constants of a 32-sample tile, wave reductions on the DPP path, lane-targeted writes, compile-time
-// loops, the fp64 MFMA wrapper and the constants of the int8-sliced Gram table.  Not installed.
+// loops, the fp64 MFMA wrapper and the constants of the int8-sliced Gram table; and the host's dispatch over the state size
+// (PPCA_DISPATCH_K).  Not installed.
 #pragma once
 
 #include <type_traits>
@@ -248,5 +249,29 @@ __host__ __device__ inline void fused_qtab_view(void *base, PassArgs &a) {
     a.cpb = a.cpad + FUSED_MAX_D * (FUSED_MAX_K + 1);
 }
 
+// Host side: EXPR with KK = k as a constant, for every state size the fused kernels are instantiated for.
+#ifdef PPCA_DEV_K10
+// kernel-tuning builds (tools/devbuild.py): only the k = 10 int8-Gram variants are instantiated
+#define PPCA_DISPATCH_K(k, EXPR)                         \
+    switch (k) {                                         \
+        case 10: { constexpr int KK = 10; EXPR; } break; \
+        default: return hipErrorInvalidValue;            \
+    }
+#else
+#define PPCA_DISPATCH_K(k, EXPR)                         \
+    switch (k) {                                         \
+        case 1: { constexpr int KK = 1; EXPR; } break;   \
+        case 2: { constexpr int KK = 2; EXPR; } break;   \
+        case 3: { constexpr int KK = 3; EXPR; } break;   \
+        case 4: { constexpr int KK = 4; EXPR; } break;   \
+        case 5: { constexpr int KK = 5; EXPR; } break;   \
+        case 6: { constexpr int KK = 6; EXPR; } break;   \
+        case 7: { constexpr int KK = 7; EXPR; } break;   \
+        case 8: { constexpr int KK = 8; EXPR; } break;   \
+        case 9: { constexpr int KK = 9; EXPR; } break;   \
+        case 10: { constexpr int KK = 10; EXPR; } break; \
+        default: return hipErrorInvalidValue;            \
+    }
+#endif
 
 }  // namespace ppca

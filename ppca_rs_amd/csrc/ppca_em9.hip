@@ -1296,19 +1296,9 @@ bool em9_covers(int k) {
 
 hipError_t launch_em9(int k, int grid, const PassArgs &a, hipStream_t s) {
     const bool gather = a.rows != nullptr;
-#define PPCA_E9_CASE(KK) \
-    case KK:             \
-        return gather ? launch_em9_t<KK, true, true>(grid, a, s) : (a.w ? launch_em9_t<KK, false, true>(grid, a, s) : launch_em9_t<KK, false, false>(grid, a, s));
-    switch (k) {
-#ifdef PPCA_DEV_K10
-        PPCA_E9_CASE(10)
-#else
-        PPCA_E9_CASE(1) PPCA_E9_CASE(2) PPCA_E9_CASE(3) PPCA_E9_CASE(4) PPCA_E9_CASE(5) PPCA_E9_CASE(6) PPCA_E9_CASE(7)
-        PPCA_E9_CASE(8) PPCA_E9_CASE(9) PPCA_E9_CASE(10)
-#endif
-        default: return hipErrorInvalidValue;
-    }
-#undef PPCA_E9_CASE
+    PPCA_DISPATCH_K(k, return gather ? (launch_em9_t<KK, true, true>(grid, a, s))
+                                     : a.w ? (launch_em9_t<KK, false, true>(grid, a, s)) : (launch_em9_t<KK, false, false>(grid, a, s)));
+    return hipErrorInvalidValue;
 }
 
 }  // namespace ppca

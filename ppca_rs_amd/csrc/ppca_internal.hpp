@@ -195,13 +195,12 @@ hipError_t launch_qprep16(int k, const double *model, int d, double *qscale, sig
 hipError_t launch_em16(int k, int grid, const Em16Launch &a, hipStream_t s);
 // The log-likelihood sweep alone (ppca_llk.hip): per-sample llks (nullable) and the per-workgroup scalars; honours
 // a.qflag like the int8 instantiation of pass_kernel.
-hipError_t launch_llk2(int k, int grid, const PassArgs &a, hipStream_t s);
+hipError_t launch_llk8(int k, int grid, const PassArgs &a, hipStream_t s);
 // PPCAModel::smooth / extrapolate (recon modes 0 / 1) on the same eight-wave sweep (ppca_llk.hip, llk8_run<K, OUT>)
 bool recon8_covers(const PassArgs &a);
 hipError_t launch_recon8(int k, int grid, const PassArgs &a, hipStream_t s);
 // ... of ALL components of a mixture in one launch (same state size k <= FUSED_MAX_K, nm <= MIX_MAX): units = (component, run of
 // tiles), dealt so that the workgroups of one XCD walk the same rows for the different components (X from HBM once per iteration)
-bool mix_llk8_available();  // false under PPCA_LLK8=0
 int mix_llk_runs_per_xcd(int grid, int nm);
 hipError_t launch_mix_llk8(int k, int grid, const MixLlkArgs &a, hipStream_t s);
 // the fp64-Gram instantiation of the post pass alone, behind a.qflag (the fallback of the int8 llk sweeps: returns at once unless the

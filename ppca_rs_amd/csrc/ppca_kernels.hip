@@ -1928,14 +1928,6 @@ static int gram_mode() {
     return v;
 }
 
-static bool llk2_enabled() {
-    static const bool v = [] {
-        const char *e = getenv("PPCA_LLK2");
-        return !(e && atoi(e) == 0);
-    }();
-    return v;
-}
-
 // Slice table + guard flags of the current model (device-side, no host sync), then the pass: the int8 variant and,
 // behind the guard, the fp64 variant -- each returns at once unless qflag selects it.
 template <int K, bool EM>
@@ -1951,9 +1943,9 @@ static hipError_t launch_pass_guarded(int grid, PassArgs a, hipStream_t s) {
 #endif
     if (!a.skip_qprep) hipLaunchKernelGGL((qprep_kernel<K>), dim3(Cfg<K>::NTP), dim3(256), 0, s, a.model, a.d, a.qscale, a.qtab, a.qflag);
     auto int8_pass = [&](const PassArgs &b) {
-        if constexpr (!EM) {  // llk / llks alone: the two-tile sweep (ppca_llk.hip) unless PPCA_LLK2=0
-            if (!b.states && !b.covs && !b.recon && llk2_enabled()) return launch_llk2(K, grid, b, s);
-            if (recon8_covers(b)) return launch_recon8(K, grid, b, s);  // smooth / extrapolate on the eight-wave sweep (round 6)
+        if constexpr (!EM) {
+            if (!b.states && !b.covs && !b.recon) return launch_llk8(K, grid, b, s);  // llk / llks alone: the eight-wave sweep (ppca_llk.hip)
+            if (recon8_covers(b)) return launch_recon8(K, grid, b, s);  // smooth / extrapolate on the same sweep (round 6)
         }
         if constexpr (EM) return launch_em9(K, grid, b, s);  // eight waves, two roles, the solve pipelined across tiles (ppca_em9.hip)
         else return launch_pass_t<K, EM, 4, true>(grid, b, s);
@@ -1970,30 +1962,6 @@ static hipError_t launch_pass_guarded(int grid, PassArgs a, hipStream_t s) {
     return launch_pass_t<K, EM, 4, false>(grid, a, s);
 #endif
 }
-
-#ifdef PPCA_DEV_K10
-// kernel-tuning builds (tools/devbuild.py): only the k = 10 int8-Gram variants are instantiated
-#define PPCA_DISPATCH_K(k, EXPR)                         \
-    switch (k) {                                         \
-        case 10: { constexpr int KK = 10; EXPR; } break; \
-        default: return hipErrorInvalidValue;            \
-    }
-#else
-#define PPCA_DISPATCH_K(k, EXPR)                         \
-    switch (k) {                                         \
-        case 1: { constexpr int KK = 1; EXPR; } break;   \
-        case 2: { constexpr int KK = 2; EXPR; } break;   \
-        case 3: { constexpr int KK = 3; EXPR; } break;   \
-        case 4: { constexpr int KK = 4; EXPR; } break;   \
-        case 5: { constexpr int KK = 5; EXPR; } break;   \
-        case 6: { constexpr int KK = 6; EXPR; } break;   \
-        case 7: { constexpr int KK = 7; EXPR; } break;   \
-        case 8: { constexpr int KK = 8; EXPR; } break;   \
-        case 9: { constexpr int KK = 9; EXPR; } break;   \
-        case 10: { constexpr int KK = 10; EXPR; } break; \
-        default: return hipErrorInvalidValue;            \
-    }
-#endif
 
 hipError_t launch_pass_em(int k, int grid, const PassArgs &a, hipStream_t s) {
     // (the eight-wave fp64-Gram instantiation of pass_kernel that PPCA_FUSED_WAVES=8 used to select is gone: it ignored

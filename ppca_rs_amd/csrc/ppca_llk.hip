@@ -1,30 +1,39 @@
 // ppca_llk.hip -- the log-likelihood sweep (PPCAModel::llk / llks, ppca/src/ppca_model.rs:124-159, on
 // OutputCovariance::quadratic_form / covariance_log_det, ppca/src/output_covariance.rs:115-142) as its own kernel for
 // the fused shapes (d <= 256, k <= 10).  It is the pass a mixture step runs once per component and per iteration
-// (PPCAMix::iterate_with_prior, ppca/src/mix.rs:283-288) and the trainers' metric.
+// (PPCAMix::iterate_with_prior, ppca/src/mix.rs:283-288) and the trainers' metric.  Three kernels share its body, llk8_run:
+// llk8_kernel (one model), mix_llk8_kernel (all components of a mixture in one launch) and recon8_kernel (the N x d outputs
+// PPCAModel::smooth / extrapolate on the same sweep).
 //
-// pass_kernel<K, false, ...> serves this request with its general machinery: a 32-sample tile, the solver on 32 of 64
+// pass_kernel<K, false, ...> can serve the request with its general machinery: a 32-sample tile, the solver on 32 of 64
 // lanes in every one of four waves, z by two substitutions, and room for the posterior / reconstruction outputs.  The
-// llk of a sample needs only  m, |x~|^2, ln det M  and  quad = b^T M^-1 b = |L^-1 b|^2, and with one wave per SIMD
-// every instruction of a wave -- scalar ones included -- costs an issue slot of ~4 cycles (measured: the staging of a
-// tile took 4.07 cycles per instruction of any kind), so this kernel is built to issue few of them:
-//   * TWO tiles per round: P1 / P2 of tile A, P1 / P2 of tile B (the x~ tile is free again after a tile's P2: nothing
-//     reads it later in this pass), then ONE solver step for the 64 samples on all 64 lanes of wave 0 -- factorisation
-//     + the forward substitution only; the observed counts are popcounts of the mask words, taken there;
-//   * the wave's slice of the int8 digit table (8 slices x 4 k-chunks x 16 bytes per lane = 128 registers; there are
-//     no statistics accumulators in this pass) is loaded ONCE per workgroup and stays in registers: no table traffic
-//     and no load latency inside the tile loop;
-//   * staging without scalar work: the finite test |x| < lim (lim = +inf, or -1 for the padding past d) gives the wave
-//     mask that is both the select predicate and, as it comes, mask word 2 h + e of the row (qprep orders the table
-//     rows to match); a tile's rows are addressed through ONE buffer descriptor with a scalar offset per row (rows
-//     past the end read as zeros and are never somebody's sample); the eight per-lane |x~|^2 partials of a wave's rows
-//     are summed together (v_permlane32_swap / v_permlane16_swap fold two rows per add, then four DPP steps for the
-//     last two registers) instead of one six-step reduction per row;
-//   * the next tile's rows are requested as soon as the registers of the previous one are staged, so they travel
-//     under a whole P2.
-// Per-sample arithmetic is that of pass_kernel except for the ORDER of the |x~|^2 sum (same int8-sliced Gram behind
-// the same guard, same Cholesky), so the llks agree with it to rounding.  The guard's fallback is
+// llk of a sample needs only  m, |x~|^2, ln det M  and  quad = b^T M^-1 b = |L^-1 b|^2, and a wave is issue-bound: with
+// one wave per SIMD every instruction -- scalar ones included -- costs an issue slot of ~4 cycles (measured: the staging
+// of a tile took 4.07 cycles per instruction of any kind), and a vector instruction leaves every ~5-8 cycles (dependent
+// chains, LDS waits).  So the sweep is built to issue few instructions and to fill the slots it leaves:
+//   * an EIGHT-wave workgroup, two waves per SIMD with 256 registers each: the second wave takes the slots the first leaves;
+//   * TWO tiles per round and ONE solver step for their 64 samples on all 64 lanes of one wave -- factorisation + the
+//     forward substitution only; the observed counts are popcounts of the mask words, taken there;
+//   * the work of a tile split by ROLES: waves 0-3 the int8 Gram of packed-column tile ct = wave for BOTH row tiles, with the
+//     slice of the int8 digit table of THEIR column tile (8 slices x 4 k-chunks x 16 bytes per lane = 128 registers; there are
+//     no statistics accumulators in this pass) loaded once and resident: no table traffic and no load latency inside the
+//     tile loop; waves 4-7 b = X~ C of one row tile for one HALF of the dimensions, the two K-split partials summed by the
+//     solver in a fixed order.  Wave w and w + 4 share a SIMD.  The solver step runs on a b wave (wave 4), which holds no
+//     slice: next to the packed factor (110 registers) it could not keep one;
+//   * staging without scalar work, four rows per wave: the finite test |x| < lim (lim = +inf, or -1 for the padding past d)
+//     gives the wave mask that is both the select predicate and, as it comes, mask word 2 h + e of the row (qprep orders the
+//     table rows to match); a tile's rows are addressed through ONE buffer descriptor with a scalar offset per row (rows
+//     past the end read as zeros and are never somebody's sample); the per-lane |x~|^2 partials of a wave's rows are summed
+//     together (v_permlane32_swap / v_permlane16_swap fold two rows per add, then four DPP steps) instead of one six-step
+//     reduction per row;
+//   * rows requested early: the next tile's rows are requested as soon as the registers of the previous one are staged, so
+//     they travel under a whole contraction, and one dword of each of their lines is touched a round before that (touch_tile);
+//   * the first tile of round r + 1 is staged by seven waves WHILE the solver wave works on round r; the solver wave hands
+//     its four rows to four other waves through LDS (llk8_run's round comment).
+// Per-sample arithmetic is that of pass_kernel except for the ORDER of the |x~|^2 sum and of the b partials (same
+// int8-sliced Gram behind the same guard, same Cholesky), so the llks agree with it to rounding.  The guard's fallback is
 // pass_kernel<K, false, 4, false>.
+// (llk2_kernel, the four-wave form of this sweep of rounds 2-3 -- two tiles per round, every wave a Gram and a b unit -- last existed in commit e1e9872.)
 #include <cstdlib>
 
 #include "ppca_device.hpp"
@@ -32,310 +41,13 @@
 namespace ppca {
 
 template <int K>
-struct CfgL {
-    using c = Cfg<K>;
-    static constexpr int KP = c::KP, NTP = c::NTP, B = c::B, DP = c::DP, XS = c::XS, CS = c::CS;
-    static constexpr int GS = 16 * NTP + 16 + 1;  // [G (16 NTP) | b partial of dims 0-127 (16)], 2 B rows
-    static constexpr int BS = 17;                 // b partial of dims 128-255, 2 B rows
-    static constexpr int OFF_X = 0;
-    static constexpr int OFF_C = OFF_X + B * XS;
-    static constexpr int OFF_G = OFF_C + DP * CS;
-    static constexpr int OFF_B1 = OFF_G + 2 * B * GS;
-    static constexpr int OFF_M = OFF_B1 + 2 * B * BS;   // mask words of the round's two tiles, 2 B x 4 u64
-    static constexpr int OFF_XX = OFF_M + 2 * B * 4;    // |x~|^2 of the 2 B samples
-    static constexpr int LDS_DOUBLES = OFF_XX + 2 * B;
-};
-
-template <int K>
-__global__ __launch_bounds__(256) void llk2_kernel(PassArgs p) {
-    using cfg = CfgL<K>;
-    constexpr int KP = cfg::KP, NTP = cfg::NTP, B = cfg::B, XS = cfg::XS, CS = cfg::CS, GS = cfg::GS, BS = cfg::BS;
-    constexpr int NW = 4, RPW = B / NW, DPS = cfg::DP / 2, STEPS = DPS / 4;
-    static_assert(NTP <= NW && QS == 8 && RPW == 8, "int8 Gram: one wave per packed-column tile, 8 digit slices; 8 rows per wave");
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double *Xs = sm + cfg::OFF_X;
-    double *Cs = sm + cfg::OFF_C;
-    double *Gs = sm + cfg::OFF_G;
-    double *B1 = sm + cfg::OFF_B1;
-    unsigned long long *Ms = reinterpret_cast<unsigned long long *>(sm + cfg::OFF_M);
-    double *xxs = sm + cfg::OFF_XX;
-
-    if (p.qflag) {  // qprep's dynamic-range guard: pass_kernel<K, false, 4, false> runs instead
-        int unsafe = 0;
-#pragma unroll
-        for (int t = 0; t < NTP; ++t) unsafe |= p.qflag[t];
-        if (unsafe) return;
-    }
-    const int tid = threadIdx.x, lane_entry = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int d = p.d;
-    const int64_t n = p.n;
-    const double *mC = p.model + MODEL_HDR;
-    const double *mMean = mC + (int64_t)d * K;
-    const double s2 = p.model[1], lnsig = p.model[2];
-    for (int idx = tid; idx < cfg::DP * CS; idx += 256) {
-        int j = idx / CS, a = idx - j * CS;
-        Cs[idx] = (j < d && a < K) ? mC[(int64_t)j * K + a] : 0.0;
-    }
-    // staging lane map: lane l holds dims 128 h + 2 l + e (element q = 2 h + e) of a row; observed <=> |x| < lim
-    double mu[4], lim[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int j = 128 * (q >> 1) + 2 * lane_entry + (q & 1);
-        mu[q] = (j < d) ? mMean[j] : 0.0;
-        lim[q] = (j < d) ? __builtin_inf() : -1.0;
-    }
-
-    const int64_t ntiles = (n + B - 1) / B;
-    const int64_t tiles_per_wg = (ntiles + gridDim.x - 1) / gridDim.x;
-    const int64_t tile_begin = (int64_t)blockIdx.x * tiles_per_wg;
-    const int64_t tile_end = tile_begin + tiles_per_wg < ntiles ? tile_begin + tiles_per_wg : ntiles;
-    const int64_t nleft = n - tile_begin * B;
-    const int nrel = (int)(nleft < (1 << 30) ? nleft : (1 << 30));  // rows from the workgroup's first row to the end
-    const double *Xwg = p.X + tile_begin * B * p.ldx;
-    const int rowbytes = d * (int)sizeof(double);  // rows are contiguous (ldx == d)
-#ifdef PPCA_PHASE_TIMING
-    long long tph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = clock64();
-#define LLK_STAMP(i) { long long tn = clock64(); tph[i] += tn - tlast; tlast = tn; }
-#else
-#define LLK_STAMP(i)
-#endif
-    double xr[RPW][4];
-    // One descriptor per tile (base = its first row, extent = its real rows): the row is a scalar offset, the lane
-    // a constant VGPR, the half an immediate.  Rows past n read as zeros ("observed", but no lane's sample).
-    auto load_tile = [&](int64_t tile) {
-        const int rel0 = (int)(tile - tile_begin) * B;
-        int cnt = nrel - rel0;
-        cnt = __builtin_amdgcn_readfirstlane(cnt < 0 ? 0 : (cnt > B ? B : cnt));  // (keeps the descriptor scalar)
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<double *>(Xwg + (int64_t)rel0 * p.ldx), 0, cnt * rowbytes, 0x00020000);
-        const int wbase = wave * RPW * rowbytes;
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-                const u4_t v = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, lane_entry * 16, wbase + r * rowbytes + 1024 * h, 0);
-                xr[r][2 * h] = __longlong_as_double(((long long)v[1] << 32) | v[0]);
-                xr[r][2 * h + 1] = __longlong_as_double(((long long)v[3] << 32) | v[2]);
-            }
-        }
-    };
-    // The wave's slice of the digit table, resident: fragment (slice sl, k-chunk kc) = 16 bytes per lane.  Waves
-    // without a column tile (k' <= 48) read past the table (zeros), run the same MFMAs and skip only the store.
-    const bool gram_wave = NTP >= NW || wave < NTP;
-    i4_t qt[QS][4];
-    {
-        const __amdgpu_buffer_rsrc_t qrsrc = __builtin_amdgcn_make_buffer_rsrc(p.qtab, 0, (int)qtab_bytes<K>(), 0x00020000);
-        const int qbase = wave * QS * 4 * 1024;
-#pragma unroll
-        for (int sl = 0; sl < QS; ++sl)
-#pragma unroll
-            for (int kc = 0; kc < 4; ++kc) {
-                typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-                const u4_t v = __builtin_amdgcn_raw_buffer_load_b128(qrsrc, lane_entry * 16, qbase + (sl * 4 + kc) * 1024, 0);
-                qt[sl][kc] = i4_t{(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
-            }
-    }
-    const double qs = gram_wave ? p.qscale[16 * wave + (lane_entry & 15)] : 0.0;
-
-    // ---- P1: stage one tile (slot 0 / 1 of the round): x~ into the LDS tile, mask words, |x~|^2 per sample
-    auto stage_tile = [&](int lane, int slot) {
-        int st_wlo = 0, st_whi = 0;
-        double pxx[RPW];
-        static_for<RPW>([&](auto r_tag) {
-            constexpr int r = decltype(r_tag)::value;
-            const int ri = wave * RPW + r;
-            double xt[4];
-            static_for<4>([&](auto q_tag) {
-                constexpr int q = decltype(q_tag)::value;
-                const double v = xr[r][q];
-                const bool ob = __builtin_fabs(v) < lim[q];  // finite (dataset.rs:19-22) and a real dimension
-                xt[q] = ob ? v - mu[q] : 0.0;                // select, never multiply (utils.rs:118-127)
-                // mask word q of the row = this ballot as it comes (bit l <-> dim 128 h + 2 l + e), into lane 4 r + q
-                writelane_mask<4 * r + q>(st_wlo, st_whi, __builtin_amdgcn_ballot_w64(ob));
-            });
-            typedef double d2_t __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<d2_t *>(Xs + ri * XS + 2 * lane) = d2_t{xt[0], xt[1]};
-            *reinterpret_cast<d2_t *>(Xs + ri * XS + 128 + 2 * lane) = d2_t{xt[2], xt[3]};
-            pxx[r] = xt[0] * xt[0] + xt[1] * xt[1] + xt[2] * xt[2] + xt[3] * xt[3];
-        });
-        const unsigned long long myw = ((unsigned long long)(unsigned)st_whi << 32) | (unsigned)st_wlo;
-        if (lane < 4 * RPW) Ms[(slot * B + wave * RPW) * 4 + lane] = myw;
-        store_row_sums(pxx, lane, xxs + slot * B + wave * RPW);
-    };
-    // ---- P2: [G | b] of the staged tile into rows slot * B .. of the exchange buffers
-    auto contract_tile = [&](int lane, int slot) {
-        const int l15 = lane & 15, l4 = lane >> 4;
-        const int colb = (l15 < K) ? l15 : K;
-        const int rt = wave & 1, kq = wave >> 1;
-        const int si = 16 * rt + l15;
-        d4_t accb = d4_t{0, 0, 0, 0};
-        const double *xrow = Xs + si * XS + DPS * kq + l4;
-        const double *cpc = Cs + (DPS * kq + l4) * CS + colb;
-        // A = mask bytes: lane (sample = 16 rt2 + l15, k = 64 kc + 16 l4 .. +15 of word kc); 4 bits -> 4 bytes by
-        // one multiply: (x * 0x204081) & 0x01010101 puts bit i of x into byte i
-        i4_t af[2][4];
-        unsigned long long mwd[2][4];
-#pragma unroll
-        for (int rt2 = 0; rt2 < 2; ++rt2)
-#pragma unroll
-            for (int kc = 0; kc < 4; ++kc) mwd[rt2][kc] = Ms[(slot * B + 16 * rt2 + l15) * 4 + kc];
-        {
-            // b = X~ C first: its operands are requested four k-steps ahead, and the mask words arrive under it
-            constexpr int CH = 4;
-            double axb[2][CH], cbb[2][CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                axb[0][u] = xrow[4 * u];
-                cbb[0][u] = cpc[4 * u * CS];
-            }
-#pragma unroll
-            for (int c = 0; c < STEPS / CH; ++c) {
-                if (c + 1 < STEPS / CH) {
-#pragma unroll
-                    for (int u = 0; u < CH; ++u) {
-                        axb[(c + 1) & 1][u] = xrow[4 * ((c + 1) * CH + u)];
-                        cbb[(c + 1) & 1][u] = cpc[4 * ((c + 1) * CH + u) * CS];
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < CH; ++u) accb = mfma(axb[c & 1][u], cbb[c & 1][u], accb);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        LLK_STAMP(4)
-#pragma unroll
-        for (int rt2 = 0; rt2 < 2; ++rt2)
-#pragma unroll
-            for (int kc = 0; kc < 4; ++kc) {
-                const unsigned bits = (unsigned)(mwd[rt2][kc] >> (16 * l4)) & 0xFFFFu;
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    af[rt2][kc][u] = (int)((((bits >> (4 * u)) & 0xFu) * 0x00204081u) & 0x01010101u);
-            }
-        // digit pairs high to low: exact integer sums (|sum| <= 2^14 per digit, two digits per i32), folded into the
-        // running fp64 value by Horner in 128^2
-        double v[2][4];
-#pragma unroll
-        for (int g = 0; g < QS / 2; ++g) {
-            const int sl = QS - 2 - 2 * g;
-#pragma unroll
-            for (int rt2 = 0; rt2 < 2; ++rt2) {
-                i4_t ia[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    ia[u] = i4_t{0, 0, 0, 0};
-#pragma unroll
-                    for (int kc = 0; kc < 4; ++kc)
-                        ia[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[rt2][kc], qt[sl + u][kc], ia[u], 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int part = ia[1][r] * QBASE + ia[0][r];
-                    v[rt2][r] = g == 0 ? (double)part : v[rt2][r] * (double)(QBASE * QBASE) + (double)part;
-                }
-            }
-        }
-        LLK_STAMP(5)
-        if (gram_wave) {
-#pragma unroll
-            for (int rt2 = 0; rt2 < 2; ++rt2)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)  // C/D map of the 16x16 integer MFMA: row = 4 (lane >> 4) + reg
-                    Gs[(slot * B + 16 * rt2 + 4 * l4 + r) * GS + 16 * wave + l15] = v[rt2][r] * qs;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {  // the K-split partials of b, summed by the solver in a fixed order (p0 + p1)
-            if (kq == 0) Gs[(slot * B + 16 * rt + l4 + 4 * r) * GS + 16 * NTP + l15] = accb[r];
-            else B1[(slot * B + 16 * rt + l4 + 4 * r) * BS + l15] = accb[r];
-        }
-    };
-
-    double run_llk = 0.0, run_w = 0.0;  // wave 0: running sums of its lane's samples
-    if (tile_begin < tile_end) load_tile(tile_begin);
-    __syncthreads();
-    for (int64_t tile = tile_begin; tile < tile_end; tile += 2) {
-        int lane = lane_entry;
-        asm volatile("" : "+v"(lane));
-        LLK_STAMP(7)
-        stage_tile(lane, 0);
-        load_tile(tile + 1);  // travels under the contraction below
-        LLK_STAMP(0)
-        __syncthreads();
-        LLK_STAMP(1)
-        contract_tile(lane, 0);
-        LLK_STAMP(2)
-        __syncthreads();
-        LLK_STAMP(1)
-        stage_tile(lane, 1);
-        load_tile(tile + 2);
-        LLK_STAMP(0)
-        __syncthreads();
-        LLK_STAMP(1)
-        contract_tile(lane, 1);
-        LLK_STAMP(2)
-        __syncthreads();
-        LLK_STAMP(1)
-        if (wave == 0) {
-            // ---- P3: lane i < 32 -> sample i of tile, lane i >= 32 -> sample i - 32 of tile + 1
-            const int slot = lane >> 5, i = lane & (B - 1);
-            const int64_t t = tile + slot;
-            const int64_t row = t * B + i;
-            const bool mine = t < tile_end && row < n;
-            const double *g0 = Gs + lane * GS;
-            const double *b1 = B1 + lane * BS;
-            const double wgt = mine ? (p.w ? p.w[row] : 1.0) : 0.0;
-            const unsigned long long *mw = Ms + lane * 4;
-            const int m = __popcll(mw[0]) + __popcll(mw[1]) + __popcll(mw[2]) + __popcll(mw[3]);
-            const double xx = xxs[lane];
-            Posterior<K> post;
-            double pm;
-            int pe;
-            post.factor([&](int e) { return g0[e]; }, s2, pm, pe);
-            const double quad = post.forward_quad([&](int a) { return g0[16 * NTP + a] + b1[a]; });
-            const double lk = sample_llk(xx, quad, Posterior<K>::logdet(pm, pe), s2, lnsig, m, K);
-            run_llk += wgt * lk;
-            run_w += wgt;
-            if (p.llks && mine) p.llks[row] = lk;
-        }
-        LLK_STAMP(3)
-        __syncthreads();
-    }
-#ifdef PPCA_PHASE_TIMING
-    if (p.dbg && tid == 0)
-        for (int i = 0; i < 16; ++i) p.dbg[(int64_t)blockIdx.x * 16 + i] = (double)tph[i];
-#endif
-    if (wave == 0) {
-        const double v2 = wave_sum(run_llk), v3 = wave_sum(run_w);
-        if (lane_entry == 0) {
-            double *sc = p.scal_part + (int64_t)blockIdx.x * 8;
-            sc[SC_SQERR] = 0.0;
-            sc[SC_DEVSQ] = 0.0;
-            sc[SC_LLK] = v2;
-            sc[SC_SUMW] = v3;
-            sc[SC_NONEMPTY] = 0.0;
-            sc[5] = 0.0;
-            sc[6] = 0.0;
-            sc[7] = 0.0;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// llk8_kernel -- the same sweep as an EIGHT-wave workgroup (two waves per SIMD, 256 registers each; round 4).  One wave per
-// SIMD issues a vector instruction every ~5-8 cycles (dependent chains, LDS waits); a second wave fills those slots.  The
-// work of a tile is split eight ways instead of four: four staged rows per wave; the int8 Gram as (packed-column tile, row
-// tile) = 4 x 2 wave units, each with ITS column tile's digit-table slice resident (128 registers, as in llk2_kernel); b = X~ C
-// as (row tile, quarter of the dimensions) = 2 x 4 units, the four K-split partials summed by the solver in a fixed order.
-// The solver step (64 samples of the round's two tiles on the 64 lanes of wave 0) is unchanged.
-template <int K>
 struct CfgL8 {
     using c = Cfg<K>;
     static constexpr int KP = c::KP, NTP = c::NTP, B = c::B, DP = c::DP, XS = c::XS, CS = c::CS;
-    static constexpr int GS = 16 * NTP + 16 + 1;  // [G (16 NTP) | b partial of dims 0-63 (16)], 2 B rows
-    static constexpr int BS = 17;                 // b partials of dims 64-127, 128-191, 192-255: 3 x 2 B rows
+    static constexpr int GS = 16 * NTP + 16 + 1;  // [G (16 NTP) | b partial of dims 0-127 (16)], 2 B rows
+    // b partial of dims 128-255: the first of 3 blocks of 2 B rows.  The other two held the partials of rounds 4-5, when b was split in
+    // quarters; nothing writes them now, and they stay reserved because moving an offset changes the code
+    static constexpr int BS = 17;
     static constexpr int OFF_X = 0;
     static constexpr int OFF_C = OFF_X + B * XS;
     static constexpr int OFF_G = OFF_C + DP * CS;
@@ -376,15 +88,16 @@ __device__ __forceinline__ void store_row_sums4(const double (&pxx)[4], int lane
 // runs the back substitution (z = M^-1 b into the sample's dead b-partial slots), then every wave forms eight of the round's 64 output
 // rows with the lane map of the staging (lane l: dims 128 h + 2 l, + 1: its two rows of C in registers, z broadcast from LDS, K
 // multiply-adds per element) and stores them as whole 16-byte pieces, 1 KB per instruction; extrapolate re-reads the rows (L2: they
-// were staged a round ago) and selects by the mask words still in LDS -- bit-exact pass-through.  The waves drop their table slices
-// for that phase and request them again behind it, as the solver wave always did.  Needs an even d (16-byte pieces).  The four-wave
+// were staged a round ago) and selects by the mask words still in LDS -- bit-exact pass-through.  The Gram waves drop their table slices
+// for that phase and request them again behind it (32 loads from L2).  Needs an even d (16-byte pieces).  The four-wave
 // pass_kernel<K, false> (5.3 / 5.7 ms at N = 4 M) formed the outputs on the fp64 MFMA, moved them through LDS and stored 8 bytes per lane.
 template <int K, int OUT = 0>
 __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const int64_t tile_begin, const int64_t tile_end, double *scal) {
     using cfg = CfgL8<K>;
     constexpr int KP = cfg::KP, NTP = cfg::NTP, B = cfg::B, XS = cfg::XS, CS = cfg::CS, GS = cfg::GS, BS = cfg::BS;
-    constexpr int NW = 8, RPW = B / NW, DPQ = cfg::DP / 4, STEPS = DPQ / 4;
-    static_assert(NTP <= 4 && QS == 8 && RPW == 4, "int8 Gram: (column tile, row tile) wave units, 8 digit slices; 4 rows per wave");
+    constexpr int NW = 8, RPW = B / NW, DPH = cfg::DP / 2, NST = DPH / 4;  // a b wave: half of the dimensions in NST k-steps of 4
+    constexpr int SOLVER = 4;  // the wave of the solver step: a b wave, its SIMD's other wave is Gram wave 0
+    static_assert(NTP <= 4 && QS == 8 && RPW == 4, "int8 Gram: one wave per packed-column tile, 8 digit slices; 4 rows per wave");
     double *Xs = sm + cfg::OFF_X;
     double *Cs = sm + cfg::OFF_C;
     double *Gs = sm + cfg::OFF_G;
@@ -433,7 +146,7 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
     // (round 6) One dword of every 128-byte line of the wave's four rows of a tile, a round before the rows themselves are requested:
     // since the first tile of round r + 1 is staged in round r's solver phase its rows are wanted a solver step EARLIER than before,
     // and the register set that receives them is free only one contraction ahead -- less than an HBM round trip (the phase table
-    // showed wave 0 standing ~4 k cycles at its hand-off).  The touch brings the lines into the XCD's L2 (one instruction, one
+    // showed the solver wave standing ~4 k cycles at its hand-off).  The touch brings the lines into the XCD's L2 (one instruction, one
     // register whose value only keeps the load alive); the 16-byte requests that follow are L2 hits.
     int pf_acc = 0;
     auto touch_tile = [&](int64_t tile) {
@@ -444,24 +157,14 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
             const_cast<double *>(Xwg + (int64_t)rel0 * p.ldx), 0, cnt * rowbytes, 0x00020000);
         pf_acc |= (int)__builtin_amdgcn_raw_buffer_load_b32(xrsrc, lane_entry * 128, wave * RPW * rowbytes, 0);
     };
-    // Contraction units.  LLK8_ROLES = 0 (rounds 4-5): every wave one Gram unit (packed-column tile ct, row tile rt) + one b unit (row
-    // tile rtb, quarter kq of the dimensions).  LLK8_ROLES = 1 (round 6): waves 0-3 the Gram of column tile ct = wave for BOTH row tiles
-    // (one table slice, two units), waves 4-7 b of row tile rtb for one HALF of the dimensions (two of the old units in one loop: two
-    // K-split partials instead of four).  The same MFMAs per SIMD (wave w and w + 4 share one); what it buys: the solver step runs on a
-    // b wave (wave 4), which holds no table slice -- the solver wave of rounds 4-5 dropped its slice for the solver step and requested
-    // the 32 KB again behind it, ~2 k cycles of request issue on the round's critical path (phase table of the LLK8_TIMING build).
-#ifndef LLK8_ROLES
-#define LLK8_ROLES 1
-#endif
-    constexpr bool ROLES = LLK8_ROLES != 0;
-    constexpr int SOLVER = ROLES ? 4 : 0;
-    const int ct = wave & 3, rt = wave >> 2;
-    const int rtb = wave & 1, kq = wave >> 1;
-    const bool is_gram = !ROLES || wave < 4, is_b = !ROLES || wave >= 4;
+    // Contraction units: waves 0-3 the Gram of column tile ct = wave for BOTH row tiles (one table slice, two units), waves 4-7 b of row
+    // tile rtb for one HALF of the dimensions.  Until round 6 every wave had one Gram unit and one b unit of a quarter of the dimensions;
+    // the MFMAs per SIMD are the same.  What the roles buy: the solver wave of rounds 4-5 held a slice, dropped it for the solver step and
+    // requested the 32 KB again behind it, ~2 k cycles of request issue on the round's critical path (phase table of the LLK8_TIMING build).
+    const int ct = wave & 3, rtb = wave & 1;
+    const bool is_gram = wave < 4, is_b = wave >= 4;
     const bool gram_wave = is_gram && ct < NTP;
-    // the unit's slice of the digit table, resident (128 registers).  The solver wave cannot hold it next to the packed
-    // factor (110 registers): it drops the slice for its solver step and requests it again right after (32 loads from
-    // L2 that travel under the next staging) -- a spill through scratch would wait on the row loads in flight instead.
+    // the Gram wave's slice of the digit table, resident (128 registers)
     i4_t qt[QS][4];
     auto load_table = [&]() {
         const __amdgpu_buffer_rsrc_t qrsrc = __builtin_amdgcn_make_buffer_rsrc(p.qtab, 0, (int)qtab_bytes<K>(), 0x00020000);
@@ -534,9 +237,8 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
         if (is_b) {
             // the unit: row tile rb, dimensions [dim0, dim0 + 4 NST); its partial of b goes to the row's b slots (part 0) or to B1
             const int rb = rtb;
-            const int part = ROLES ? (wave - 4) >> 1 : kq;
-            constexpr int NST = ROLES ? 2 * STEPS : STEPS;
-            const int dim0 = (ROLES ? 2 * DPQ : DPQ) * part;
+            const int part = (wave - 4) >> 1;
+            const int dim0 = DPH * part;
             double accb[NCB];
             int ccol[NCB];
 #pragma unroll
@@ -578,13 +280,13 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
             for (int c = 0; c < NCB; ++c) {
                 const int col = 4 * c + (lane & 3);
                 if (part == 0) Gs[row * GS + 16 * NTP + col] = accb[c];
-                else B1[((part - 1) * 2 * B + row) * BS + col] = accb[c];
+                else B1[((part - 1) * 2 * B + row) * BS + col] = accb[c];  // (part = 1: the first block of B1)
             }
         }
         if (is_gram) {
-            // Gram units of this wave: column tile ct, row tile rg
-            static_for<ROLES ? 2 : 1>([&](auto u_tag) {
-                const int rg = ROLES ? decltype(u_tag)::value : rt;
+            // Gram units of this wave: column tile ct, row tiles rg = 0, 1
+            static_for<2>([&](auto u_tag) {
+                const int rg = decltype(u_tag)::value;
                 unsigned long long mwd[4];
 #pragma unroll
                 for (int kc = 0; kc < 4; ++kc) mwd[kc] = Ms[(mr + 16 * rg + l15) * 4 + kc];
@@ -649,11 +351,11 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
     unsigned handed = 0u;  // rounds whose solver wave has handed its rows of the next first tile over
 
     // Round r: [its first tile was staged during round r - 1's solver step] contract A, stage B, contract B, then the solver step of
-    // the round's 64 samples on wave 0 WHILE the other seven waves stage the first tile of round r + 1 (wave 0 stages its four rows
-    // behind its solver step).  Until round 6 the other waves stood at the barrier during the solver step (a sixth of the round by
+    // the round's 64 samples on wave SOLVER WHILE the other seven waves stage the first tile of round r + 1 and four of them one of the
+    // solver wave's four rows each, handed over through the x~ tile.  Until round 6 the other waves stood at the barrier during the solver step (a sixth of the round by
     // ablation, a build without the step's arithmetic: 2.36 -> 1.97 ms at N = 4 M) and everybody staged the first tile afterwards
     // (another sixth, a build without that staging: 1.98 ms).
-#ifdef LLK8_TIMING  // (diagnostic build: per-phase cycle sums of wave 0 -- and the overlapped staging of wave 1 -- into the scalars)
+#ifdef LLK8_TIMING  // (diagnostic build: per-phase cycle sums of the solver wave -- and the overlapped staging of wave 1 -- into the scalars)
     long long tq[6] = {0, 0, 0, 0, 0, 0}, tl = clock64();
 #define L8_STAMP(i) { __builtin_amdgcn_sched_barrier(0); const long long tn = clock64(); tq[i] += tn - tl; tl = tn; __builtin_amdgcn_sched_barrier(0); }
 #else
@@ -672,10 +374,8 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
         int lane = lane_entry;
         asm volatile("" : "+v"(lane));
         L8_STAMP(5)
-#ifndef LLK8_NO_TOUCH
         touch_tile(tile + 2);
         touch_tile(tile + 3);
-#endif
         contract_tile(lane, 0, par);
         L8_STAMP(0)
         __syncthreads();
@@ -717,23 +417,23 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
             double pm;
             int pe;
             post.factor([&](int e) { return g0[e]; }, s2, pm, pe);
+            auto b_of = [&](int a) { return g0[16 * NTP + a] + b1[a]; };  // the two K-split partials, in this order
             if constexpr (OUT == 0) {
-                const double quad = post.forward_quad([&](int a) { return ROLES ? g0[16 * NTP + a] + b1[a] : ((g0[16 * NTP + a] + b1[a]) + b1[2 * B * BS + a]) + b1[4 * B * BS + a]; });
+                const double quad = post.forward_quad(b_of);
                 const double lk = sample_llk(xx, quad, lean_log(pm) + (double)pe * LN_2, s2, lnsig, m, K);
                 run_llk += wgt * lk;
                 run_w += wgt;
                 if (p.llks && mine) p.llks[row] = lk;
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!ROLES) load_table();
-                else kill_table();  // (LLK8_ROLES = 1: the solver wave is a b wave and holds no slice)
+                kill_table();  // (the solver wave is a b wave and holds no slice)
             } else {
                 double z[K], quad, zz;
-                post.solve([&](int a) { return ROLES ? g0[16 * NTP + a] + b1[a] : ((g0[16 * NTP + a] + b1[a]) + b1[2 * B * BS + a]) + b1[4 * B * BS + a]; }, z, quad, zz);
+                post.solve(b_of, z, quad, zz);
                 double *zr = B1 + lane * BS;  // (the first b partial of the sample is dead: its z goes there)
 #pragma unroll
                 for (int a = 0; a < K; ++a) zr[a] = z[a];
                 (void)xx; (void)m; (void)wgt; (void)pm; (void)pe;
-                if constexpr (ROLES) kill_table();
+                kill_table();
             }
         }
         if (more) {  // the first tile of the next round (its rows have been in registers since this round's second staging)
@@ -741,11 +441,9 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
             if (wave != SOLVER) {
                 stage_tile(lane, 0, par ^ 1);
                 load_tile(tile + 3);
-#ifndef LLK8_HAND_WAVES
-#define LLK8_HAND_WAVES (LLK8_ROLES ? 0x1765 : 0x4321)  // nibble r: the wave that stages row r of the solver wave (its SIMD's other wave is spared)
-#endif
-                const int hrow = wave == ((LLK8_HAND_WAVES >> 0) & 15) ? 0 : wave == ((LLK8_HAND_WAVES >> 4) & 15) ? 1
-                               : wave == ((LLK8_HAND_WAVES >> 8) & 15) ? 2 : wave == ((LLK8_HAND_WAVES >> 12) & 15) ? 3 : -1;
+                constexpr int HAND_WAVES = 0x1765;  // nibble r: the wave that stages row r of the solver wave (its SIMD's other wave is spared)
+                const int hrow = wave == ((HAND_WAVES >> 0) & 15) ? 0 : wave == ((HAND_WAVES >> 4) & 15) ? 1
+                               : wave == ((HAND_WAVES >> 8) & 15) ? 2 : wave == ((HAND_WAVES >> 12) & 15) ? 3 : -1;
                 if (hrow >= 0) {  // ... and one of the solver wave's rows
                     for (;;) {
                         const unsigned seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(hand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -884,11 +582,11 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
             sc[6] = 0.0;
             sc[7] = 0.0;
 #ifdef LLK8_TIMING
-            sc[SC_SQERR] = (double)tq[0];      // contractions (wave 0)
-            sc[SC_DEVSQ] = (double)tq[1];      // second staging (wave 0)
-            sc[SC_NONEMPTY] = (double)tq[2];   // hand-off + solver + table request (wave 0)
-            sc[5] = (double)tq[3];             // wait at the round's last barrier (wave 0)
-            sc[6] = (double)tq[4];             // waits at the other barriers (wave 0)
+            sc[SC_SQERR] = (double)tq[0];      // contractions (solver wave)
+            sc[SC_DEVSQ] = (double)tq[1];      // second staging (solver wave)
+            sc[SC_NONEMPTY] = (double)tq[2];   // hand-off + solver (solver wave)
+            sc[5] = (double)tq[3];             // wait at the round's last barrier (solver wave)
+            sc[6] = (double)tq[4];             // waits at the other barriers (solver wave)
             sc[7] = sm[cfg::OFF_FLAG + 1];     // overlapped staging of the next first tile (wave 1)
 #endif
         }
@@ -972,28 +670,11 @@ __global__ __launch_bounds__(512) void mix_llk8_kernel(MixLlkArgs m) {
     }
 }
 
-static bool llk8_enabled() {  // PPCA_LLK8=0: the four-wave llk2_kernel (A/B runs)
-    static const bool v = [] {
-        const char *e = getenv("PPCA_LLK8");
-        return !(e && atoi(e) == 0);
-    }();
-    return v;
-}
-
 template <int K>
 static hipError_t launch_llk8_t(int grid, const PassArgs &a, hipStream_t s) {
     const size_t lds = sizeof(double) * CfgL8<K>::LDS_DOUBLES;
     if (hipError_t e = ensure_dynamic_lds<llk8_kernel<K>>(lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((llk8_kernel<K>), dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int K>
-static hipError_t launch_llk2_t(int grid, const PassArgs &a, hipStream_t s) {
-    if (llk8_enabled()) return launch_llk8_t<K>(grid, a, s);
-    const size_t lds = sizeof(double) * CfgL<K>::LDS_DOUBLES;
-    if (hipError_t e = ensure_dynamic_lds<llk2_kernel<K>>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL((llk2_kernel<K>), dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
@@ -1019,20 +700,12 @@ bool recon8_covers(const PassArgs &a) {
         const char *e = getenv("PPCA_RECON8");
         return !(e && atoi(e) == 0);
     }();
-    return on && llk8_enabled() && a.recon && !a.states && !a.covs && !a.llks && (a.recon_mode == 0 || a.recon_mode == 1) && (a.d & 1) == 0 &&
+    return on && a.recon && !a.states && !a.covs && !a.llks && (a.recon_mode == 0 || a.recon_mode == 1) && (a.d & 1) == 0 &&
            a.ldx == a.d;
 }
 hipError_t launch_recon8(int k, int grid, const PassArgs &a, hipStream_t s) {
-#define PPCA_R8(KK) case KK: return a.recon_mode == 0 ? launch_recon8_t<KK, 1>(grid, a, s) : launch_recon8_t<KK, 2>(grid, a, s);
-    switch (k) {
-#ifdef PPCA_DEV_K10
-        PPCA_R8(10)
-#else
-        PPCA_R8(1) PPCA_R8(2) PPCA_R8(3) PPCA_R8(4) PPCA_R8(5) PPCA_R8(6) PPCA_R8(7) PPCA_R8(8) PPCA_R8(9) PPCA_R8(10)
-#endif
-        default: return hipErrorInvalidValue;
-    }
-#undef PPCA_R8
+    PPCA_DISPATCH_K(k, return a.recon_mode == 0 ? (launch_recon8_t<KK, 1>(grid, a, s)) : (launch_recon8_t<KK, 2>(grid, a, s)));
+    return hipErrorInvalidValue;
 }
 
 // Runs of tiles per XCD group of workgroups for a launch of `grid` workgroups over nm components: the smallest count that deals
@@ -1048,46 +721,14 @@ int mix_llk_runs_per_xcd(int grid, int nm) {
     return Wx / a;  // Wx / gcd(nm, Wx)
 }
 
-bool mix_llk8_available() { return llk8_enabled(); }
-
 hipError_t launch_mix_llk8(int k, int grid, const MixLlkArgs &a, hipStream_t s) {
-    switch (k) {
-#ifdef PPCA_DEV_K10
-        case 10: return launch_mix_llk8_t<10>(grid, a, s);
-#else
-        case 1: return launch_mix_llk8_t<1>(grid, a, s);
-        case 2: return launch_mix_llk8_t<2>(grid, a, s);
-        case 3: return launch_mix_llk8_t<3>(grid, a, s);
-        case 4: return launch_mix_llk8_t<4>(grid, a, s);
-        case 5: return launch_mix_llk8_t<5>(grid, a, s);
-        case 6: return launch_mix_llk8_t<6>(grid, a, s);
-        case 7: return launch_mix_llk8_t<7>(grid, a, s);
-        case 8: return launch_mix_llk8_t<8>(grid, a, s);
-        case 9: return launch_mix_llk8_t<9>(grid, a, s);
-        case 10: return launch_mix_llk8_t<10>(grid, a, s);
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    PPCA_DISPATCH_K(k, return launch_mix_llk8_t<KK>(grid, a, s));
+    return hipErrorInvalidValue;
 }
 
-hipError_t launch_llk2(int k, int grid, const PassArgs &a, hipStream_t s) {
-    switch (k) {
-#ifdef PPCA_DEV_K10
-        case 10: return launch_llk2_t<10>(grid, a, s);
-#else
-        case 1: return launch_llk2_t<1>(grid, a, s);
-        case 2: return launch_llk2_t<2>(grid, a, s);
-        case 3: return launch_llk2_t<3>(grid, a, s);
-        case 4: return launch_llk2_t<4>(grid, a, s);
-        case 5: return launch_llk2_t<5>(grid, a, s);
-        case 6: return launch_llk2_t<6>(grid, a, s);
-        case 7: return launch_llk2_t<7>(grid, a, s);
-        case 8: return launch_llk2_t<8>(grid, a, s);
-        case 9: return launch_llk2_t<9>(grid, a, s);
-        case 10: return launch_llk2_t<10>(grid, a, s);
-#endif
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_llk8(int k, int grid, const PassArgs &a, hipStream_t s) {
+    PPCA_DISPATCH_K(k, return launch_llk8_t<KK>(grid, a, s));
+    return hipErrorInvalidValue;
 }
 
 }  // namespace ppca

@@ -1347,8 +1347,8 @@ def test_full_size_properties_config5(P):
         assert np.isfinite(llk) and llk >= prev - 1e-9 * abs(llk), it
         prev = llk
         if it == 4:
-            again, llk2 = mix.iterate_with_llk(ds)
-            assert llk2 == llk
+            again, llk_again = mix.iterate_with_llk(ds)
+            assert llk_again == llk
             for a, b in zip(new.models, again.models):
                 np.testing.assert_array_equal(a.transform, b.transform)
             np.testing.assert_array_equal(new.log_weights, again.log_weights)
@@ -1468,7 +1468,31 @@ def test_large_downloads_are_pipelined_and_canonical(P):
 
 
 # --------------------------------------------------------------------------- round 6
-def test_multi_component_step_equals_component_by_component(oracle, tmp_path):
+@pytest.fixture(scope="module")
+def mix_multi_child(tmp_path_factory):
+    """tools/mix_multi_check.py in a child process under the given switches (no other switch of its kind set) -> its arrays.  One child
+    per set of switches for the whole module."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    done = {}
+
+    def run(**switches):
+        key = tuple(sorted(switches.items()))
+        if key not in done:
+            path = str(tmp_path_factory.mktemp("mix_multi") / "out.npz")
+            env = {k: v for k, v in os.environ.items() if k not in ("PPCA_MIX_MULTI", "PPCA_LLK8", "PPCA_LLK2")}
+            r = subprocess.run([sys.executable, os.path.join(root, "tools", "mix_multi_check.py"), path],
+                               capture_output=True, text=True, env=dict(env, **switches), timeout=900)
+            assert r.returncode == 0 and "mix multi check written" in r.stdout, (switches, r.stdout[-1500:], r.stderr[-2500:])
+            done[key] = dict(np.load(path))
+        return done[key]
+
+    return run
+
+
+def test_multi_component_step_equals_component_by_component(oracle, mix_multi_child):
     """Round 6: the mixture step launches every stage ONCE over all components (mix_llk8_kernel: the K llk sweeps with X read from
     HBM once; selection, reduction + verdict, finalisation + next slice tables with blockIdx.y = component).  Against the
     component-by-component form of rounds 2-5 (PPCA_MIX_MULTI=0) in a child process each: the llks are BIT-identical (same per-sample
@@ -1476,18 +1500,7 @@ def test_multi_component_step_equals_component_by_component(oracle, tmp_path):
     llk total differ only by the order of two sums -- under a tau + inverse-gamma prior too (k3_prior: finalize_qprep_multi_kernel
     against finalize_kernel).  The case with a component outside the int8 Gram's dynamic range must take that
     component's llks from the fp64 instantiation (engine 1) and agree with the oracle."""
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for flag in ("1", "0"):
-        path = str(tmp_path / f"mix_multi_{flag}.npz")
-        r = subprocess.run([sys.executable, os.path.join(root, "tools", "mix_multi_check.py"), path],
-                           capture_output=True, text=True, env=dict(os.environ, PPCA_MIX_MULTI=flag), timeout=900)
-        assert r.returncode == 0 and "mix multi check written" in r.stdout, (flag, r.stdout[-1500:], r.stderr[-2500:])
-        outs.append(np.load(path))
-    multi, single = outs
+    multi, single = mix_multi_child(PPCA_MIX_MULTI="1"), mix_multi_child(PPCA_MIX_MULTI="0")
     for case in ("k8", "k8_grid8", "k3_grid2", "k3_grid16", "k16", "k3_prior"):
         np.testing.assert_array_equal(multi[case + "_llks"], single[case + "_llks"], err_msg=case)
         np.testing.assert_array_equal(multi[case + "_lp"], single[case + "_lp"], err_msg=case)
@@ -1500,6 +1513,26 @@ def test_multi_component_step_equals_component_by_component(oracle, tmp_path):
         assert _rel(multi[case + "_trace"], single[case + "_trace"]) < 1e-13, case
     np.testing.assert_array_equal(multi["guard_llks"], single["guard_llks"])
     np.testing.assert_array_equal(multi["guard_engine"], np.array([0, 0, 1, 0]))
+
+
+def test_retired_sweep_switches_are_inert(mix_multi_child):
+    """PPCA_LLK8=0 used to select the four-wave log-likelihood sweep (and with it the component-by-component mixture step) and
+    PPCA_LLK2=0 sent an llk request through the general output pass; both forms summed |x~|^2 and the partials of b in another order
+    than the eight-wave sweep, so the last bits moved.  The four-wave kernel and both switches are gone: a child of
+    tools/mix_multi_check.py under both settings must write what a child without them writes, bit for bit -- the mixture's llks, log
+    posteriors, models, log-weights and llk trace, and the llks / llk of one model alone (llk8_kernel) -- and still serve the component
+    outside the int8 Gram's dynamic range from the fp64 instantiation."""
+    default = mix_multi_child(PPCA_MIX_MULTI="1")  # (the default form of the mixture step: shared with the test above)
+    retired = mix_multi_child(PPCA_MIX_MULTI="1", PPCA_LLK8="0", PPCA_LLK2="0")
+    assert sorted(default) == sorted(retired)
+    for case in ("k8", "k8_grid8", "k3_grid2", "k3_grid16", "k3_prior", "k16", "guard"):
+        assert case + "_single_llks" in default and case + "_single_llk" in default, case
+        assert np.isfinite(default[case + "_single_llk"]), case
+    for key in sorted(default):
+        a, b = default[key], retired[key]
+        np.testing.assert_array_equal(a, b, err_msg=key)
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), key
+    np.testing.assert_array_equal(retired["guard_engine"], np.array([0, 0, 1, 0]))
 
 
 def test_generic_wp_digits_under_predicted_scales(oracle, tmp_path):

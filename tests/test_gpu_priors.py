@@ -400,7 +400,7 @@ def test_composed_and_sharded_steps_with_prior_equal_the_plain_step(P, oracle, d
     ctx = _lib.default_context()
     ds, start = P.Dataset(x, w), P.PPCAModel(s, c, mu)
     want1, llk1 = start.iterate_with_llk(ds, pr)
-    want2, llk2 = want1.iterate_with_llk(ds, pr)
+    want2, llk_second = want1.iterate_with_llk(ds, pr)
     # composed by hand
     stats = torch.zeros(stats_len(d, k), dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
@@ -422,7 +422,7 @@ def test_composed_and_sharded_steps_with_prior_equal_the_plain_step(P, oracle, d
         for make in (lambda: ShardedEM(ds, start, pr, comm=comm), lambda: ShardedEM(ds, start, pr)):
             em = make()
             try:
-                for want, want_llk in ((want1, llk1), (want2, llk2)):
+                for want, want_llk in ((want1, llk1), (want2, llk_second)):
                     em.step()
                     g = em.model()
                     assert em.llk_of_previous() == want_llk

@@ -122,8 +122,8 @@ def test_eight_wave_em_pass_steady_state(P, oracle, ctx, k, d):
 
 @pytest.mark.parametrize("k,d", [(1, 64), (4, 200), (7, 255), (10, 256)])
 def test_output_passes_steady_state(P, oracle, ctx, k, d):
-    """llk2_kernel (two-tile rounds) and pass_kernel<K, false> (states, covariances, smooth, extrapolate, covariance
-    diagonals) with ~300 tiles per workgroup against the oracle."""
+    """llk8_kernel (llk, llks: two-tile rounds), recon8_kernel (smooth, extrapolate at an even d) and pass_kernel<K, false>
+    (states, covariances, covariance diagonals; smooth, extrapolate at an odd d) with ~300 tiles per workgroup against the oracle."""
     n = 20_000
     rng = np.random.default_rng(600 + k)
     x, _, _ = oracle.synth(n, d, k, 0.3, 7100 + k)

@@ -9,6 +9,11 @@ still the same function), and .vgpr_count / .sgpr_count / .group_segment_fixed_s
 note.  Prints one line per file and every kernel that differs, appeared or disappeared; exits 1 when a kernel present on both
 sides differs or one appeared (kernels that disappeared are listed: whether they were meant to go is the reader's call).
 Whole files are not compared: two builds of identical code differ in a few bytes outside the sections.
+
+One kind of operand depends on where the function lies and is compared as equal: the 32-bit literal of the s_add_u32 / s_addc_u32
+pair that follows an s_getpc_b64 on the same register pair -- the distance from the code to a constant table in another section
+(lean_log's coefficients, for one).  Deleting a kernel from a file moves the others and changes nothing else in them.  The line
+of a file says how many such literals were masked on either side.  The zero padding between a function and the next is left out too.
 """
 import os
 import re
@@ -38,8 +43,27 @@ def build(tree, out):
         list(ex.map(one, srcs))
 
 
+def mask_pcrel(lines):
+    """The literal (operand and encoding dword) of the s_add_u32 lo / s_addc_u32 hi behind `s_getpc_b64 s[lo:hi]` -> <pcrel>; how many."""
+    n, want = 0, []  # want: the registers whose additions are still expected, in order
+    for i, ln in enumerate(lines):
+        m = re.match(r"\s*s_getpc_b64 s\[(\d+):(\d+)\]", ln)
+        if m:
+            want = [("s_add_u32", m.group(1)), ("s_addc_u32", m.group(2))]
+            continue
+        if want:
+            op, reg = want.pop(0)
+            m = re.match(r"(\s*%s s%s, s%s, )\S+(\s+// [0-9A-F]{8}) [0-9A-F]{8}$" % (op, reg, reg), ln)
+            if m:
+                lines[i] = m.group(1) + "<pcrel>" + m.group(2) + " <pcrel>"
+                n += 1
+            else:
+                want = []
+    return n
+
+
 def kernels(elf):
-    """{kernel symbol: (code without addresses, metadata tuple)}"""
+    """{kernel symbol: (code without addresses and position-dependent literals, metadata tuple)}, literals masked"""
     notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", elf], check=True, capture_output=True, text=True).stdout
     meta = {}
     for blk in re.split(r"\n\s*- \.agpr_count:|\n\s*- \.args:", notes)[1:]:
@@ -55,7 +79,11 @@ def kernels(elf):
             code[cur] = []
         elif cur is not None and ln.strip():
             code[cur].append(re.sub(r"\s*//\s*[0-9A-Fa-f]+:", " //", ln))  # the trailing "// address: encoding" keeps the encoding
-    return {k: ("\n".join(code.get(k, [])), v) for k, v in meta.items()}
+    for lines in code.values():  # (zero padding up to the next function's alignment, printed as "...": depends on the neighbour)
+        while lines and lines[-1].strip() == "...":
+            lines.pop()
+    masked = sum(mask_pcrel(code.get(k, [])) for k in meta)
+    return {k: ("\n".join(code.get(k, [])), v) for k, v in meta.items()}, masked
 
 
 def main(old, new):
@@ -64,17 +92,18 @@ def main(old, new):
         if not f.endswith(".elf"):
             continue
         if not os.path.exists(os.path.join(new, f)):
-            print("%-22s only in OLD (%d kernels)" % (f, len(kernels(os.path.join(old, f)))))
+            print("%-22s only in OLD (%d kernels)" % (f, len(kernels(os.path.join(old, f))[0])))
             continue
         if not os.path.exists(os.path.join(old, f)):
             print("%-22s only in NEW" % f)
             bad += 1
             continue
-        a, b = kernels(os.path.join(old, f)), kernels(os.path.join(new, f))
+        (a, ma), (b, mb) = kernels(os.path.join(old, f)), kernels(os.path.join(new, f))
         both = sorted(set(a) & set(b))
         diff = [k for k in both if a[k] != b[k]]
         gone, came = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-        print("%-22s old %3d  new %3d  identical %3d  differ %d  gone %d  new-only %d" % (f, len(a), len(b), len(both) - len(diff), len(diff), len(gone), len(came)))
+        print("%-22s old %3d  new %3d  identical %3d  differ %d  gone %d  new-only %d  pc-relative literals masked %d / %d"
+              % (f, len(a), len(b), len(both) - len(diff), len(diff), len(gone), len(came), ma, mb))
         for k in diff:
             print("   DIFFERS  %s  %s meta %s -> %s" % (k, "code" if a[k][0] != b[k][0] else "", a[k][1], b[k][1]))
         for k in gone:

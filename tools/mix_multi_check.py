@@ -3,8 +3,10 @@ finalise launches with blockIdx.y = component) against the component-by-componen
 
     python tools/mix_multi_check.py OUT.npz        (PPCA_MIX_MULTI=0 in the environment: the component-by-component form)
 
-Writes the mixture llks / log posteriors of the start mixture and the models, log-weights and llk trace of a few EM iterations for a
-list of cases; tests/test_gpu_parity.py::test_multi_component_step_equals_component_by_component runs it twice and compares.  Cases:
+Writes the mixture llks / log posteriors of the start mixture, the llks / llk of its first component alone (PPCAModel.llks / llk: the
+one-model sweep) and the models, log-weights and llk trace of a few EM iterations for a list of cases;
+tests/test_gpu_parity.py::test_multi_component_step_equals_component_by_component runs it twice and compares, and
+test_retired_sweep_switches_are_inert runs it under the switches of the retired four-wave sweep.  Cases:
 K = 8 at d = 256, k = 10 (weighted rows, an all-masked row, a zero weight); K = 3 at d = 40, k = 3 on a grid capped at 2 and at 16
 workgroups (several (component, run) units per workgroup); the same K = 3 with a transformation precision and an inverse-gamma noise
 prior (finalize_qprep_multi_kernel against finalize_kernel under the prior); K = 16 at k = 1; one component whose transform trips the
@@ -45,6 +47,7 @@ def run(name, x, w, start, steps, out, grid_limit=0, prior=None):
     ds = P.Dataset(x, w) if w is not None else P.Dataset(x)
     out[name + "_llks"] = start.llks(ds)
     out[name + "_lp"] = start.infer_cluster(ds)
+    single(name, start, ds, out)
     mix, trace = start, []
     for _ in range(steps):
         mix, llk = mix.iterate_with_llk(ds, prior)
@@ -55,6 +58,12 @@ def run(name, x, w, start, steps, out, grid_limit=0, prior=None):
     out[name + "_mean"] = np.stack([m.mean for m in mix.models])
     out[name + "_lw"] = np.asarray(mix.log_weights)
     ctx.set_grid_limit(0)
+
+
+def single(name, start, ds, out):
+    """The one-model sweep (llk8_kernel, which no mixture call launches): llks and llk of the start mixture's first component."""
+    out[name + "_single_llks"] = start.models[0].llks(ds)
+    out[name + "_single_llk"] = np.array(start.models[0].llk(ds))
 
 
 def main():
@@ -83,6 +92,7 @@ def main():
     ds = P.Dataset(x, w)
     out["guard_llks"] = start.llks(ds)
     out["guard_lp"] = start.infer_cluster(ds)
+    single("guard", start, ds, out)
     out["guard_engine"] = np.array([int(_engine(ds, m)) for m in start.models])
     np.savez(sys.argv[1], **out)
     print("mix multi check written", sys.argv[1])
