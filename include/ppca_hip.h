@@ -218,6 +218,30 @@ int ppca_covariance_diagonal(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *
 int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int32_t mode, uint64_t seed,
                           int64_t row_offset, ppca_dataset **out);
 
+/* Entry-wise hold-out (Wold's cross-validation split) on the device, in one streaming pass (an extension with no reference
+ * counterpart).  Entry (i, j) of global row g = row_offset + i draws u = (word >> 11) 2^-53 in [0, 1) from the
+ * counter-based generator of ppca_posterior_sample, stream 8: word = row_word(row_key(seed, 8, g), j).  An observed
+ * (finite) entry is HELD iff u < fraction: it becomes NaN in train and keeps its bits in held; a kept entry keeps its bits in train
+ * and becomes NaN in held; a masked entry is NaN in both.  Both outputs are new datasets carrying the input weights.  fraction = 0
+ * holds nothing, fraction = 1 every observed entry; a fraction outside [0, 1] or NaN is PPCA_ERR_INVALID.  counts_host (nullable, 2) =
+ * [entries kept, entries held], unweighted.  Nothing depends on the grid; a shard with the right row_offset reproduces the
+ * single-device rows. */
+int ppca_dataset_holdout(ppca_ctx *ctx, ppca_dataset *ds, double fraction, uint64_t seed, int64_t row_offset, ppca_dataset **train_out,
+                         ppca_dataset **held_out, double *counts_host);
+/* The predictive log-density of held-out entries.  With (z, Sigma) the posterior of row i given its entries in
+ * `train` (ppca_infer), every finite entry x of `held` in that row is scored as a NEW reading of column j:
+ *   m = mean_j + c_j^T z,  v = sigma^2 + c_j^T Sigma c_j,  e = x - m,  l = -1/2 (ln 2 pi + ln v + e^2 / v)
+ * whatever `train` holds at j: the two datasets need equal shape (else PPCA_ERR_INVALID) but no particular relation.  A row without
+ * entries in train gets the prior predictive (mean_j, sigma^2 + |c_j|^2), state size 0 gives (mean_j, sigma^2).  Weights are train's.
+ *   per_row (nullable, n; host or device as ppca_llk's per-sample output): sum_j l, 0 for a row without held entries
+ *   totals_host (6): sum_i w_i n_i, sum w l, sum w e^2, sum w e^2 / v (each the column sums added in index order), the unweighted
+ *                    entry count, the rows with at least one held entry
+ *   col_sums_host (nullable, 4 d): per column the weighted count, sum w l, sum w e^2, sum w e^2 / v
+ * No N x d buffer is allocated or written.  per_row depends on its row alone (bit-identical across grids, chunks and slices); the
+ * sums are bit-reproducible for a given grid (fixed-order partials, no float atomics). */
+int ppca_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, const ppca_model *model, double *totals_host,
+                       double *col_sums_host, double *per_row);
+
 /* Leave-one-out predictive of every entry (an extension with no reference counterpart): for each entry j of row i,
  * the predictive of x_ij given the row's OTHER observed entries, the model held fixed.  With z, Sigma the row's posterior (ppca_infer),
  * r_j = x_j - mean_j - c_j^T z, q_j = c_j^T Sigma c_j and s_j = sigma^2 - q_j:
@@ -543,6 +567,15 @@ int ppca_mix_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *mod
  * (component c takes the first k_c normals of the row's eps stream).  The output carries no weights. */
 int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *models, const double *log_weights,
                               int32_t n_models, int32_t mode, uint64_t seed, int64_t row_offset, ppca_dataset **out);
+
+/* ppca_heldout_score for a mixture.  a_c = exp(lp_c), lp_c the row's log posterior of component c given `train`
+ * (ppca_mix_llk); m_c, v_c, l_c the component's predictive of the held entry x as ppca_heldout_score gives it.  Per held entry
+ *   l = logsumexp_c(lp_c + l_c),  A = sum_c a_c (m_c - x),  V = sum_c a_c v_c,  Q = sum_c a_c (m_c - x)^2,
+ *   e = -A,  variance V + max(Q - A^2, 0)
+ * (centred on x, so that the cancellation of Q - A^2 is harmless; the clamp keeps the variance >= min_c v_c).  A component of
+ * weight 0 contributes nothing.  Outputs as ppca_heldout_score; a one-component mixture gives the model's result. */
+int ppca_mix_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, ppca_model *const *models, const double *log_weights,
+                           int32_t n_models, double *totals_host, double *col_sums_host, double *per_row);
 
 /* The leave-one-out predictive of a mixture (an extension with no reference counterpart).  Component c gives m_cj,
  * v_cj, l_cj as ppca_loo_predictive does; lp_c is the row's log posterior of c (ppca_mix_llk).  Observed j: a_cj = exp(lp_c - l_cj - L_j)

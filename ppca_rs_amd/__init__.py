@@ -5,11 +5,11 @@ Dataset, Prior, PPCAModel (llk / llks / infer / smooth / extrapolate / iterate /
 iterate_with_prior / to_canonical), InferredMasked, PPCAMix and the trainers, over
 hand-written HIP kernels for gfx950 behind the C-ABI of include/ppca_hip.h.
 """
-from .api import (Dataset, DatasetChunks, FAMix, FAMixTrainer, FAModel, FATrainer, HPPCAModel, HPPCATrainer, InferredFA, InferredMasked, InferredMaskedMix, KMeans, KMeansStep, LooPredictive, PairwiseMoments, PosteriorSampler, PosteriorSamplerMix,
+from .api import (Dataset, DatasetChunks, FAMix, FAMixTrainer, FAModel, FATrainer, HeldOutScore, HPPCAModel, HPPCATrainer, InferredFA, InferredMasked, InferredMaskedMix, KMeans, KMeansStep, LooPredictive, PairwiseMoments, PosteriorSampler, PosteriorSamplerMix,
                   PPCAMix, PPCAMixTrainer, PPCAModel, PPCATrainer, Prior, TPPCAModel, TPPCATrainer, TrainMetrics)
 from ._lib import PPCAError
 from .frames import DataFrameAdapter, DataFrameAdapterDescription
 
 __version__ = "0.1.0"
-__all__ = ["Dataset", "DatasetChunks", "FAMix", "FAMixTrainer", "FAModel", "FATrainer", "HPPCAModel", "HPPCATrainer", "InferredFA", "InferredMasked", "InferredMaskedMix", "KMeans", "KMeansStep", "LooPredictive", "PairwiseMoments", "PosteriorSampler", "PosteriorSamplerMix", "PPCAMix", "PPCAMixTrainer", "PPCAModel",
+__all__ = ["Dataset", "DatasetChunks", "FAMix", "FAMixTrainer", "FAModel", "FATrainer", "HeldOutScore", "HPPCAModel", "HPPCATrainer", "InferredFA", "InferredMasked", "InferredMaskedMix", "KMeans", "KMeansStep", "LooPredictive", "PairwiseMoments", "PosteriorSampler", "PosteriorSamplerMix", "PPCAMix", "PPCAMixTrainer", "PPCAModel",
            "PPCATrainer", "Prior", "TPPCAModel", "TPPCATrainer", "TrainMetrics", "PPCAError", "DataFrameAdapter", "DataFrameAdapterDescription", "__version__"]

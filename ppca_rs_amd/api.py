@@ -129,6 +129,26 @@ class Dataset:
                                                ptr(sums), ptr(rows)))
         return (Dataset._wrap(h, self._ctx) if out else None), sums, rows
 
+    def holdout(self, fraction: float, seed: Optional[int] = None, *, row_offset: int = 0):
+        """(train, held): the entry-wise hold-out split of cross-validation, in one streaming pass on the GPU.  Every observed entry
+        is held with probability `fraction`, decided by a counter-based generator keyed by (seed, row_offset + row, column): a held
+        entry is NaN in `train` and keeps its bits in `held`, a kept one the other way round, a masked one is NaN in both.  Both
+        carry the input weights.  A slice starting at row s split with row_offset=s reproduces those rows of the whole.
+        seed=None draws a fresh seed.  train.holdout_counts = held.holdout_counts = (entries kept, entries held)."""
+        if not 0.0 <= float(fraction) <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError("fraction must lie in [0, 1]")
+        if row_offset < 0:
+            raise ValueError("row_offset must be >= 0")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        th, hh = C.c_void_p(), C.c_void_p()
+        counts = np.zeros(2)
+        check(lib().ppca_dataset_holdout(self._ctx.handle, self._h, float(fraction), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset),
+                                         C.byref(th), C.byref(hh), ptr(counts)))
+        train, held = Dataset._wrap(th, self._ctx), Dataset._wrap(hh, self._ctx)
+        train.holdout_counts = held.holdout_counts = (int(counts[0]), int(counts[1]))
+        return train, held
+
     def _fill_masked(self, fill: "Dataset", a) -> "Dataset":
         """ppca_dataset_fill_masked: this dataset's observed entries as they are, fill * a elsewhere."""
         h = C.c_void_p()
@@ -832,6 +852,14 @@ class PPCAModel:
         """sum_i w_i loo_llks[i]: the leave-one-out pseudo-log-likelihood, a criterion for the state size that needs no refit."""
         return self._loo(dataset, False, False)._llk
 
+    def heldout_score(self, train: Dataset, held: Dataset) -> "HeldOutScore":
+        """How this model predicts the finite entries of `held` from the rows of `train` (the two parts of Dataset.holdout; any two
+        datasets of one shape will do): per entry the predictive N(mean_j + c_j^T z, sigma^2 + c_j^T Sigma c_j) of a new reading
+        of column j under the row's posterior (z, Sigma) given `train`.  One GPU pass over each dataset; no N x d output."""
+        ctx = train._ctx
+        return _heldout_call(train, held, lambda t, c, r: lib().ppca_heldout_score(ctx.handle, train._h, held._h, self._device(ctx).h,
+                                                                                  t, c, r))
+
     def _iterate(self, dataset: Dataset, prior: Optional[Prior], want_llk: bool):
         ctx = dataset._ctx
         if len(dataset) == 0:
@@ -1020,6 +1048,92 @@ class PosteriorSampler:
         return Dataset(np.ascontiguousarray(noise + m._mean + z @ m._c.T))
 
 
+# --------------------------------------------------------------------------- held-out scoring
+class HeldOutScore:
+    """What `heldout_score` returns: how a model fitted on the train part of Dataset.holdout predicts the held entries.
+
+    count       sum_i w_i (held entries of row i)            n_entries   the unweighted entry count
+    llk         sum w l, l the predictive log-density        mean_llk    llk / count
+    mse, rmse   sum w e^2 / count and its root               mean_z2     sum w e^2 / v / count (about 1 when the intervals are calibrated)
+    llks        per row, the sum of l over its held entries (0 for a row with none)
+    columns     per column: count, llk, se (sum w e^2), z2 (sum w e^2 / v), rmse
+    Scores of disjoint shards add (`a + b`): sums field by field, llks concatenated."""
+
+    def __init__(self, col_sums: np.ndarray, n_entries: float, n_rows: float, llks: np.ndarray):
+        self._cols = np.asarray(col_sums, dtype=np.float64).reshape(4, -1)
+        self.n_entries, self.n_rows, self._llks = int(n_entries), int(n_rows), np.asarray(llks, dtype=np.float64)
+        self.count, self.llk, self._se, self._z2 = (float(sum(row.tolist())) for row in self._cols)  # (the columns in index order)
+
+    @staticmethod
+    def _ratio(a, b):
+        return a / b if b > 0 else float("nan")
+
+    @property
+    def mean_llk(self) -> float:
+        return self._ratio(self.llk, self.count)
+
+    @property
+    def mse(self) -> float:
+        return self._ratio(self._se, self.count)
+
+    @property
+    def rmse(self) -> float:
+        return math.sqrt(self.mse)
+
+    @property
+    def mean_z2(self) -> float:
+        return self._ratio(self._z2, self.count)
+
+    @property
+    def llks(self) -> np.ndarray:
+        return self._llks.copy()
+
+    @property
+    def columns(self) -> dict:
+        cnt, llk, se, z2 = (row.copy() for row in self._cols)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rmse = np.sqrt(se / cnt)
+        return dict(count=cnt, llk=llk, se=se, z2=z2, rmse=rmse)
+
+    def __add__(self, other: "HeldOutScore") -> "HeldOutScore":
+        if self._cols.shape != other._cols.shape:
+            raise ValueError("the two scores are of different output sizes")
+        return HeldOutScore(self._cols + other._cols, self.n_entries + other.n_entries, self.n_rows + other.n_rows,
+                            np.concatenate([self._llks, other._llks]))
+
+    def __repr__(self) -> str:
+        return f"HeldOutScore(n_entries={self.n_entries}, mean_llk={self.mean_llk:.6g}, rmse={self.rmse:.6g}, mean_z2={self.mean_z2:.4g})"
+
+
+def _heldout_call(train: Dataset, held: Dataset, fn) -> HeldOutScore:
+    if len(train) != len(held) or train._d != held._d:
+        raise ValueError("the train part and the held part differ in shape")
+    totals, cols, rows = np.zeros(6), np.zeros((4, train._d)), np.zeros(len(train))
+    check(fn(ptr(totals), ptr(cols), ptr(rows)))
+    return HeldOutScore(cols, totals[4], totals[5], rows)
+
+
+def _heldout_unwhiten(score: HeldOutScore, held: Dataset, noise: np.ndarray) -> HeldOutScore:
+    """The score of whitened data (columns divided by noise) in the units of the data: llk_j -= cnt_j ln s_j, se_j *= s_j^2, z2_j
+    unchanged; per row, minus the sum of ln s_j over the row's held entries."""
+    ln = np.log(noise)
+    _, _, jac = held._scale_columns(np.ones_like(noise), l=ln, out=False, row_sums=True)
+    cols = score._cols.copy()
+    cols[1] -= cols[0] * ln
+    cols[2] *= noise * noise
+    return HeldOutScore(cols, score.n_entries, score.n_rows, score._llks - jac)
+
+
+def _select_state_size(dataset: Dataset, state_sizes, fraction: float, seed: Optional[int], fit):
+    """One hold-out split, then per state size fit(train part, k) -> model and its score on the held part."""
+    train, held = dataset.holdout(fraction, seed)
+    out = []
+    for k in state_sizes:
+        model = fit(train, int(k))
+        out.append((int(k), model.heldout_score(train, held), model))
+    return out
+
+
 # --------------------------------------------------------------------------- trainers
 @dataclass(frozen=True)
 class TrainMetrics:
@@ -1064,6 +1178,15 @@ class PPCATrainer:
         model = start or PPCAModel.init(state_size, ds, seed=seed, method=init)
         return _train_loop(model, n_iters, quiet, metric, "PPCA", len(ds), lambda m: m.iterate_with_llk(ds, prior),
                            lambda m: m.iterate_with_prior(ds, prior) if prior is not None else m.iterate(ds))
+
+
+    def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
+                          init: str = "random", prior: Optional[Prior] = None):
+        """Entry-wise cross-validation of the state size: one Dataset.holdout(fraction, seed), then for every size one `train` on the
+        train part (quiet; model seed = `seed`) and one `heldout_score`.  Returns [(state_size, HeldOutScore, PPCAModel)]: choose the
+        size whose score.mean_llk is largest."""
+        return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: PPCATrainer(tr).train(
+            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init, prior=prior))
 
 
 # --------------------------------------------------------------------------- own npz containers (FAModel, TPPCAModel, FAMix)
@@ -1211,6 +1334,12 @@ class FAModel:
         y, sums, _ = self._whiten(dataset, col_sums=True)
         return self.whitened().llk(y) - float(np.dot(sums[0], np.log(self._noise)))
 
+    def heldout_score(self, train: Dataset, held: Dataset) -> "HeldOutScore":
+        """PPCAModel.heldout_score for per-column noise: both parts whitened with the same scales, scored by the whitened model and
+        mapped back to the units of the data."""
+        score = self.whitened().heldout_score(self._whiten(train)[0], self._whiten(held)[0])
+        return _heldout_unwhiten(score, held, self._noise)
+
     def infer(self, dataset: Dataset) -> InferredFA:
         """Posterior of the latent state of every sample (that of the whitened model on the whitened rows)."""
         inf = self.whitened().infer(self._whiten(dataset)[0])
@@ -1287,6 +1416,16 @@ class FATrainer:
         floor = min_noise_ratio * np.sqrt(ds.column_stats()[2])
         return _train_loop(model, n_iters, quiet, metric, "FA", len(ds), lambda m: m.iterate_with_llk(ds, floor),
                            lambda m: m.iterate(ds, floor))
+
+
+    def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
+                          init: str = "random", prior: Optional[Prior] = None):
+        """PPCATrainer.select_state_size with FAModel fits: [(state_size, HeldOutScore, FAModel)].  FAModel has no MAP step:
+        `prior` must be None."""
+        if prior is not None:
+            raise ValueError("FATrainer takes no prior")
+        return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: FATrainer(tr).train(
+            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init))
 
 
 # --------------------------------------------------------------------------- Student-t PPCA (robust to outlying rows)
@@ -1899,6 +2038,15 @@ class PPCAMix:
                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), C.byref(h)))
         return Dataset._wrap(h, ctx)
 
+    def heldout_score(self, train: Dataset, held: Dataset) -> "HeldOutScore":
+        """PPCAModel.heldout_score for the mixture: per held entry the mixture of the components' predictives, component c weighted
+        by its posterior given the row of `train`.  l = logsumexp_c(lp_c + l_c); the error is the mixture mean's, the variance
+        sum_c a_c v_c plus the spread of the components' means."""
+        ctx = train._ctx
+        devs, arr = self._handles(ctx)
+        return _heldout_call(train, held, lambda t, c, r: lib().ppca_mix_heldout_score(ctx.handle, train._h, held._h, arr,
+                                                                                      ptr(self._lw), len(devs), t, c, r))
+
     def _loo(self, dataset: Dataset, full: bool, per_sample: bool):
         ctx = dataset._ctx
         devs, arr = self._handles(ctx)
@@ -2252,6 +2400,12 @@ class FAMix:
         """Weighted log-likelihood."""
         y, sums, _ = self._whiten(dataset, col_sums=True)
         return self.whitened().llk(y) - float(np.dot(sums[0], np.log(self._noise)))
+
+    def heldout_score(self, train: Dataset, held: Dataset) -> "HeldOutScore":
+        """PPCAMix.heldout_score of the whitened mixture on both parts whitened with the same scales, mapped back to the units of
+        the data (FAModel.heldout_score)."""
+        score = self.whitened().heldout_score(self._whiten(train)[0], self._whiten(held)[0])
+        return _heldout_unwhiten(score, held, self._noise)
 
     def infer_cluster(self, dataset: Dataset) -> np.ndarray:
         """Log posteriors over the components (N, n_models): those of the whitened mixture on the whitened rows."""

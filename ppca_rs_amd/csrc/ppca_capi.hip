@@ -1478,6 +1478,111 @@ extern "C" int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_m
     return PPCA_OK;
 }
 
+// ------------------------------------------------------------------ held-out scoring
+extern "C" int ppca_dataset_holdout(ppca_ctx *ctx, ppca_dataset *ds, double fraction, uint64_t seed, int64_t row_offset,
+                                    ppca_dataset **train_out, ppca_dataset **held_out, double *counts_host) {
+    if (!ctx || !ds || !train_out || !held_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!(fraction >= 0.0 && fraction <= 1.0)) return fail(PPCA_ERR_INVALID, "fraction must lie in [0, 1]");
+    if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
+    if (int rc = check_same_device(ds, ctx)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = ds->n;
+    const int d = ds->d;
+    DatasetPtr tr, he;  // the input weights carried over, as ppca_reconstruct does
+    if (int rc = dataset_like(ctx, ds, true, tr)) return rc;
+    if (int rc = dataset_like(ctx, ds, true, he)) return rc;
+    double counts[2] = {0.0, 0.0};
+    if (n > 0) {
+        Partials part;
+        const int grid = holdout_grid(n, d, ctx->n_cu);
+        if (int rc = part.alloc(grid, 2)) return rc;
+        HIP_TRY(launch_holdout(ds->X, ds->d, n, d, fraction, seed, row_offset, static_cast<double *>(tr->xbuf->p),
+                               static_cast<double *>(he->xbuf->p), part.p, grid, ctx->stream));
+        if (counts_host) {
+            HIP_TRY(part.reduce(ctx->stream));
+            HIP_TRY(hipMemcpyAsync(counts, part.red, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (counts_host) std::memcpy(counts_host, counts, sizeof(counts));
+    *train_out = tr.release();
+    *held_out = he.release();
+    return PPCA_OK;
+}
+
+// Rows of a scoring chunk: the posterior covariance and state of a row are its scratch (chunk_rows: under 1 GiB).
+// PPCA_HELD_CHUNK=rows forces a chunk length (tests: several chunks at small N).
+static int64_t held_chunk_rows(int64_t n, int k) {
+    int64_t c = chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)k * k + k));
+    if (const char *e = getenv("PPCA_HELD_CHUNK")) {
+        const long long v = atoll(e);
+        if (v > 0) c = v;
+    }
+    return c;
+}
+
+static int check_held_pair(const ppca_dataset *train, const ppca_dataset *held) {
+    if (!train || !held) return fail(PPCA_ERR_INVALID, "null dataset");
+    if (train->n != held->n || train->d != held->d)
+        return fail(PPCA_ERR_INVALID, "the train part (%lld x %d) and the held part (%lld x %d) differ in shape", (long long)train->n,
+                    train->d, (long long)held->n, held->d);
+    if (train->ctx->device != held->ctx->device) return fail(PPCA_ERR_INVALID, "the two datasets live on different devices");
+    return PPCA_OK;
+}
+
+// totals = [sum w n_i, sum w l, sum w e^2, sum w e^2 / v, entries, rows with an entry]: the first four are the column sums added
+// in index order.
+static void held_totals(const double *sums, int d, double *totals) {
+    for (int q = 0; q < 4; ++q) {
+        double s = 0.0;
+        for (int j = 0; j < d; ++j) s += sums[(size_t)q * d + j];
+        totals[q] = s;
+    }
+    totals[4] = sums[(size_t)4 * d];
+    totals[5] = sums[(size_t)4 * d + 1];
+}
+
+extern "C" int ppca_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, const ppca_model *model,
+                                  double *totals_host, double *col_sums_host, double *per_row) {
+    if (!ctx || !totals_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_held_pair(train, held)) return rc;
+    if (int rc = check_pair(train, model)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = train->n;
+    const int d = train->d, k = model->k;
+    std::vector<double> sums((size_t)4 * d + 2, 0.0);
+    if (n > 0) {
+        const int64_t chunk = held_chunk_rows(n, k);
+        const size_t rows = (size_t)std::min(chunk, n);
+        const int64_t plen = heldout_part_len(d, k);
+        const int grid = heldout_score_grid((int64_t)rows, d, k, ctx->n_cu);
+        BufRef st, cv, pr;
+        Partials part;
+        if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
+        if (int rc = part.alloc(grid, plen)) return rc;
+        if (per_row)
+            if (int rc = dev_alloc(sizeof(double) * (size_t)n, &pr)) return rc;
+        double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
+        double *rowv = pr ? static_cast<double *>(pr->p) : nullptr;
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            ppca_dataset tp = row_slice(train, r0, chunk), hp = row_slice(held, r0, chunk);
+            if (int rc = run_post(ctx, &tp, model, nullptr, states, covs, nullptr, 0, nullptr)) return rc;
+            const int g = heldout_score_grid(tp.n, d, k, ctx->n_cu);  // (<= grid: the last chunk may be shorter)
+            HIP_TRY(launch_heldout_score(hp.X, hp.d, tp.w, d, k, tp.n, model->p(), states, covs, rowv ? rowv + r0 : nullptr, part.p, g,
+                                         ctx->stream));
+            HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+        }
+        HIP_TRY(hipMemcpyAsync(sums.data(), part.red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+        if (per_row)  // (host or device destination, as ppca_llk's per-sample output)
+            HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    held_totals(sums.data(), d, totals_host);
+    if (col_sums_host) std::memcpy(col_sums_host, sums.data(), sizeof(double) * (size_t)4 * d);
+    return PPCA_OK;
+}
+
 // ------------------------------------------------------------------ mixture
 static int mix_check(ppca_dataset *ds, ppca_model *const *models, int32_t nm) {
     if (!ds || !models || nm < 1) return fail(PPCA_ERR_INVALID, "bad mixture arguments");
@@ -2122,6 +2227,63 @@ extern "C" int ppca_mix_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, ppca_m
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     *out = nd.release();
+    return PPCA_OK;
+}
+
+// ppca_heldout_score for a mixture: the rows' log posteriors given `train` (mix_posteriors), then per chunk of rows each component's
+// posterior pass and its fold into per-entry state (5 doubles per entry of the chunk, touched at the held entries), then one
+// summing pass.
+extern "C" int ppca_mix_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, ppca_model *const *models,
+                                      const double *log_weights, int32_t n_models, double *totals_host, double *col_sums_host,
+                                      double *per_row) {
+    if (!ctx || !log_weights || !totals_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_held_pair(train, held)) return rc;
+    if (int rc = mix_check(train, models, n_models)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = train->n;
+    const int d = train->d, nm = n_models;
+    std::vector<double> sums((size_t)4 * d + 2, 0.0);
+    if (n > 0) {
+        BufRef llk, u, lse, lp;
+        if (int rc = mix_posteriors(ctx, train, models, log_weights, nm, llk, u, lse, &lp)) return rc;
+        const double *logpost = static_cast<const double *>(lp->p);
+        int kmax = 1;
+        for (int c = 0; c < nm; ++c) kmax = std::max(kmax, models[c]->k);
+        int64_t chunk = chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)kmax * kmax + kmax + (int64_t)5 * d));
+        if (const char *e = getenv("PPCA_HELD_CHUNK")) {
+            const long long v = atoll(e);
+            if (v > 0) chunk = v;
+        }
+        const size_t rows = (size_t)std::min(chunk, n);
+        const int64_t plen = heldout_part_len(d, 0);
+        const int grid = heldout_score_grid((int64_t)rows, d, 0, ctx->n_cu);
+        BufRef st, cv, fo, pr;
+        Partials part;
+        if (int rc = dev_alloc(sizeof(double) * rows * kmax, &st)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * rows * kmax * kmax, &cv)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * rows * d * 5, &fo)) return rc;
+        if (int rc = part.alloc(grid, plen)) return rc;
+        if (per_row)
+            if (int rc = dev_alloc(sizeof(double) * (size_t)n, &pr)) return rc;
+        double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p), *fold = static_cast<double *>(fo->p);
+        double *rowv = pr ? static_cast<double *>(pr->p) : nullptr;
+        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+            ppca_dataset tp = row_slice(train, r0, chunk), hp = row_slice(held, r0, chunk);
+            for (int c = 0; c < nm; ++c) {
+                if (int rc = run_post(ctx, &tp, models[c], nullptr, states, covs, nullptr, 0, nullptr)) return rc;
+                HIP_TRY(launch_heldout_fold(hp.X, hp.d, d, models[c]->k, tp.n, models[c]->p(), states, covs, logpost + r0 * nm, c, nm,
+                                            fold, heldout_score_grid(tp.n, d, models[c]->k, ctx->n_cu), ctx->stream));
+            }
+            const int g = heldout_score_grid(tp.n, d, 0, ctx->n_cu);
+            HIP_TRY(launch_heldout_finish(hp.X, hp.d, tp.w, d, tp.n, fold, rowv ? rowv + r0 : nullptr, part.p, g, ctx->stream));
+            HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+        }
+        HIP_TRY(hipMemcpyAsync(sums.data(), part.red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+        if (per_row) HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    held_totals(sums.data(), d, totals_host);
+    if (col_sums_host) std::memcpy(col_sums_host, sums.data(), sizeof(double) * (size_t)4 * d);
     return PPCA_OK;
 }
 

@@ -287,6 +287,29 @@ hipError_t launch_mix_loo_var(const double *X, int64_t ldx, int d, int64_t n_row
                               const double *m, const double *v, const double *ell, const double *L, const double *mean, double *var,
                               int first, hipStream_t s);
 
+// held-out scoring (ppca_heldout.hip).  launch_holdout: train / held (n x d each) = the split of X by the
+// counter-based generator (stream 8, keyed by row_offset + row and column); part[grid][2] = the workgroups' [kept, held] counts
+// (reduce with launch_reduce_partials); grid = holdout_grid.  launch_heldout_score: the predictive log-density of the finite entries
+// of H (a chunk's rows of `held`) under the rows' posteriors (states, covs: what the posterior pass wrote for the same rows of
+// `train`); per_row (nullable) = the row's sum; part[grid][heldout_part_len(d, k)] = [w | w l | w e^2 | w e^2 / v (d each) | entries |
+// rows with an entry | (scratch)] per workgroup (reduce with launch_reduce_partials; the first 4 d + 2 are the sums); grid =
+// heldout_score_grid.
+int holdout_grid(int64_t n, int d, int n_cu);
+hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double fraction, uint64_t seed, int64_t row_offset,
+                          double *train, double *held, double *part, int grid, hipStream_t s);
+size_t heldout_score_lds_bytes(int d, int k);
+int64_t heldout_part_len(int d, int k);
+int heldout_score_grid(int64_t n_rows, int d, int k, int n_cu);
+hipError_t launch_heldout_score(const double *H, int64_t ldh, const double *w, int d, int k, int64_t n_rows, const double *model,
+                                const double *states, const double *covs, double *per_row, double *part, int grid, hipStream_t s);
+// The mixture (chunk-local buffers): launch_heldout_fold folds component comp's (m, v, l) of every held entry into fold (5 arrays of
+// n_rows x d: running maximum and scaled sum of lp_c + l_c, sum a_c (m_c - x), sum a_c v_c, sum a_c (m_c - x)^2; comp 0 initialises);
+// launch_heldout_finish sums l = mx + ln sm, e^2 = A^2, e^2 / (V + max(Q - A^2, 0)) as launch_heldout_score does (part:
+// heldout_part_len(d, 0), grid = heldout_score_grid(n_rows, d, 0, n_cu)).
+hipError_t launch_heldout_fold(const double *H, int64_t ldh, int d, int k, int64_t n_rows, const double *model, const double *states,
+                               const double *covs, const double *logpost, int comp, int nm, double *fold, int grid, hipStream_t s);
+hipError_t launch_heldout_finish(const double *H, int64_t ldh, const double *w, int d, int64_t n_rows, const double *fold,
+                                 double *per_row, double *part, int grid, hipStream_t s);
 // per-column streaming passes of factor analysis (ppca_scale.hip).  launch_scale_columns: out (nullable, n x d)
 // = x a_j on observed entries, NaN elsewhere; part[grid][3 d] the workgroups' column sums tot / sum / sq of w m, w m (x a - b),
 // w m (x a - b)^2 (reduce with launch_reduce_partials); rowsum (nullable, n) = sum_j m_ij l_j; abl_dev = [a | b | l], 3 d doubles;

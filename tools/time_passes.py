@@ -18,7 +18,9 @@ without the scaled rows, a whole TPPCAModel.iterate, and the passes they are com
 PPCAModel.iterate).  `--hetero` runs ONLY the legs of PPCA with a precision per entry, in one process, alternating:
 the sweep alone (HPPCAModel.llks), a whole HPPCAModel.iterate, PPCAModel.llks and PPCAModel.iterate on the same rows, and the
 device-to-device copy of X whose rate prices the traffic floor of the iteration (X and P read twice, the records written and read
-once)."""
+once).  `--heldout` runs ONLY the legs of held-out scoring, in one process, alternating: the device split, the
+score, PPCAModel.loo_llks and the scale pass with output for comparison, and the composition the feature replaces (extrapolate, the
+extrapolated covariance diagonal and both downloads)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -144,6 +146,54 @@ def robust_legs(reps=10):
 
 if "--robust" in sys.argv:
     robust_legs()
+    sys.exit(0)
+
+def heldout_legs(reps=10, fraction=0.1):
+    """Held-out scoring, in one process and alternating: the device split (Dataset.holdout), the score
+    (PPCAModel.heldout_score on the two parts), PPCAModel.loo_llks on the same data (the same posterior pass, the k^2 work on every
+    entry), the column-scale pass with output (two of the split's three array streams), and the composition the feature replaces:
+    extrapolate + extrapolated_covariances_diagonal of the train part and both downloads.  Every repetition timed on its own."""
+    def series(fn, r):
+        fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  ({len(ts)} repetitions)", flush=True)
+        return med
+
+    train, held = ds.holdout(fraction, 11)
+    print(f"split: kept {train.holdout_counts[0]}, held {train.holdout_counts[1]} "
+          f"(share {train.holdout_counts[1] / max(sum(train.holdout_counts), 1):.5f})", flush=True)
+    a = np.ones(d)
+
+    def composition():  # (the diagonal through the device pass, ppca_covariance_diagonal mode 1: the faster of the two public routes)
+        o = C.c_void_p()
+        _lib.check(L.ppca_covariance_diagonal(ctx.handle, train._h, md.h, 1, C.byref(o)))
+        return m.extrapolate(train).numpy(), P.Dataset._wrap(o, ctx).numpy()
+
+    legs = [("Dataset.holdout (one read, two writes, counts)", lambda: ds.holdout(fraction, 11)),
+            ("PPCAModel.heldout_score (train, held)", lambda: m.heldout_score(train, held)),
+            ("PPCAModel.loo_llks (train + held rows = the dataset)", lambda: m.loo_llks(ds)),
+            ("scale pass with output", lambda: ds._scale_columns(a, out=True)),
+            ("extrapolate + covariance diagonal + both downloads", composition)]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn, reps))
+    med = [report(name, np.concatenate(got[name])) for name, _ in legs]
+    print(f"  split / scale pass with output = {med[0] / med[3]:.3f}   (three array streams against two: 1.5 expected)")
+    print(f"  score / loo_llks = {med[1] / med[2]:.3f}")
+    print(f"  composition / (split + score) = {med[4] / (med[0] + med[1]):.1f}")
+
+if "--heldout" in sys.argv:
+    heldout_legs()
     sys.exit(0)
 
 def hetero_legs(reps=10):
