@@ -233,6 +233,39 @@ static int64_t chunk_rows(int64_t n, int64_t bytes_per_row) {
     return std::max<int64_t>(1024, std::min<int64_t>(std::max<int64_t>(n, 1), ((int64_t)1 << 30) / bytes_per_row));
 }
 
+// `rows`, unless the environment variable `name` holds a positive row count (tests: several chunks at small N).  Read on every call.
+static int64_t chunk_override(const char *name, int64_t rows) {
+    const char *e = getenv(name);
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? v : rows;
+}
+
+// The scratch of a pass that takes the posterior of ds chunk by chunk -- states (rows x k) and covs (rows x k x k) for
+// min(chunk, n) rows at state size k (a mixture: its largest) -- and the walk over the chunks.
+struct PostChunks {
+    BufRef st, cv;
+    double *states = nullptr, *covs = nullptr;
+    int64_t chunk = 0;
+    size_t rows = 0;  // of the scratch: min(chunk, n)
+    int alloc(int64_t n, int64_t chunk_, int k) {
+        chunk = chunk_;
+        rows = (size_t)std::min(chunk, n);
+        if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
+        states = static_cast<double *>(st->p), covs = static_cast<double *>(cv->p);
+        return PPCA_OK;
+    }
+    // f(part, r0) for every chunk of ds in row order: part = its rows r0 .. r0 + chunk (row_slice)
+    template <class F>
+    int each(const ppca_dataset *ds, F &&f) const {
+        for (int64_t r0 = 0; r0 < ds->n; r0 += chunk) {
+            ppca_dataset part = row_slice(ds, r0, chunk);
+            if (int rc = f(part, r0)) return rc;
+        }
+        return PPCA_OK;
+    }
+};
+
 // Per-workgroup partial sums p[grid][len] and, behind them, red[len]: their sum in the fixed order of launch_reduce_partials.
 struct Partials {
     BufRef buf;
@@ -1368,23 +1401,19 @@ extern "C" int ppca_covariance_diagonal(ppca_ctx *ctx, ppca_dataset *ds, const p
 // ------------------------------------------------------------------ posterior sampling
 // The draw of ppca_sample.hip over the dataset's rows into out (dataset rows x d): the posterior means and covariances of a
 // chunk of rows (the pass of ppca_infer, fused or generic) into scratch, then one draw kernel over the chunk (chunk_rows; the draw
-// depends on the row alone, not on the chunk).
+// depends on the row alone, not on the chunk: PPCA_POST_CHUNK=rows forces a chunk length for the tests of that).
 static int posterior_sample_rows(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int mode, uint64_t seed,
                                  int64_t row_offset, double *out, const int *choice, int comp) {
     const int k = model->k;
-    const int64_t chunk = chunk_rows(ds->n, (int64_t)sizeof(double) * ((int64_t)k * k + k));
-    const size_t rows = (size_t)std::min(chunk, ds->n);
-    BufRef st, cv;
-    if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
-    if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
-    double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
-    for (int64_t r0 = 0; r0 < ds->n; r0 += chunk) {
-        ppca_dataset part = row_slice(ds, r0, chunk);
-        if (int rc = run_post(ctx, &part, model, nullptr, states, covs, nullptr, 0, nullptr)) return rc;
-        HIP_TRY(launch_posterior_draw(ds->X, ds->d, ds->d, k, part.n, r0, row_offset, model->p(), states, covs, out, mode, seed,
+    PostChunks pc;
+    if (int rc = pc.alloc(ds->n, chunk_override("PPCA_POST_CHUNK", chunk_rows(ds->n, (int64_t)sizeof(double) * ((int64_t)k * k + k))), k))
+        return rc;
+    return pc.each(ds, [&](ppca_dataset &part, int64_t r0) -> int {
+        if (int rc = run_post(ctx, &part, model, nullptr, pc.states, pc.covs, nullptr, 0, nullptr)) return rc;
+        HIP_TRY(launch_posterior_draw(ds->X, ds->d, ds->d, k, part.n, r0, row_offset, model->p(), pc.states, pc.covs, out, mode, seed,
                                       choice, comp, ctx->n_cu, ctx->stream));
-    }
-    return PPCA_OK;
+        return PPCA_OK;
+    });
 }
 
 extern "C" int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *model, int32_t mode, uint64_t seed,
@@ -1407,8 +1436,9 @@ extern "C" int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca
 
 // ------------------------------------------------------------------ leave-one-out predictive
 // The rows of a LOO chunk: per row the posterior covariance, the state and the llk, and per_entry doubles per dimension.
+// PPCA_POST_CHUNK=rows forces a chunk length (tests: the outputs depend on the row alone).
 static int64_t loo_chunk_rows(int64_t n, int d, int k, int per_entry) {
-    return chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)k * k + k + (int64_t)per_entry * d + 1));
+    return chunk_override("PPCA_POST_CHUNK", chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)k * k + k + (int64_t)per_entry * d + 1)));
 }
 
 // The LOO pass of one model over part (a chunk of rows): the posterior pass of ppca_infer (fused or generic) into states / covs, then
@@ -1459,18 +1489,13 @@ extern "C" int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_m
     double *mean = md ? static_cast<double *>(md->xbuf->p) : nullptr, *var = vd ? static_cast<double *>(vd->xbuf->p) : nullptr;
     double *llks = want_l ? static_cast<double *>(lb->p) : nullptr;
     if (n > 0) {
-        const int64_t chunk = loo_chunk_rows(n, ds->d, k, 0);
-        const size_t rows = (size_t)std::min(chunk, n);
-        BufRef st, cv;
-        if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
-        if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
-        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            ppca_dataset part = row_slice(ds, r0, chunk);
-            if (int rc = loo_part(ctx, &part, model, static_cast<double *>(st->p), static_cast<double *>(cv->p),
-                                  mean ? mean + r0 * ds->d : nullptr, var ? var + r0 * ds->d : nullptr, nullptr,
-                                  llks ? llks + r0 : nullptr))
-                return rc;
-        }
+        PostChunks pc;
+        if (int rc = pc.alloc(n, loo_chunk_rows(n, ds->d, k, 0), k)) return rc;
+        if (int rc = pc.each(ds, [&](ppca_dataset &part, int64_t r0) {
+                return loo_part(ctx, &part, model, pc.states, pc.covs, mean ? mean + r0 * ds->d : nullptr,
+                                var ? var + r0 * ds->d : nullptr, nullptr, llks ? llks + r0 : nullptr);
+            }))
+            return rc;
     }
     if (int rc = loo_totals(ctx, ds, llks, total_host, per_sample_host)) return rc;
     if (mean_out) *mean_out = md.release();
@@ -1510,15 +1535,10 @@ extern "C" int ppca_dataset_holdout(ppca_ctx *ctx, ppca_dataset *ds, double frac
     return PPCA_OK;
 }
 
-// Rows of a scoring chunk: the posterior covariance and state of a row are its scratch (chunk_rows: under 1 GiB).
-// PPCA_HELD_CHUNK=rows forces a chunk length (tests: several chunks at small N).
-static int64_t held_chunk_rows(int64_t n, int k) {
-    int64_t c = chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)k * k + k));
-    if (const char *e = getenv("PPCA_HELD_CHUNK")) {
-        const long long v = atoll(e);
-        if (v > 0) c = v;
-    }
-    return c;
+// Rows of a scoring chunk: the posterior covariance and state of a row and per_entry doubles per entry (the mixture's folded state)
+// are its scratch (chunk_rows: under 1 GiB).  PPCA_HELD_CHUNK=rows forces a chunk length (tests: several chunks at small N).
+static int64_t held_chunk_rows(int64_t n, int d, int k, int per_entry) {
+    return chunk_override("PPCA_HELD_CHUNK", chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)k * k + k + (int64_t)per_entry * d)));
 }
 
 static int check_held_pair(const ppca_dataset *train, const ppca_dataset *held) {
@@ -1542,6 +1562,21 @@ static void held_totals(const double *sums, int d, double *totals) {
     totals[5] = sums[(size_t)4 * d + 1];
 }
 
+// The end of a held-out pass over n rows (n = 0: zeros, nothing is read): the reduced sums (red: 4 d column sums | 2 counts) and the
+// rows' scores (rowv; per_row nullable, a host or device destination as ppca_llk's per-sample output) come down, then held_totals.
+static int held_finish(ppca_ctx *ctx, int64_t n, int d, const double *red, const double *rowv, double *totals_host,
+                       double *col_sums_host, double *per_row) {
+    std::vector<double> sums((size_t)4 * d + 2, 0.0);
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(sums.data(), red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+        if (per_row) HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    held_totals(sums.data(), d, totals_host);
+    if (col_sums_host) std::memcpy(col_sums_host, sums.data(), sizeof(double) * (size_t)4 * d);
+    return PPCA_OK;
+}
+
 extern "C" int ppca_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, const ppca_model *model,
                                   double *totals_host, double *col_sums_host, double *per_row) {
     if (!ctx || !totals_host) return fail(PPCA_ERR_INVALID, "null argument");
@@ -1550,40 +1585,39 @@ extern "C" int ppca_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_datas
     USE_CTX(ctx);
     const int64_t n = train->n;
     const int d = train->d, k = model->k;
-    std::vector<double> sums((size_t)4 * d + 2, 0.0);
+    PostChunks pc;
+    BufRef pr;
+    Partials part;
+    double *rowv = nullptr;
     if (n > 0) {
-        const int64_t chunk = held_chunk_rows(n, k);
-        const size_t rows = (size_t)std::min(chunk, n);
-        const int64_t plen = heldout_part_len(d, k);
-        const int grid = heldout_score_grid((int64_t)rows, d, k, ctx->n_cu);
-        BufRef st, cv, pr;
-        Partials part;
-        if (int rc = dev_alloc(sizeof(double) * rows * k, &st)) return rc;
-        if (int rc = dev_alloc(sizeof(double) * rows * k * k, &cv)) return rc;
-        if (int rc = part.alloc(grid, plen)) return rc;
-        if (per_row)
+        if (int rc = pc.alloc(n, held_chunk_rows(n, d, k, 0), k)) return rc;
+        if (int rc = part.alloc(heldout_score_grid((int64_t)pc.rows, d, k, ctx->n_cu), heldout_part_len(d, k))) return rc;
+        if (per_row) {
             if (int rc = dev_alloc(sizeof(double) * (size_t)n, &pr)) return rc;
-        double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
-        double *rowv = pr ? static_cast<double *>(pr->p) : nullptr;
-        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            ppca_dataset tp = row_slice(train, r0, chunk), hp = row_slice(held, r0, chunk);
-            if (int rc = run_post(ctx, &tp, model, nullptr, states, covs, nullptr, 0, nullptr)) return rc;
-            const int g = heldout_score_grid(tp.n, d, k, ctx->n_cu);  // (<= grid: the last chunk may be shorter)
-            HIP_TRY(launch_heldout_score(hp.X, hp.d, tp.w, d, k, tp.n, model->p(), states, covs, rowv ? rowv + r0 : nullptr, part.p, g,
-                                         ctx->stream));
-            HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+            rowv = static_cast<double *>(pr->p);
         }
-        HIP_TRY(hipMemcpyAsync(sums.data(), part.red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
-        if (per_row)  // (host or device destination, as ppca_llk's per-sample output)
-            HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (int rc = pc.each(train, [&](ppca_dataset &tp, int64_t r0) -> int {
+                ppca_dataset hp = row_slice(held, r0, pc.chunk);
+                if (int rc = run_post(ctx, &tp, model, nullptr, pc.states, pc.covs, nullptr, 0, nullptr)) return rc;
+                const int g = heldout_score_grid(tp.n, d, k, ctx->n_cu);  // (<= part.grid: the last chunk may be shorter)
+                HIP_TRY(launch_heldout_score(hp.X, hp.d, tp.w, d, k, tp.n, model->p(), pc.states, pc.covs, rowv ? rowv + r0 : nullptr,
+                                             part.p, g, ctx->stream));
+                HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+                return PPCA_OK;
+            }))
+            return rc;
     }
-    held_totals(sums.data(), d, totals_host);
-    if (col_sums_host) std::memcpy(col_sums_host, sums.data(), sizeof(double) * (size_t)4 * d);
-    return PPCA_OK;
+    return held_finish(ctx, n, d, part.red, rowv, totals_host, col_sums_host, per_row);
 }
 
 // ------------------------------------------------------------------ mixture
+// The largest state size of the components (at least 1): what the chunked passes size their posterior scratch for.
+static int mix_kmax(ppca_model *const *models, int nm) {
+    int kmax = 1;
+    for (int c = 0; c < nm; ++c) kmax = std::max(kmax, models[c]->k);
+    return kmax;
+}
+
 static int mix_check(ppca_dataset *ds, ppca_model *const *models, int32_t nm) {
     if (!ds || !models || nm < 1) return fail(PPCA_ERR_INVALID, "bad mixture arguments");
     // components may have different state sizes (mix.rs:50-71, state_sizes :91): every pass below runs per
@@ -2242,49 +2276,37 @@ extern "C" int ppca_mix_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_d
     USE_CTX(ctx);
     const int64_t n = train->n;
     const int d = train->d, nm = n_models;
-    std::vector<double> sums((size_t)4 * d + 2, 0.0);
+    PostChunks pc;
+    BufRef llk, u, lse, lp, fo, pr;
+    Partials part;
+    double *rowv = nullptr;
     if (n > 0) {
-        BufRef llk, u, lse, lp;
         if (int rc = mix_posteriors(ctx, train, models, log_weights, nm, llk, u, lse, &lp)) return rc;
         const double *logpost = static_cast<const double *>(lp->p);
-        int kmax = 1;
-        for (int c = 0; c < nm; ++c) kmax = std::max(kmax, models[c]->k);
-        int64_t chunk = chunk_rows(n, (int64_t)sizeof(double) * ((int64_t)kmax * kmax + kmax + (int64_t)5 * d));
-        if (const char *e = getenv("PPCA_HELD_CHUNK")) {
-            const long long v = atoll(e);
-            if (v > 0) chunk = v;
-        }
-        const size_t rows = (size_t)std::min(chunk, n);
-        const int64_t plen = heldout_part_len(d, 0);
-        const int grid = heldout_score_grid((int64_t)rows, d, 0, ctx->n_cu);
-        BufRef st, cv, fo, pr;
-        Partials part;
-        if (int rc = dev_alloc(sizeof(double) * rows * kmax, &st)) return rc;
-        if (int rc = dev_alloc(sizeof(double) * rows * kmax * kmax, &cv)) return rc;
-        if (int rc = dev_alloc(sizeof(double) * rows * d * 5, &fo)) return rc;
-        if (int rc = part.alloc(grid, plen)) return rc;
-        if (per_row)
+        const int kmax = mix_kmax(models, nm);
+        if (int rc = pc.alloc(n, held_chunk_rows(n, d, kmax, 5), kmax)) return rc;
+        if (int rc = dev_alloc(sizeof(double) * pc.rows * d * 5, &fo)) return rc;
+        if (int rc = part.alloc(heldout_score_grid((int64_t)pc.rows, d, 0, ctx->n_cu), heldout_part_len(d, 0))) return rc;
+        if (per_row) {
             if (int rc = dev_alloc(sizeof(double) * (size_t)n, &pr)) return rc;
-        double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p), *fold = static_cast<double *>(fo->p);
-        double *rowv = pr ? static_cast<double *>(pr->p) : nullptr;
-        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            ppca_dataset tp = row_slice(train, r0, chunk), hp = row_slice(held, r0, chunk);
-            for (int c = 0; c < nm; ++c) {
-                if (int rc = run_post(ctx, &tp, models[c], nullptr, states, covs, nullptr, 0, nullptr)) return rc;
-                HIP_TRY(launch_heldout_fold(hp.X, hp.d, d, models[c]->k, tp.n, models[c]->p(), states, covs, logpost + r0 * nm, c, nm,
-                                            fold, heldout_score_grid(tp.n, d, models[c]->k, ctx->n_cu), ctx->stream));
-            }
-            const int g = heldout_score_grid(tp.n, d, 0, ctx->n_cu);
-            HIP_TRY(launch_heldout_finish(hp.X, hp.d, tp.w, d, tp.n, fold, rowv ? rowv + r0 : nullptr, part.p, g, ctx->stream));
-            HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+            rowv = static_cast<double *>(pr->p);
         }
-        HIP_TRY(hipMemcpyAsync(sums.data(), part.red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
-        if (per_row) HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        double *fold = static_cast<double *>(fo->p);
+        if (int rc = pc.each(train, [&](ppca_dataset &tp, int64_t r0) -> int {
+                ppca_dataset hp = row_slice(held, r0, pc.chunk);
+                for (int c = 0; c < nm; ++c) {
+                    if (int rc = run_post(ctx, &tp, models[c], nullptr, pc.states, pc.covs, nullptr, 0, nullptr)) return rc;
+                    HIP_TRY(launch_heldout_fold(hp.X, hp.d, d, models[c]->k, tp.n, models[c]->p(), pc.states, pc.covs, logpost + r0 * nm,
+                                                c, nm, fold, heldout_score_grid(tp.n, d, models[c]->k, ctx->n_cu), ctx->stream));
+                }
+                const int g = heldout_score_grid(tp.n, d, 0, ctx->n_cu);
+                HIP_TRY(launch_heldout_finish(hp.X, hp.d, tp.w, d, tp.n, fold, rowv ? rowv + r0 : nullptr, part.p, g, ctx->stream));
+                HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+                return PPCA_OK;
+            }))
+            return rc;
     }
-    held_totals(sums.data(), d, totals_host);
-    if (col_sums_host) std::memcpy(col_sums_host, sums.data(), sizeof(double) * (size_t)4 * d);
-    return PPCA_OK;
+    return held_finish(ctx, n, d, part.red, rowv, totals_host, col_sums_host, per_row);
 }
 
 // Per chunk of rows: each component's LOO pass folded into per-entry state (launch_mix_loo_fold), the mean and L_j, then -- when the
@@ -2314,34 +2336,34 @@ extern "C" int ppca_mix_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, ppca_mod
         BufRef llk, u, lse, lp;
         if (int rc = mix_posteriors(ctx, ds, models, log_weights, nm, llk, u, lse, &lp)) return rc;
         const double *logpost = static_cast<const double *>(lp->p);
-        int kmax = 1;
-        for (int c = 0; c < nm; ++c) kmax = std::max(kmax, models[c]->k);
+        const int kmax = mix_kmax(models, nm);
         // per row and dimension: the component's m, v, l and the state mx, sm, wm
-        const int64_t chunk = loo_chunk_rows(n, d, kmax, 6);
-        const size_t rows = (size_t)std::min(chunk, n), nd = rows * (size_t)d;
-        BufRef st, cv, sc;
-        if (int rc = dev_alloc(sizeof(double) * rows * kmax, &st)) return rc;
-        if (int rc = dev_alloc(sizeof(double) * rows * kmax * kmax, &cv)) return rc;
+        PostChunks pc;
+        if (int rc = pc.alloc(n, loo_chunk_rows(n, d, kmax, 6), kmax)) return rc;
+        const size_t nd = pc.rows * (size_t)d;
+        BufRef sc;
         if (int rc = dev_alloc(sizeof(double) * nd * 6, &sc)) return rc;
-        double *states = static_cast<double *>(st->p), *covs = static_cast<double *>(cv->p);
         double *m = static_cast<double *>(sc->p), *v = m + nd, *ell = v + nd, *mx = ell + nd, *sm = mx + nd, *wm = sm + nd;
-        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            ppca_dataset part = row_slice(ds, r0, chunk);
-            const double *lpc = logpost + r0 * nm;
-            for (int c = 0; c < nm; ++c) {
-                if (int rc = loo_part(ctx, &part, models[c], states, covs, want_m ? m : nullptr, nullptr, ell, nullptr)) return rc;
-                HIP_TRY(launch_mix_loo_fold(part.X, d, d, part.n, lpc, c, nm, m, ell, mx, sm, want_m ? wm : nullptr, c == 0,
-                                            ctx->stream));
-            }
-            double *mean_c = mean ? mean + r0 * d : (want_m ? wm : nullptr);
-            HIP_TRY(launch_mix_loo_finish(part.X, d, d, part.n, mx, sm, wm, mean_c, llks ? llks + r0 : nullptr, ctx->n_cu, ctx->stream));
-            if (var)
+        if (int rc = pc.each(ds, [&](ppca_dataset &part, int64_t r0) -> int {
+                const double *lpc = logpost + r0 * nm;
                 for (int c = 0; c < nm; ++c) {
-                    if (int rc = loo_part(ctx, &part, models[c], states, covs, m, v, ell, nullptr)) return rc;
-                    HIP_TRY(launch_mix_loo_var(part.X, d, d, part.n, lpc, c, nm, m, v, ell, mx, mean_c, var + r0 * d, c == 0,
-                                               ctx->stream));
+                    if (int rc = loo_part(ctx, &part, models[c], pc.states, pc.covs, want_m ? m : nullptr, nullptr, ell, nullptr))
+                        return rc;
+                    HIP_TRY(launch_mix_loo_fold(part.X, d, d, part.n, lpc, c, nm, m, ell, mx, sm, want_m ? wm : nullptr, c == 0,
+                                                ctx->stream));
                 }
-        }
+                double *mean_c = mean ? mean + r0 * d : (want_m ? wm : nullptr);
+                HIP_TRY(launch_mix_loo_finish(part.X, d, d, part.n, mx, sm, wm, mean_c, llks ? llks + r0 : nullptr, ctx->n_cu,
+                                              ctx->stream));
+                if (var)
+                    for (int c = 0; c < nm; ++c) {
+                        if (int rc = loo_part(ctx, &part, models[c], pc.states, pc.covs, m, v, ell, nullptr)) return rc;
+                        HIP_TRY(launch_mix_loo_var(part.X, d, d, part.n, lpc, c, nm, m, v, ell, mx, mean_c, var + r0 * d, c == 0,
+                                                   ctx->stream));
+                    }
+                return PPCA_OK;
+            }))
+            return rc;
     }
     if (int rc = loo_totals(ctx, ds, llks, total_host, per_sample_host)) return rc;
     if (mean_out) *mean_out = md.release();
@@ -3290,12 +3312,7 @@ static int h_check(const ppca_dataset *ds, const ppca_dataset *prec, const ppca_
 // Rows of a chunk: the record, the posterior mean and the log-density of a row are its scratch (chunk_rows: under 1 GiB).
 // PPCA_H_CHUNK=rows forces a chunk length (tests: several chunks at small N).
 static int64_t h_chunk_rows(int64_t n, int k) {
-    int64_t c = chunk_rows(n, (int64_t)sizeof(double) * (hetero_nrp(k) + k + 1));
-    if (const char *e = getenv("PPCA_H_CHUNK")) {
-        const long long v = atoll(e);
-        if (v > 0) c = v;
-    }
-    return c;
+    return chunk_override("PPCA_H_CHUNK", chunk_rows(n, (int64_t)sizeof(double) * (hetero_nrp(k) + k + 1)));
 }
 
 // What a sweep keeps alive until the caller's synchronisation.

@@ -2,7 +2,7 @@
 //
 //   holdout_kernel   one sweep over an N x d dataset (row stride ldx): one read, two writes.  Entry (i, j) of global row
 //                    g = row_offset + i draws u = (row_word(row_key(seed, 8, g), j) >> 11) 2^-53 from the counter-based generator of
-//                    ppca_sample.hip (restated below, stream 8); an observed (finite) entry is HELD iff u < fraction:
+//                    ppca_sweep.hpp (u01_floor, STREAM_HOLDOUT); an observed (finite) entry is HELD iff u < fraction:
 //                      held:   train = NaN, held = x (the bits as they are)        kept:   train = x, held = NaN
 //                      masked (any non-finite value): NaN in both
 //                    part[workgroup][2] = the workgroup's [kept, held] entry counts (integers, as doubles).  Nothing depends on the
@@ -22,58 +22,13 @@
 //                    same kernel once per component in a form that folds (m, v, l) into per-entry state, then a form that sums it.
 #include <algorithm>
 
-#include "ppca_device.hpp"
+#include "ppca_sweep.hpp"
 
 namespace ppca {
 namespace {
 
-constexpr uint64_t STREAM_HOLDOUT = 8;
 constexpr int HOLD_THREADS = 256;
 constexpr int HOLD_ROWS = 4;  // row steps a thread has in flight
-constexpr double LOG_2PI = 1.8378770664093454836;
-
-// The generator of ppca_sample.hip, restated: splitmix64's finaliser, a key per (seed, stream, row), a
-// word per (key, index).
-__device__ __forceinline__ uint64_t smix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t stream, uint64_t grow) {
-    return smix64(smix64(seed ^ (stream * 0xD1342543DE82EF95ull)) + grow);
-}
-__device__ __forceinline__ uint64_t row_word(uint64_t key, uint64_t p) { return smix64(key + p * 0xA0761D6478BD642Full); }
-
-typedef double d2_t __attribute__((ext_vector_type(2)));
-
-template <int VEC>
-struct Vec {
-    double v[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ Vec<VEC> load_nt(const double *p) {
-    Vec<VEC> r;
-    if constexpr (VEC == 2) {
-        const d2_t t = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(p));
-        r.v[0] = t.x;
-        r.v[1] = t.y;
-    } else {
-        r.v[0] = __builtin_nontemporal_load(p);
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void store_nt(double *p, const Vec<VEC> &r) {
-    if constexpr (VEC == 2) {
-        d2_t t;
-        t.x = r.v[0];
-        t.y = r.v[1];
-        __builtin_nontemporal_store(t, reinterpret_cast<d2_t *>(p));
-    } else {
-        __builtin_nontemporal_store(r.v[0], p);
-    }
-}
 
 struct HoldArgs {
     const double *X;
@@ -92,10 +47,9 @@ template <int VEC>
 __global__ __launch_bounds__(HOLD_THREADS) void holdout_kernel(HoldArgs a) {
     __shared__ unsigned long long red[2][HOLD_THREADS / 64];
     const int t = threadIdx.x, d = a.d;
-    const int tpr = 1 << a.tpr_log2, rps = HOLD_THREADS >> a.tpr_log2;
-    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
-    const int slots = (d + VEC - 1) / VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    int tpr, rps, tc, tr, slots;
+    int64_t r0, r1;
+    sweep_layout<HOLD_THREADS, VEC>(t, d, a.tpr_log2, a.rows_per_wg, a.n, tpr, rps, tc, tr, slots, r0, r1);
     const double qnan = __builtin_nan("");
     unsigned long long kept = 0, heldc = 0;
     for (int c0 = 0; c0 < slots; c0 += tpr) {
@@ -108,7 +62,7 @@ __global__ __launch_bounds__(HOLD_THREADS) void holdout_kernel(HoldArgs a) {
             for (int u = 0; u < HOLD_ROWS; ++u) {
                 const int64_t r = rb + (int64_t)u * rps + tr;
                 if (on && r < r1) {
-                    x[u] = load_nt<VEC>(a.X + r * a.ldx + j);
+                    x[u] = load_vec<VEC, true>(a.X + r * a.ldx + j);
                 } else {
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) x[u].v[v] = qnan;
@@ -124,15 +78,15 @@ __global__ __launch_bounds__(HOLD_THREADS) void holdout_kernel(HoldArgs a) {
                 for (int v = 0; v < VEC; ++v) {
                     const double xv = x[u].v[v];
                     const bool obs = __builtin_isfinite(xv);
-                    const double uu = (double)(row_word(key, (uint64_t)(j + v)) >> 11) * (1.0 / 9007199254740992.0);
+                    const double uu = u01_floor(row_word(key, (uint64_t)(j + v)));
                     const bool hold = obs && uu < a.fraction;
                     tv.v[v] = (obs && !hold) ? xv : qnan;
                     hv.v[v] = hold ? xv : qnan;
                     kept += (obs && !hold) ? 1u : 0u;
                     heldc += hold ? 1u : 0u;
                 }
-                store_nt<VEC>(a.train + r * d + j, tv);
-                store_nt<VEC>(a.held + r * d + j, hv);
+                store_vec<VEC, true>(a.train + r * d + j, tv);
+                store_vec<VEC, true>(a.held + r * d + j, hv);
             }
         }
     }
@@ -153,10 +107,7 @@ __global__ __launch_bounds__(HOLD_THREADS) void holdout_kernel(HoldArgs a) {
     }
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---- the score
-__host__ __device__ inline int held_kq(int k) { return (k + 15) / 16 * 16; }
 constexpr int HELD_LIST = 128;  // the list holds < 64 entries before a block of <= 64 is appended
 
 struct HeldArgs {
@@ -185,14 +136,14 @@ enum { HELD_MODEL = 0, HELD_FOLD = 1, HELD_FINISH = 2 };
 // per-entry state instead of summed (the first component initialises it; a component of weight 0 contributes nothing).
 // HELD_FINISH: per held entry l = mx + ln sm, e = -A, variance V + max(Q - A^2, 0) from the folded state (k = 0: no Sigma), summed as
 // HELD_MODEL sums its own.
-// LDS: Sigma padded to kq = 16 ceil(k / 16) columns with zeros (k x kq) | z padded (kq) | the list's values (HELD_LIST) | the list's
+// LDS: Sigma padded to kq = pad16(k) columns with zeros (k x kq) | z padded (kq) | the list's values (HELD_LIST) | the list's
 // columns (HELD_LIST ints) | when they fit 64 KiB with the rest (sums_in_lds): the column sums (4 d), l of the row's columns (d).
 // Otherwise those 5 d doubles are the workgroup's own partial in global memory, [sums (4 d) | 2 counts | l slots (d, back at 0 when
 // the kernel ends)], read and written by this wave alone with a barrier between a write and the next read of a slot.
 template <int MODE>
 __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
     extern __shared__ double lds[];
-    const int k = a.k, d = a.d, kq = held_kq(k), lane = threadIdx.x;
+    const int k = a.k, d = a.d, kq = pad16(k), lane = threadIdx.x;
     double *S = lds, *Z = S + (size_t)k * kq, *lx = Z + kq;
     int *lj = reinterpret_cast<int *>(lx + HELD_LIST);
     double *part = nullptr, *cs = nullptr, *L = nullptr;
@@ -247,7 +198,8 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
                 double e2, v, l;
                 if constexpr (MODE != HELD_FINISH) {
                     const double *cj = C + (int64_t)j * k;
-                    // q = c_j^T Sigma c_j by blocks of 16 columns of Sigma (loo_kernel's loop); the padding columns are 0
+                    // q = c_j^T Sigma c_j by blocks of 16 columns of Sigma: the loop of loo_kernel (ppca_loo.hip, see the note there)
+                    // without |c_j|^2; the padding columns are 0
                     double dot = 0.0, q = 0.0;
                     for (int b0 = 0; b0 < k; b0 += 16) {
                         double acc[16];
@@ -272,7 +224,7 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
                         double M = a.first ? -INFINITY : a.mx[o], Sm = a.first ? 0.0 : a.sm[o];
                         double A = a.first ? 0.0 : a.fa[o], V = a.first ? 0.0 : a.fv[o], Q = a.first ? 0.0 : a.fq[o];
                         const double tc = lp + l;
-                        if (tc > M) {  // the running maximum of mix_loo_fold_kernel
+                        if (tc > M) {  // the log-sum-exp push of mix_loo_fold_kernel (ppca_loo.hip), which also rescales its W
                             Sm = Sm * exp(M - tc) + 1.0;
                             M = tc;
                         } else if (tc > -INFINITY) {
@@ -356,12 +308,9 @@ int holdout_grid(int64_t n, int d, int n_cu) { return scale_grid(n, d, n_cu); }
 hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double fraction, uint64_t seed, int64_t row_offset,
                           double *train, double *held, double *part, int grid, hipStream_t s) {
     if (n <= 0 || grid <= 0) return hipSuccess;
-    const bool vec = d % 2 == 0 && ldx % 2 == 0 && aligned16(X) && aligned16(train) && aligned16(held);
-    const int slots = vec ? d / 2 : d;
-    int lg = 0;
-    while ((1 << lg) < slots && lg < 8) ++lg;
-    HoldArgs a{X, ldx, n, d, fraction, seed, row_offset, train, held, part, lg, (n + grid - 1) / grid};
-    if (vec)
+    const SweepCut cut = sweep_cut(d, ldx % 2 == 0, {X, train, held});
+    HoldArgs a{X, ldx, n, d, fraction, seed, row_offset, train, held, part, cut.tpr_log2, (n + grid - 1) / grid};
+    if (cut.vec)
         hipLaunchKernelGGL(holdout_kernel<2>, dim3((unsigned)grid), dim3(HOLD_THREADS), 0, s, a);
     else
         hipLaunchKernelGGL(holdout_kernel<1>, dim3((unsigned)grid), dim3(HOLD_THREADS), 0, s, a);
@@ -369,7 +318,7 @@ hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double
 }
 
 static size_t held_lds_base(int k) {
-    const int kq = held_kq(k);
+    const int kq = pad16(k);
     return sizeof(double) * ((size_t)k * kq + kq + HELD_LIST) + sizeof(int) * HELD_LIST;
 }
 static bool held_sums_in_lds(int d, int k) { return held_lds_base(k) + sizeof(double) * (size_t)5 * d <= 64 * 1024; }

@@ -23,7 +23,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "ppca_device.hpp"
+#include "ppca_sweep.hpp"
 
 namespace ppca {
 
@@ -1484,19 +1484,14 @@ __global__ __launch_bounds__(256) void finalize_qprep_multi_kernel(MixFinalArgs 
 }
 
 // ------------------------------------------------------------------ synthetic data
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// (the generator and its streams: ppca_sweep.hpp)
 __device__ __forceinline__ uint64_t rng_bits(uint64_t seed, uint64_t stream, uint64_t row, uint64_t col) {
-    return mix64(mix64(mix64(seed ^ (stream * 0xD1342543DE82EF95ull)) + row) + col * 0xA0761D6478BD642Full);
+    return row_word(row_key(seed, stream, row), col);
 }
-__device__ __forceinline__ double rng_u01(uint64_t bits) { return ((double)(bits >> 11) + 0.5) * (1.0 / 9007199254740992.0); }
+// fp64 Box-Muller from two words: not the draw of ppca_sample.hip's normal_pair
 __device__ __forceinline__ double rng_normal(uint64_t seed, uint64_t stream, uint64_t row, uint64_t col) {
-    double u1 = rng_u01(rng_bits(seed, stream, row, 2 * col));
-    double u2 = rng_u01(rng_bits(seed, stream, row, 2 * col + 1));
+    double u1 = u01_open(rng_bits(seed, stream, row, 2 * col));
+    double u2 = u01_open(rng_bits(seed, stream, row, 2 * col + 1));
     return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
 }
 
@@ -1505,7 +1500,7 @@ __global__ void synth_latent_kernel(double *z, int64_t row_offset, int64_t n_row
     if (idx >= n_rows * k) return;
     int64_t i = idx / k;
     int a = (int)(idx - i * k);
-    z[idx] = rng_normal(seed, 1, (uint64_t)(row_offset + i), (uint64_t)a);
+    z[idx] = rng_normal(seed, STREAM_SYNTH_LATENT, (uint64_t)(row_offset + i), (uint64_t)a);
 }
 
 __global__ void synth_data_kernel(const double *c, const double *mean, const double *z, double *x, int64_t row_offset,
@@ -1516,13 +1511,13 @@ __global__ void synth_data_kernel(const double *c, const double *mean, const dou
     int64_t i = idx / d;
     int j = (int)(idx - i * d);
     const uint64_t grow = (uint64_t)(row_offset + i);
-    double v = mean[j] + sigma * rng_normal(seed, 2, grow, (uint64_t)j);
+    double v = mean[j] + sigma * rng_normal(seed, STREAM_SYNTH_NOISE, grow, (uint64_t)j);
     for (int a = 0; a < k; ++a) v += c[(int64_t)j * k + a] * z[i * k + a];
     bool masked;
     if (mask_kind == 0) {
-        masked = rng_u01(rng_bits(seed, 3, grow, (uint64_t)j)) < mask_prob;
+        masked = u01_open(rng_bits(seed, STREAM_SYNTH_MASK, grow, (uint64_t)j)) < mask_prob;
     } else {
-        int start = (int)(rng_u01(rng_bits(seed, 4, grow, 0)) * d);
+        int start = (int)(u01_open(rng_bits(seed, STREAM_SYNTH_RUN, grow, 0)) * d);
         int off = j - start;
         if (off < 0) off += d;
         masked = off < mask_run;

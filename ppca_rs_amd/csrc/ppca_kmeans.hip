@@ -25,7 +25,7 @@
 // moments_multi_kernel uses e_ci): 3 fp64 operations per element and centre, no LDS.
 #include <algorithm>
 
-#include "ppca_device.hpp"
+#include "ppca_sweep.hpp"
 
 namespace ppca {
 namespace {
@@ -33,8 +33,6 @@ namespace {
 constexpr int KM_THREADS = 256;
 constexpr int KM_ROWS = 4;  // row steps a thread has in flight
 constexpr int WD_BLOCK = 4096;
-
-typedef double d2_t __attribute__((ext_vector_type(2)));
 
 struct KMeansArgs {
     const double *X;
@@ -52,17 +50,6 @@ struct KMeansArgs {
     int tpr_log2;       // threads per row = 1 << tpr_log2
     int64_t rows_per_wg;
 };
-
-template <int VEC>
-__device__ __forceinline__ void load_nt(const double *p, double *out) {
-    if constexpr (VEC == 2) {
-        const d2_t t = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(p));
-        out[0] = t.x;
-        out[1] = t.y;
-    } else {
-        out[0] = __builtin_nontemporal_load(p);
-    }
-}
 
 // dv[NR][KB] over the row's threads: a butterfly over min(tpr, 64) lanes (groups are aligned powers of two), then the row's
 // waves in index order through rs.  (uniform over the workgroup: two barriers when tpr > 64)
@@ -128,10 +115,9 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(KMeansArgs a) {
     __shared__ double red[KM_THREADS];
     __shared__ double rs[RH * KB][4];
     const int t = threadIdx.x, d = a.d;
-    const int tpr = 1 << a.tpr_log2, rps = KM_THREADS >> a.tpr_log2;
-    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
-    const int slots = (d + VEC - 1) / VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    int tpr, rps, tc, tr, slots;
+    int64_t r0, r1;
+    sweep_layout<KM_THREADS, VEC>(t, d, a.tpr_log2, a.rows_per_wg, a.n, tpr, rps, tc, tr, slots, r0, r1);
     const double qnan = __builtin_nan("");
     bool on[NS];
     int j[NS];
@@ -153,17 +139,17 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(KMeansArgs a) {
     }
     double inert = 0.0;
     for (int64_t rb = r0; rb < r1; rb += (int64_t)rps * KM_ROWS) {  // (uniform trip count: the row sums meet at barriers)
-        double x[KM_ROWS][NS][VEC];
+        Vec<VEC> x[KM_ROWS][NS];
 #pragma unroll
         for (int u = 0; u < KM_ROWS; ++u) {
             const int64_t r = rb + (int64_t)u * rps + tr;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 if (on[s] && r < r1) {
-                    load_nt<VEC>(a.X + r * a.ldx + j[s], x[u][s]);
+                    x[u][s] = load_vec<VEC, true>(a.X + r * a.ldx + j[s]);
                 } else {
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) x[u][s][v] = qnan;
+                    for (int v = 0; v < VEC; ++v) x[u][s].v[v] = qnan;
                 }
             }
         }
@@ -180,8 +166,8 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(KMeansArgs a) {
                 for (int s = 0; s < NS; ++s)
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
-                        const bool obs = __builtin_isfinite(x[u][s][v]);
-                        const double e = obs ? __dmul_rn(__dsub_rn(x[u][s][v], mu[q][s][v]), av[s][v]) : 0.0;
+                        const bool obs = __builtin_isfinite(x[u][s].v[v]);
+                        const double e = obs ? __dmul_rn(__dsub_rn(x[u][s].v[v], mu[q][s][v]), av[s][v]) : 0.0;
                         acc = fma(e, e, acc);
                     }
                 dv[uh][q] = acc;
@@ -208,8 +194,8 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(KMeansArgs a) {
                 for (int s = 0; s < NS; ++s)
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
-                        const bool obs = __builtin_isfinite(x[u][s][v]);
-                        const double xv = obs ? x[u][s][v] : 0.0;
+                        const bool obs = __builtin_isfinite(x[u][s].v[v]);
+                        const double xv = obs ? x[u][s].v[v] : 0.0;
 #pragma unroll
                         for (int q = 0; q < KB; ++q) {
                             const bool mine = obs && lab == a.k0 + q;
@@ -256,10 +242,9 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_wide_kernel(KMeansArgs a) {
     __shared__ double red[KM_THREADS];
     __shared__ double rs[KM_ROWS * KB][4];
     const int t = threadIdx.x, d = a.d;
-    const int tpr = 1 << a.tpr_log2, rps = KM_THREADS >> a.tpr_log2;
-    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
-    const int slots = (d + VEC - 1) / VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    int tpr, rps, tc, tr, slots;
+    int64_t r0, r1;
+    sweep_layout<KM_THREADS, VEC>(t, d, a.tpr_log2, a.rows_per_wg, a.n, tpr, rps, tc, tr, slots, r0, r1);
     const double qnan = __builtin_nan("");
     double inert = 0.0;
     for (int64_t rb = r0; rb < r1; rb += (int64_t)rps * KM_ROWS) {
@@ -272,15 +257,16 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_wide_kernel(KMeansArgs a) {
             const int slot = c0 + tc;
             const bool on = slot < slots;
             const int j = slot * VEC;
-            double x[KM_ROWS][VEC], av[VEC], mu[KB][VEC];
+            Vec<VEC> x[KM_ROWS];
+            double av[VEC], mu[KB][VEC];
 #pragma unroll
             for (int u = 0; u < KM_ROWS; ++u) {
                 const int64_t r = rb + (int64_t)u * rps + tr;
                 if (on && r < r1) {
-                    load_nt<VEC>(a.X + r * a.ldx + j, x[u]);
+                    x[u] = load_vec<VEC, true>(a.X + r * a.ldx + j);
                 } else {
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) x[u][v] = qnan;
+                    for (int v = 0; v < VEC; ++v) x[u].v[v] = qnan;
                 }
             }
 #pragma unroll
@@ -293,10 +279,10 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_wide_kernel(KMeansArgs a) {
             for (int u = 0; u < KM_ROWS; ++u)
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
-                    const bool obs = __builtin_isfinite(x[u][v]);
+                    const bool obs = __builtin_isfinite(x[u].v[v]);
 #pragma unroll
                     for (int q = 0; q < KB; ++q) {
-                        const double e = obs ? __dmul_rn(__dsub_rn(x[u][v], mu[q][v]), av[v]) : 0.0;
+                        const double e = obs ? __dmul_rn(__dsub_rn(x[u].v[v], mu[q][v]), av[v]) : 0.0;
                         dv[u][q] = fma(e, e, dv[u][q]);
                     }
                 }
@@ -324,10 +310,9 @@ template <int VEC, int KB>
 __global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(KMeansArgs a) {
     __shared__ double red[KM_THREADS];
     const int t = threadIdx.x, d = a.d;
-    const int tpr = 1 << a.tpr_log2, rps = KM_THREADS >> a.tpr_log2;
-    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
-    const int slots = (d + VEC - 1) / VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    int tpr, rps, tc, tr, slots;
+    int64_t r0, r1;
+    sweep_layout<KM_THREADS, VEC>(t, d, a.tpr_log2, a.rows_per_wg, a.n, tpr, rps, tc, tr, slots, r0, r1);
     double *part = a.part + (int64_t)blockIdx.x * a.plen;
     const double qnan = __builtin_nan("");
     for (int c0 = 0; c0 < slots; c0 += tpr) {
@@ -343,17 +328,18 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(KMeansArgs a)
                 tot[q][v] = sum[q][v] = 0.0;
             }
         for (int64_t rb = r0; rb < r1; rb += (int64_t)rps * KM_ROWS) {
-            double x[KM_ROWS][VEC], wr[KM_ROWS];
+            Vec<VEC> x[KM_ROWS];
+            double wr[KM_ROWS];
             int lab[KM_ROWS];
 #pragma unroll
             for (int u = 0; u < KM_ROWS; ++u) {
                 const int64_t r = rb + (int64_t)u * rps + tr;
                 const bool live = on && r < r1;
                 if (live) {
-                    load_nt<VEC>(a.X + r * a.ldx + j, x[u]);
+                    x[u] = load_vec<VEC, true>(a.X + r * a.ldx + j);
                 } else {
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) x[u][v] = qnan;
+                    for (int v = 0; v < VEC; ++v) x[u].v[v] = qnan;
                 }
                 wr[u] = live ? (a.w ? a.w[r] : 1.0) : 0.0;
                 lab[u] = live ? a.labels[r] : -1;
@@ -362,8 +348,8 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_update_kernel(KMeansArgs a)
             for (int u = 0; u < KM_ROWS; ++u)
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
-                    const bool obs = __builtin_isfinite(x[u][v]);
-                    const double xv = obs ? x[u][v] : 0.0;
+                    const bool obs = __builtin_isfinite(x[u].v[v]);
+                    const double xv = obs ? x[u].v[v] : 0.0;
 #pragma unroll
                     for (int q = 0; q < KB; ++q) {
                         const bool mine = obs && lab[u] == a.k0 + q;
@@ -410,8 +396,6 @@ __global__ __launch_bounds__(KM_THREADS) void wd_block_kernel(const double *w, c
     if (t == 0) out[blockIdx.x] = red[0];
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int kmeans_kb(int nc) { return nc <= 1 ? 1 : (nc <= 4 ? 4 : KMEANS_KB_MAX); }
 
 template <int VEC, int NS, bool ACC>
@@ -444,12 +428,6 @@ void launch_update(int kb, dim3 g, dim3 b, hipStream_t s, const KMeansArgs &a) {
         hipLaunchKernelGGL((kmeans_update_kernel<VEC, KMEANS_KB_MAX>), g, b, 0, s, a);
 }
 
-int log2_ceil(int v, int cap) {
-    int lg = 0;
-    while ((1 << lg) < v && lg < cap) ++lg;
-    return lg;
-}
-
 }  // namespace
 
 // One wave of workgroups, each with one equal run of rows: what is resident at once at the fused kernel's register count.
@@ -465,12 +443,11 @@ hipError_t launch_kmeans_assign(const double *X, int64_t ldx, const double *w, i
                                 int inertia, int grid, hipStream_t s) {
     if (n <= 0 || grid <= 0) return hipSuccess;
     if (nc < 1 || nc > KMEANS_KB_MAX || (carry && (!labels || !dist)) || ((accumulate || inertia) && !part)) return hipErrorInvalidValue;
-    const bool vec = d % 2 == 0 && ldx % 2 == 0 && aligned16(X);
-    const int slots = vec ? d / 2 : d;
+    const auto [vec, slots, lg] = sweep_cut(d, ldx % 2 == 0, {X});
     const int ns = slots <= KM_THREADS ? 1 : ((!vec && slots <= 2 * KM_THREADS) ? 2 : 0);  // 0: wider than the workgroup
     if (accumulate && (ns == 0 || carry || k0 != 0)) return hipErrorInvalidValue;
     KMeansArgs a{X, ldx, n, d, w, mu_dev, a_dev, nc, k0, carry, labels, dist, part, plen, inertia,
-                 log2_ceil(ns == 2 ? (slots + 1) / 2 : slots, 8), (n + grid - 1) / grid};
+                 ns == 2 ? sweep_tpr_log2((slots + 1) / 2) : lg, (n + grid - 1) / grid};
     const dim3 g((unsigned)grid), b(KM_THREADS);
     const int kb = kmeans_kb(nc);
     if (ns == 0) {
@@ -500,12 +477,11 @@ hipError_t launch_kmeans_update(const double *X, int64_t ldx, const double *w, i
                                 const int32_t *labels, double *part, int64_t plen, int grid, hipStream_t s) {
     if (n <= 0 || grid <= 0) return hipSuccess;
     if (nc < 1 || nc > KMEANS_KB_MAX || !labels || !part) return hipErrorInvalidValue;
-    const bool vec = d % 2 == 0 && ldx % 2 == 0 && aligned16(X);
-    const int slots = vec ? d / 2 : d;
-    KMeansArgs a{X, ldx, n, d, w, mu_dev, nullptr, nc, k0, 0, const_cast<int32_t *>(labels), nullptr, part, plen, 0, log2_ceil(slots, 8),
+    const SweepCut cut = sweep_cut(d, ldx % 2 == 0, {X});
+    KMeansArgs a{X, ldx, n, d, w, mu_dev, nullptr, nc, k0, 0, const_cast<int32_t *>(labels), nullptr, part, plen, 0, cut.tpr_log2,
                  (n + grid - 1) / grid};
     const dim3 g((unsigned)grid), b(KM_THREADS);
-    if (vec)
+    if (cut.vec)
         launch_update<2>(kmeans_kb(nc), g, b, s, a);
     else
         launch_update<1>(kmeans_kb(nc), g, b, s, a);

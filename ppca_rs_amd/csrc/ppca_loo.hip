@@ -18,15 +18,12 @@
 // the mean (mix_loo_var_kernel).
 #include <algorithm>
 
-#include "ppca_device.hpp"
+#include "ppca_sweep.hpp"
 
 namespace ppca {
 namespace {
 
 constexpr int LOO_THREADS = 256;
-constexpr double LOG_2PI = 1.8378770664093454836;
-
-__host__ __device__ inline int loo_kq(int k) { return (k + 15) / 16 * 16; }
 
 struct LooArgs {
     const double *X;       // the chunk's rows (masks and values)
@@ -53,11 +50,11 @@ __device__ __forceinline__ double block_sum256(double v, double *red) {
     return s;
 }
 
-// One workgroup per row (grid-stride over the chunk), one thread per entry.  LDS: Sigma, padded to kq = 16 ceil(k / 16) columns
-// with zeros, z padded likewise, 4 doubles of reduction.
+// One workgroup per row (grid-stride over the chunk), one thread per entry.  LDS: Sigma, padded to kq = pad16(k) columns with zeros,
+// z padded likewise, 4 doubles of reduction.
 __global__ __launch_bounds__(LOO_THREADS) void loo_kernel(LooArgs a) {
     extern __shared__ double lds[];
-    const int k = a.k, d = a.d, kq = loo_kq(k), t = threadIdx.x;
+    const int k = a.k, d = a.d, kq = pad16(k), t = threadIdx.x;
     double *S = lds, *Z = lds + (size_t)k * kq, *red = Z + kq;
     const double sig2 = a.model[1];
     const double *C = a.model + 4;
@@ -74,7 +71,8 @@ __global__ __launch_bounds__(LOO_THREADS) void loo_kernel(LooArgs a) {
         double lsum = 0.0;
         for (int j = t; j < d; j += LOO_THREADS) {
             const double *cj = C + (int64_t)j * k;
-            // q = c_j^T Sigma c_j by blocks of 16 columns of Sigma (acc = c_j^T Sigma[:, b0:b0+16]); the padding columns are 0
+            // q = c_j^T Sigma c_j by blocks of 16 columns of Sigma (acc = c_j^T Sigma[:, b0:b0+16]); the padding columns are 0.
+            // (heldout_score_kernel has this loop without cn; shared, it changed both kernels' code: change the two together)
             double dot = 0.0, cn = 0.0, q = 0.0;
             for (int b0 = 0; b0 < k; b0 += 16) {
                 double acc[16];
@@ -200,7 +198,7 @@ unsigned elem_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 size_t loo_lds_bytes(int k) {
-    const int kq = loo_kq(k);
+    const int kq = pad16(k);
     return sizeof(double) * ((size_t)k * kq + kq + 4);
 }
 

@@ -6,31 +6,19 @@
 //          for the lower Cholesky factor L_i of M_i = C_o^T C_o + sigma^2 I)
 //     x_i  = C (z_i + U_i eps_i) + mean + sigma eta_i                       mode 0 (sample, ppca_model.rs:597-626)
 //     x_ij = the input where it is observed, the mode-0 value elsewhere     mode 1 (one draw of multiple imputation)
-// eps_i in R^k, eta_i in R^d are standard normals of the counter-based generator below, keyed by (seed, stream, g, index):
-// nothing depends on the grid, the chunking of the rows or the path that produced z_i and Sigma_i.  DESIGN.md section 4.9
-// states the generator; tests/test_gpu_posterior_sample.py restates it bit for bit.
+// eps_i in R^k, eta_i in R^d are standard normals of the counter-based generator of ppca_sweep.hpp (streams STREAM_EPS,
+// STREAM_ETA; the mixture's component: STREAM_CHOICE), keyed by (seed, stream, g, index): nothing depends on the grid, the chunking
+// of the rows or the path that produced z_i and Sigma_i.  DESIGN.md section 4.9 states the generator;
+// tests/test_gpu_posterior_sample.py restates it bit for bit.
 #include <algorithm>
 
-#include "ppca_device.hpp"
+#include "ppca_sweep.hpp"
 
 namespace ppca {
 namespace {
 
-constexpr uint64_t STREAM_EPS = 5, STREAM_ETA = 6, STREAM_CHOICE = 7;
-
-__device__ __forceinline__ uint64_t smix64(uint64_t x) {  // splitmix64's finaliser (the mix64 of the synthetic data)
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// once per row and stream
-__device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t stream, uint64_t grow) {
-    return smix64(smix64(seed ^ (stream * 0xD1342543DE82EF95ull)) + grow);
-}
-// word p of a row's stream: one finaliser per PAIR of normals
-__device__ __forceinline__ uint64_t row_word(uint64_t key, uint64_t p) { return smix64(key + p * 0xA0761D6478BD642Full); }
-// Box-Muller on both branches, fp32: u1 = (top 24 bits + 1) 2^-24 in (0, 1], u2 = (bits 16..39) 2^-24 in [0, 1)
+// Box-Muller on both branches of one word (one finaliser per PAIR of normals), fp32: u1 = (top 24 bits + 1) 2^-24 in (0, 1],
+// u2 = (bits 16..39) 2^-24 in [0, 1)
 __device__ __forceinline__ void normal_pair(uint64_t w, double &n0, double &n1) {
     const float u1 = (float)((w >> 40) + 1ull) * 5.9604644775390625e-08f;
     const float u2 = (float)((w >> 16) & 0xFFFFFFull) * 5.9604644775390625e-08f;
@@ -134,8 +122,7 @@ __global__ __launch_bounds__(64) void posterior_draw_kernel(DrawArgs a) {
 __global__ void mix_choose_kernel(const double *logpost, int64_t n, int nm, uint64_t seed, int64_t row_offset, int *choice) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint64_t w = row_word(row_key(seed, STREAM_CHOICE, (uint64_t)(row_offset + i)), 0);
-    const double u = ((double)(w >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    const double u = u01_open(row_word(row_key(seed, STREAM_CHOICE, (uint64_t)(row_offset + i)), 0));
     double cum = 0.0;
     int pick = -1, last = 0;
     for (int c = 0; c < nm; ++c) {

@@ -33,15 +33,13 @@
 // term is 0 * (0 - b_cj)), where scale_kernel's select form would ignore a non-finite offset on masked entries.
 #include <algorithm>
 
-#include "ppca_device.hpp"
+#include "ppca_sweep.hpp"
 
 namespace ppca {
 namespace {
 
 constexpr int SCALE_THREADS = 256;
 constexpr int SCALE_ROWS = 4;  // row steps a thread has in flight
-
-typedef double d2_t __attribute__((ext_vector_type(2)));
 
 struct ScaleArgs {
     const double *X;
@@ -56,52 +54,14 @@ struct ScaleArgs {
     int64_t rows_per_wg;
 };
 
-template <int VEC>
-struct Vec {
-    double v[VEC];
-};
-
-// NT: non-temporal access.  The sweep touches every byte once; measured at 4 M x 256 and 1 M x 1024 it is 2 % faster
-// with the output and 8-10 % faster in the sums-only form than plain loads and stores.
-template <int VEC, bool NT>
-__device__ __forceinline__ Vec<VEC> load_vec(const double *p) {
-    Vec<VEC> r;
-    if constexpr (VEC == 2) {
-        const d2_t t = NT ? __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(p)) : *reinterpret_cast<const d2_t *>(p);
-        r.v[0] = t.x;
-        r.v[1] = t.y;
-    } else {
-        r.v[0] = NT ? __builtin_nontemporal_load(p) : *p;
-    }
-    return r;
-}
-template <int VEC, bool NT>
-__device__ __forceinline__ void store_vec(double *p, const Vec<VEC> &r) {
-    if constexpr (VEC == 2) {
-        d2_t t;
-        t.x = r.v[0];
-        t.y = r.v[1];
-        if (NT)
-            __builtin_nontemporal_store(t, reinterpret_cast<d2_t *>(p));
-        else
-            *reinterpret_cast<d2_t *>(p) = t;
-    } else {
-        if (NT)
-            __builtin_nontemporal_store(r.v[0], p);
-        else
-            *p = r.v[0];
-    }
-}
-
 template <int VEC, bool ROWSUM>
 __global__ __launch_bounds__(SCALE_THREADS) void scale_kernel(ScaleArgs a) {
     __shared__ double red[SCALE_THREADS];
     __shared__ double rs[SCALE_ROWS][4];
     const int t = threadIdx.x, d = a.d;
-    const int tpr = 1 << a.tpr_log2, rps = SCALE_THREADS >> a.tpr_log2;
-    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
-    const int slots = (d + VEC - 1) / VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    int tpr, rps, tc, tr, slots;
+    int64_t r0, r1;
+    sweep_layout<SCALE_THREADS, VEC>(t, d, a.tpr_log2, a.rows_per_wg, a.n, tpr, rps, tc, tr, slots, r0, r1);
     double *part = a.part + (int64_t)blockIdx.x * 3 * d;
     const double qnan = __builtin_nan("");
     for (int c0 = 0; c0 < slots; c0 += tpr) {
@@ -212,8 +172,6 @@ __global__ __launch_bounds__(SCALE_THREADS) void fill_kernel(const double *X, in
     }
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---- the column sums of K weight vectors in one sweep
 constexpr int MULTI_KB_MAX = 8;  // components whose sums a thread holds at once (3 x VEC x KB doubles)
 
@@ -233,10 +191,9 @@ template <int VEC, int KB>
 __global__ __launch_bounds__(SCALE_THREADS) void moments_multi_kernel(MultiArgs a) {
     __shared__ double red[SCALE_THREADS];
     const int t = threadIdx.x, d = a.d;
-    const int tpr = 1 << a.tpr_log2, rps = SCALE_THREADS >> a.tpr_log2;
-    const int tc = t & (tpr - 1), tr = t >> a.tpr_log2;
-    const int slots = (d + VEC - 1) / VEC;
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = r0 + a.rows_per_wg < a.n ? r0 + a.rows_per_wg : a.n;
+    int tpr, rps, tc, tr, slots;
+    int64_t r0, r1;
+    sweep_layout<SCALE_THREADS, VEC>(t, d, a.tpr_log2, a.rows_per_wg, a.n, tpr, rps, tc, tr, slots, r0, r1);
     double *part = a.part + (int64_t)blockIdx.x * a.nc * 3 * d;
     const double qnan = __builtin_nan("");
     for (int c0 = 0; c0 < slots; c0 += tpr) {
@@ -344,13 +301,10 @@ int scale_grid(int64_t n, int d, int n_cu) {
 hipError_t launch_scale_columns(const double *X, int64_t ldx, const double *w, int64_t n, int d, const double *abl_dev, double *out,
                                 double *part, int grid, double *rowsum, hipStream_t s) {
     if (n <= 0 || grid <= 0) return hipSuccess;
-    const bool vec = d % 2 == 0 && ldx % 2 == 0 && aligned16(X) && (!out || aligned16(out));
-    const int slots = vec ? d / 2 : d;
-    int lg = 0;
-    while ((1 << lg) < slots && lg < 8) ++lg;
-    ScaleArgs a{X, ldx, n, d, w, abl_dev, out, part, rowsum, lg, (n + grid - 1) / grid};
+    const SweepCut cut = sweep_cut(d, ldx % 2 == 0, {X, out});
+    ScaleArgs a{X, ldx, n, d, w, abl_dev, out, part, rowsum, cut.tpr_log2, (n + grid - 1) / grid};
     const dim3 g((unsigned)grid), b(SCALE_THREADS);
-    if (vec) {
+    if (cut.vec) {
         if (rowsum)
             hipLaunchKernelGGL((scale_kernel<2, true>), g, b, 0, s, a);
         else
@@ -377,13 +331,10 @@ int moments_multi_grid(int64_t n, int nc, int n_cu) {
 hipError_t launch_column_moments_multi(const double *X, int64_t ldx, int64_t n, int d, const double *e_dev, int nc, const double *a_dev,
                                        const double *b_dev, double *part, int grid, hipStream_t s) {
     if (n <= 0 || grid <= 0 || nc <= 0) return hipSuccess;
-    const bool vec = d % 2 == 0 && ldx % 2 == 0 && aligned16(X);
-    const int slots = vec ? d / 2 : d;
-    int lg = 0;
-    while ((1 << lg) < slots && lg < 8) ++lg;
-    MultiArgs a{X, ldx, n, d, nc, e_dev, a_dev, b_dev, part, lg, (n + grid - 1) / grid};
+    const SweepCut cut = sweep_cut(d, ldx % 2 == 0, {X});
+    MultiArgs a{X, ldx, n, d, nc, e_dev, a_dev, b_dev, part, cut.tpr_log2, (n + grid - 1) / grid};
     const dim3 g((unsigned)grid), b(SCALE_THREADS);
-    if (vec)
+    if (cut.vec)
         launch_multi_vec<2>(multi_kb(nc), g, b, s, a);
     else
         launch_multi_vec<1>(multi_kb(nc), g, b, s, a);
@@ -393,7 +344,7 @@ hipError_t launch_column_moments_multi(const double *X, int64_t ldx, int64_t n, 
 hipError_t launch_fill_masked(const double *X, int64_t ldx, const double *F, int64_t ldf, int64_t n, int d, const double *a_dev,
                               double *out, int n_cu, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const bool vec = d % 2 == 0 && ldx % 2 == 0 && ldf % 2 == 0 && aligned16(X) && aligned16(F) && aligned16(out);
+    const bool vec = sweep_cut(d, ldx % 2 == 0 && ldf % 2 == 0, {X, F, out}).vec;
     const int64_t total = n * (vec ? d / 2 : d);
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(n_cu, 1) * 8, (total + SCALE_THREADS - 1) / SCALE_THREADS));
     if (vec)

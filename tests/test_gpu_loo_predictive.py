@@ -284,6 +284,32 @@ def test_grid_chunks_and_slices(P, monkeypatch, n, d, k):
     _close(part.llks(), bl[s0:s0 + ln], np.maximum(np.abs(bl[s0:s0 + ln]), 1.0), 1e-12)
 
 
+def test_outputs_do_not_depend_on_the_row_chunks(P, monkeypatch):
+    """PPCA_POST_CHUNK=64 at n = 150: three chunks of the posterior scratch, the last of 22 rows, against one chunk -- bit for bit.
+    The mixture with the variance takes both sweeps over its components (k = 2 and k = 3) in every chunk."""
+    n, d, k = 150, 13, 3
+    rng = np.random.default_rng(61)
+    x, w = _data(n, d, 62)
+    s, c, mu = _model(rng, d, k)
+    ds = P.Dataset(x, w)
+    m = P.PPCAModel(s, c, mu)
+    mix = P.PPCAMix([P.PPCAModel(0.8, 0.5 * rng.standard_normal((d, 2)), 0.3 * rng.standard_normal(d)), m], np.log([0.4, 0.6]))
+
+    def outputs():
+        got = []
+        for model in (m, mix):
+            r = model.loo_predictive(ds)
+            got += [r.mean().numpy(), r.variance().numpy(), r.llks()]
+        return got
+
+    base = outputs()
+    monkeypatch.setenv("PPCA_POST_CHUNK", "64")
+    chunked = outputs()
+    monkeypatch.delenv("PPCA_POST_CHUNK")
+    for name, a, b in zip(("mean", "variance", "llks", "mix mean", "mix variance", "mix llks"), chunked, base):
+        assert np.array_equal(a, b), (name, np.argwhere(a != b)[:8])
+
+
 # ------------------------------------------------------------------ 5. mixture
 def _pad(cs, kmax):
     return np.stack([np.concatenate([c_, np.zeros((c_.shape[0], kmax - c_.shape[1]))], axis=1) for c_ in cs])

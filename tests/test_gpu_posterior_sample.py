@@ -187,6 +187,30 @@ def test_draws_do_not_depend_on_grid_path_or_split(P, n, d, k):
             assert _rel(np.load(out), base) < 1e-9, env
 
 
+def test_draws_do_not_depend_on_the_row_chunks(P, monkeypatch):
+    """PPCA_POST_CHUNK=64 at n = 150: three chunks of the posterior scratch, the last of 22 rows, against one chunk -- bit for bit,
+    in both modes, under a row offset and for a mixture (components of k = 2 and k = 3, each drawing the rows that chose it)."""
+    n, d, k = 150, 13, 3
+    rng = np.random.default_rng(71)
+    x, w = _data(n, d, 72)
+    s, c, mu = _model(rng, d, k)
+    ds = P.Dataset(x, w)
+    m = P.PPCAModel(s, c, mu)
+    mix = P.PPCAMix([P.PPCAModel(0.8, 0.5 * rng.standard_normal((d, 2)), 0.3 * rng.standard_normal(d)), m], np.log([0.4, 0.6]))
+
+    def draws():
+        return {(name, keep, off): model.sample_posterior(ds, seed=99, keep_observed=keep, row_offset=off).numpy()
+                for name, model in (("model", m), ("mixture", mix)) for keep in (False, True) for off in (0, 1000)}
+
+    base = draws()
+    monkeypatch.setenv("PPCA_POST_CHUNK", "64")
+    chunked = draws()
+    monkeypatch.delenv("PPCA_POST_CHUNK")
+    assert not np.array_equal(base["model", False, 0], base["model", False, 1000])  # (the offset reaches the keys)
+    for case, a in chunked.items():
+        assert np.array_equal(a, base[case]), (case, np.argwhere(a != base[case])[:8])
+
+
 # ------------------------------------------------------------------ 3. the Gram guard's fallback
 def test_draws_of_a_guard_tripping_model(P, oracle):
     from ppca_rs_amd import _lib
