@@ -228,6 +228,11 @@ int ppca_posterior_sample(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model *mod
  * single-device rows. */
 int ppca_dataset_holdout(ppca_ctx *ctx, ppca_dataset *ds, double fraction, uint64_t seed, int64_t row_offset, ppca_dataset **train_out,
                          ppca_dataset **held_out, double *counts_host);
+/* The same split with the held entries those of lo <= u < hi (the same u): ppca_dataset_holdout(fraction) is the range (0, fraction),
+ * bit for bit.  Ranges that share their edges -- (f / K, (f + 1) / K) for f = 0 .. K - 1, the last edge exactly 1 -- are K disjoint
+ * folds that hold every observed entry exactly once.  Requires 0 <= lo <= hi <= 1; anything else, or NaN, is PPCA_ERR_INVALID. */
+int ppca_dataset_holdout_range(ppca_ctx *ctx, ppca_dataset *ds, double lo, double hi, uint64_t seed, int64_t row_offset,
+                               ppca_dataset **train_out, ppca_dataset **held_out, double *counts_host);
 /* The predictive log-density of held-out entries.  With (z, Sigma) the posterior of row i given its entries in
  * `train` (ppca_infer), every finite entry x of `held` in that row is scored as a NEW reading of column j:
  *   m = mean_j + c_j^T z,  v = sigma^2 + c_j^T Sigma c_j,  e = x - m,  l = -1/2 (ln 2 pi + ln v + e^2 / v)
@@ -424,6 +429,21 @@ int ppca_t_finalize_host(int32_t d, int32_t k, double sigma, const double *trans
  * One synchronisation of its own per call (uploads and downloads are queued behind the kernels). */
 int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_t k, double sigma, const double *transform, const double *mean,
                    double dof, double *sigma_out, double *transform_out, double *mean_out, double *llk_in, double *q_out);
+/* ppca_heldout_score under the t model.  The observed part of a row and one further entry are jointly t, so given the
+ * row's m train entries a held entry is univariate t with nu_m = nu + m degrees of freedom.  With (z, Sigma) the Gaussian posterior
+ * given `train` (ppca_infer) and delta the row's distance given `train` (above; m = 0: delta = 0, z = 0, Sigma = I, the t prior
+ * predictive):
+ *   loc = mean_j + c_j . z,  s = (sigma^2 + c_j^T Sigma c_j) (nu + delta) / nu_m,  e = x - loc
+ *   l   = tbl[m] - 1/2 ln s - 1/2 (nu_m + 1) log1p(e^2 / (nu_m s))
+ *   tbl[m] = ln Gamma((nu_m + 1) / 2) - ln Gamma(nu_m / 2) - 1/2 ln(nu_m pi)
+ * The fourth sum (e^2 / v) takes the variance v = s nu_m / (nu_m - 2); when nu_m <= 2 there is none and the entry adds 0 to it (it
+ * still counts everywhere else).  Outputs, weights and the reproducibility contract are ppca_heldout_score's; no N x d buffer is
+ * allocated.  Covers 1 <= k <= 16 and 1 <= d <= 1024.
+ * ppca_t_pred_table_host: host only, tbl_out[m] for m = 0 .. d (d + 1 doubles); as ppca_t_tables_host, the difference of the two
+ * ln Gamma is taken term by term of Stirling's series where the values themselves would cancel. */
+int ppca_t_pred_table_host(int32_t d, double dof, double *tbl_out);
+int ppca_t_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, const ppca_model *model, double dof,
+                         double *totals_host, double *col_sums_host, double *per_row);
 
 /* --------------------------------------------------- PPCA with a known precision per entry */
 /* An extension with no reference counterpart (weighted / heteroscedastic PCA: Bailey's EMPCA, Delchambre's weighted PCA):
@@ -469,6 +489,16 @@ int ppca_h_finalize_host(int32_t d, int32_t k, double sigma, const double *trans
  * (nullable): the log-likelihood of the INPUT model, sum_i w_i ell_i, a by-product of the sweep. */
 int ppca_h_em_step(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, int32_t d, int32_t k, double sigma, const double *transform,
                    const double *mean, double *sigma_out, double *transform_out, double *mean_out, double *llk_in);
+/* ppca_heldout_score under known precisions.  (z, Sigma) is the posterior of row i given its entries in `train` under
+ * the precisions `train_prec` (ppca_h_estep's; a row without an observed train entry has z = 0, Sigma = I).  Every entry of `held`
+ * that is observed under `held_prec` (x finite, q finite and > 0) is scored as a new reading of column j:
+ *   m = mean_j + c_j . z,  v = sigma^2 / q_ij + c_j^T Sigma c_j,  e = x - m,  l = -1/2 (ln 2 pi + ln v + e^2 / v)
+ * held_prec may be the handle train_prec (the usual case after ppca_dataset_holdout of x: whether an entry is observed follows x).  A
+ * held precision < 0 or = +inf at a finite x is PPCA_ERR_INVALID with no output written; bad train precisions are reported as
+ * ppca_h_estep reports them.  Outputs, weights and the reproducibility contract are ppca_heldout_score's (per_row depends on its row
+ * alone; PPCA_HELD_CHUNK forces a chunk length); no N x d buffer is allocated.  Covers 1 <= k <= 16 and 1 <= d <= 1024. */
+int ppca_h_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *train_prec, ppca_dataset *held, ppca_dataset *held_prec,
+                         const ppca_model *model, double *totals_host, double *col_sums_host, double *per_row);
 
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every

@@ -146,7 +146,11 @@ SIGNATURES = {
     "ppca_loo_predictive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, c_void_pp, c_double_p, C.c_void_p]),
     "ppca_mix_loo_predictive": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, c_void_pp, c_void_pp, c_double_p, C.c_void_p]),
     "ppca_dataset_holdout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_int64, c_void_pp, c_void_pp, C.c_void_p]),
+    "ppca_dataset_holdout_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint64, C.c_int64, c_void_pp, c_void_pp, C.c_void_p]),
     "ppca_heldout_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_t_pred_table_host": (C.c_int, [C.c_int32, C.c_double, C.c_void_p]),
+    "ppca_t_heldout_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_h_heldout_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppca_mix_heldout_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppca_dataset_scale_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_void_p]),
     "ppca_dataset_pairwise_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -137,17 +137,44 @@ class Dataset:
         seed=None draws a fresh seed.  train.holdout_counts = held.holdout_counts = (entries kept, entries held)."""
         if not 0.0 <= float(fraction) <= 1.0:  # (NaN fails both comparisons)
             raise ValueError("fraction must lie in [0, 1]")
+        return self._split(lib().ppca_dataset_holdout, (float(fraction),), seed, row_offset)
+
+    def _split(self, entry, what, seed: Optional[int], row_offset: int):
+        """The call of ppca_dataset_holdout / ppca_dataset_holdout_range (`what`: the fraction, or lo and hi) and its two datasets."""
         if row_offset < 0:
             raise ValueError("row_offset must be >= 0")
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1)[0])
         th, hh = C.c_void_p(), C.c_void_p()
         counts = np.zeros(2)
-        check(lib().ppca_dataset_holdout(self._ctx.handle, self._h, float(fraction), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset),
-                                         C.byref(th), C.byref(hh), ptr(counts)))
+        check(entry(self._ctx.handle, self._h, *what, int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), C.byref(th), C.byref(hh), ptr(counts)))
         train, held = Dataset._wrap(th, self._ctx), Dataset._wrap(hh, self._ctx)
         train.holdout_counts = held.holdout_counts = (int(counts[0]), int(counts[1]))
         return train, held
+
+    def holdout_range(self, lo: float, hi: float, seed: Optional[int] = None, *, row_offset: int = 0):
+        """`holdout` with the held entries those whose uniform u lies in [lo, hi) -- the same u, so holdout(f) is holdout_range(0, f)
+        bit for bit, and ranges that share their edges are disjoint folds (`kfold`).  Requires 0 <= lo <= hi <= 1."""
+        if not 0.0 <= float(lo) <= float(hi) <= 1.0:  # (NaN fails the comparisons)
+            raise ValueError("the range must satisfy 0 <= lo <= hi <= 1")
+        return self._split(lib().ppca_dataset_holdout_range, (float(lo), float(hi)), seed, row_offset)
+
+    @staticmethod
+    def fold_edges(n_folds: int):
+        """The n_folds + 1 edges f / n_folds of `kfold`, the last one exactly 1.0."""
+        n_folds = int(n_folds)
+        if n_folds < 2:
+            raise ValueError("n_folds must be >= 2")
+        return [f / n_folds for f in range(n_folds)] + [1.0]
+
+    def kfold(self, n_folds: int, seed: Optional[int] = None, *, row_offset: int = 0):
+        """The n_folds (train, held) pairs of entry-wise K-fold cross-validation: fold f holds the observed entries whose uniform lies
+        in [f / n_folds, (f + 1) / n_folds).  Neighbouring folds share an edge value and the last edge is exactly 1, so every observed
+        entry is held in exactly one fold.  One streaming pass per fold; seed=None draws one fresh seed for all of them."""
+        edges = Dataset.fold_edges(n_folds)
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        return [self.holdout_range(lo, hi, seed, row_offset=row_offset) for lo, hi in zip(edges, edges[1:])]
 
     def _fill_masked(self, fill: "Dataset", a) -> "Dataset":
         """ppca_dataset_fill_masked: this dataset's observed entries as they are, fill * a elsewhere."""
@@ -1057,7 +1084,8 @@ class HeldOutScore:
     mse, rmse   sum w e^2 / count and its root               mean_z2     sum w e^2 / v / count (about 1 when the intervals are calibrated)
     llks        per row, the sum of l over its held entries (0 for a row with none)
     columns     per column: count, llk, se (sum w e^2), z2 (sum w e^2 / v), rmse
-    Scores of disjoint shards add (`a + b`): sums field by field, llks concatenated."""
+    Scores of disjoint shards add (`a + b`): sums field by field, llks concatenated.  Scores of several folds of the same rows
+    (Dataset.kfold) pool (`HeldOutScore.pooled`): sums field by field, llks added row by row."""
 
     def __init__(self, col_sums: np.ndarray, n_entries: float, n_rows: float, llks: np.ndarray):
         self._cols = np.asarray(col_sums, dtype=np.float64).reshape(4, -1)
@@ -1101,6 +1129,22 @@ class HeldOutScore:
         return HeldOutScore(self._cols + other._cols, self.n_entries + other.n_entries, self.n_rows + other.n_rows,
                             np.concatenate([self._llks, other._llks]))
 
+    @staticmethod
+    def pooled(scores) -> "HeldOutScore":
+        """The scores of several folds of the SAME rows (Dataset.kfold) as one: column sums and entry counts added, llks added row by
+        row; n_rows adds too, so it counts (row, fold) pairs with a held entry.  `a + b` is for disjoint shards."""
+        scores = list(scores)
+        if not scores:
+            raise ValueError("no scores to pool")
+        first = scores[0]
+        if any(s._cols.shape != first._cols.shape or s._llks.shape != first._llks.shape for s in scores):
+            raise ValueError("the scores are of different shapes")
+        cols, llks = first._cols.copy(), first._llks.copy()
+        for s in scores[1:]:
+            cols += s._cols
+            llks += s._llks
+        return HeldOutScore(cols, sum(s.n_entries for s in scores), sum(s.n_rows for s in scores), llks)
+
     def __repr__(self) -> str:
         return f"HeldOutScore(n_entries={self.n_entries}, mean_llk={self.mean_llk:.6g}, rmse={self.rmse:.6g}, mean_z2={self.mean_z2:.4g})"
 
@@ -1124,14 +1168,62 @@ def _heldout_unwhiten(score: HeldOutScore, held: Dataset, noise: np.ndarray) -> 
     return HeldOutScore(cols, score.n_entries, score.n_rows, score._llks - jac)
 
 
-def _select_state_size(dataset: Dataset, state_sizes, fraction: float, seed: Optional[int], fit):
-    """One hold-out split, then per state size fit(train part, k) -> model and its score on the held part."""
-    train, held = dataset.holdout(fraction, seed)
+def heldout_score(model, train: Dataset, held: Dataset, precisions=None, held_precisions=None) -> HeldOutScore:
+    """The held-out score of a model of ANY family on one split, so that families are compared on identical held entries:
+    model.heldout_score(train, held) for PPCAModel, PPCAMix, FAModel and FAMix; TPPCAModel.score_heldout(train, held) (the t
+    predictive); HPPCAModel.score_heldout(train, held, precisions, held_precisions) (an entry at its own noise level).  `precisions`
+    are required for an HPPCAModel and refused for every other family."""
+    if isinstance(model, HPPCAModel):
+        if precisions is None:
+            raise ValueError("an HPPCAModel is scored under precisions")
+        return model.score_heldout(train, held, precisions, held_precisions)
+    if precisions is not None or held_precisions is not None:
+        raise ValueError(f"{type(model).__name__} takes no precisions")
+    return model.score_heldout(train, held) if isinstance(model, TPPCAModel) else model.heldout_score(train, held)
+
+
+def _select_state_size(dataset: Dataset, state_sizes, fraction: float, seed: Optional[int], fit, folds: int = 1, score=None):
+    """One hold-out split, then per state size fit(train part, k) -> model and its score on the held part (score(model, train, held);
+    default heldout_score(model, train, held)).  folds > 1: the split is dataset.kfold(folds, seed) instead (`fraction` is not used),
+    one fit per size and fold; the score is HeldOutScore.pooled over the folds and the third element the list of the folds' models."""
+    score = score or heldout_score
+    if int(folds) < 1:
+        raise ValueError("folds must be >= 1")
+    if int(folds) == 1:
+        train, held = dataset.holdout(fraction, seed)
+        out = []
+        for k in state_sizes:
+            model = fit(train, int(k))
+            out.append((int(k), score(model, train, held), model))
+        return out
+    parts = dataset.kfold(int(folds), seed)
     out = []
     for k in state_sizes:
-        model = fit(train, int(k))
-        out.append((int(k), model.heldout_score(train, held), model))
+        models = [fit(train, int(k)) for train, _ in parts]
+        out.append((int(k), HeldOutScore.pooled([score(m, train, held) for m, (train, held) in zip(models, parts)]), models))
     return out
+
+
+def cross_validate(dataset: Dataset, fit, *, folds: int = 5, seed: Optional[int] = None, precisions=None):
+    """K-fold entry-wise cross-validation of any model family on the folds of dataset.kfold(folds, seed): per fold
+    model = fit(train) -- fit(train, precisions) when `precisions` (a Dataset or an array of the dataset's shape) is given -- and
+    heldout_score(model, train, held[, precisions]).  Returns (the folds' scores, HeldOutScore.pooled of them, the folds' models).
+    The folds depend on (seed, shape) alone, so fits of different families with the same seed are compared on identical held
+    entries.  `fit` may return the model or a tuple that starts with it (HPPCATrainer.train's (model, metrics))."""
+    if precisions is not None and not isinstance(precisions, Dataset):
+        p = np.ascontiguousarray(precisions, dtype=np.float64)
+        if p.shape != (len(dataset), dataset._d):
+            raise ValueError(f"precisions have shape {p.shape} but the dataset is {len(dataset)} x {dataset._d}")
+        precisions = Dataset(p, ctx=dataset._ctx)
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1)[0])
+    scores, models = [], []
+    for train, held in dataset.kfold(folds, seed):
+        model = fit(train) if precisions is None else fit(train, precisions)
+        model = model[0] if isinstance(model, tuple) else model
+        scores.append(heldout_score(model, train, held, precisions))
+        models.append(model)
+    return scores, HeldOutScore.pooled(scores), models
 
 
 # --------------------------------------------------------------------------- trainers
@@ -1181,12 +1273,13 @@ class PPCATrainer:
 
 
     def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
-                          init: str = "random", prior: Optional[Prior] = None):
+                          init: str = "random", prior: Optional[Prior] = None, folds: int = 1):
         """Entry-wise cross-validation of the state size: one Dataset.holdout(fraction, seed), then for every size one `train` on the
         train part (quiet; model seed = `seed`) and one `heldout_score`.  Returns [(state_size, HeldOutScore, PPCAModel)]: choose the
-        size whose score.mean_llk is largest."""
+        size whose score.mean_llk is largest.  folds > 1: the split is Dataset.kfold(folds, seed) instead (`fraction` is not used),
+        one fit per size and fold; the score is the pooled one and the third element the list of the folds' models."""
         return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: PPCATrainer(tr).train(
-            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init, prior=prior))
+            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init, prior=prior), folds)
 
 
 # --------------------------------------------------------------------------- own npz containers (FAModel, TPPCAModel, FAMix)
@@ -1419,13 +1512,13 @@ class FATrainer:
 
 
     def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
-                          init: str = "random", prior: Optional[Prior] = None):
+                          init: str = "random", prior: Optional[Prior] = None, folds: int = 1):
         """PPCATrainer.select_state_size with FAModel fits: [(state_size, HeldOutScore, FAModel)].  FAModel has no MAP step:
         `prior` must be None."""
         if prior is not None:
             raise ValueError("FATrainer takes no prior")
         return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: FATrainer(tr).train(
-            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init))
+            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init), folds)
 
 
 # --------------------------------------------------------------------------- Student-t PPCA (robust to outlying rows)
@@ -1597,6 +1690,17 @@ class TPPCAModel:
         """Observed values kept, masked ones replaced by C z + mean (gaussian().extrapolate)."""
         return self._base.extrapolate(dataset)
 
+    def score_heldout(self, train: Dataset, held: Dataset) -> "HeldOutScore":
+        """PPCAModel.heldout_score under the t model (module function `heldout_score` calls it for this family): given the m entries of a row in `train`, a held entry is a univariate t with
+        dof + m degrees of freedom around mean_j + c_j . z, of scale (sigma^2 + c_j^T Sigma c_j) (dof + delta) / (dof + m) -- an
+        outlying row (large delta) widens its own predictive.  z2 takes the variance scale (dof + m) / (dof + m - 2); where
+        dof + m <= 2 there is none and the entry adds 0 to it.  One pass on the GPU; nothing of size N x d is allocated."""
+        if train._d != self.output_size:
+            raise ValueError(f"dataset has {train._d} dimensions but the model has output size {self.output_size}")
+        ctx = train._ctx
+        return _heldout_call(train, held, lambda t, c, r: lib().ppca_t_heldout_score(ctx.handle, train._h, held._h,
+                                                                                     self._base._device(ctx).h, self._dof, t, c, r))
+
     def _iterate(self, dataset: Dataset, estimate_dof: bool, want_llk: bool):
         ctx = dataset._ctx
         if len(dataset) == 0:
@@ -1660,6 +1764,13 @@ class TPPCATrainer:
                            lambda m: m.iterate(ds, estimate_dof),
                            # (a dof about to be estimated for the first time counts as a parameter already)
                            n_parameters=lambda m: m.n_parameters + (1 if estimate_dof and not m._estimated else 0))
+
+    def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
+                          init: str = "random", dof: float = 4.0, estimate_dof: bool = False, folds: int = 1):
+        """PPCATrainer.select_state_size with TPPCAModel fits at `dof` degrees of freedom (estimated from there with estimate_dof),
+        scored by the t predictive: [(state_size, HeldOutScore, TPPCAModel)]."""
+        return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: TPPCATrainer(tr).train(
+            state_size=k, dof=dof, estimate_dof=estimate_dof, n_iters=n_iters, quiet=True, seed=seed, init=init), folds)
 
 
 # --------------------------------------------------------------------------- PPCA with a known precision per entry
@@ -1809,6 +1920,19 @@ class HPPCAModel:
         """Observed values kept (observed: finite value, finite precision > 0), the others replaced by C z + mean."""
         return self._recon(dataset, precisions, 1)
 
+    def score_heldout(self, train: Dataset, held: Dataset, precisions, held_precisions=None) -> "HeldOutScore":
+        """PPCAModel.heldout_score under known precisions (module function `heldout_score` calls it for this family): the posterior of a row from its entries in `train` under `precisions`,
+        then every entry of `held` that is observed under `held_precisions` (default: `precisions` -- after a split of the values the
+        precisions of both parts are the same array) scored at its own noise level, v = sigma^2 / q + c_j^T Sigma c_j.  A negative or
+        +inf precision raises PPCAError.  One pass on the GPU; nothing of size N x d is allocated."""
+        if len(train) != len(held) or train._d != held._d:
+            raise ValueError("the train part and the held part differ in shape")
+        prec = self._pair(train, precisions)
+        hprec = prec if held_precisions is None else self._pair(held, held_precisions)
+        ctx = train._ctx
+        return _heldout_call(train, held, lambda t, c, r: lib().ppca_h_heldout_score(ctx.handle, train._h, prec._h, held._h, hprec._h,
+                                                                                     self._base._device(ctx).h, t, c, r))
+
     def _iterate(self, dataset: Dataset, precisions, want_llk: bool):
         if len(dataset) == 0:
             raise ValueError("dataset is empty")
@@ -1867,6 +1991,21 @@ class HPPCATrainer:
                 print(f"Masked H-PPCA iteration {idx + 1}: {metric}={getattr(metrics[-1], metric)}")
             model = new_model
         return model.to_canonical(), metrics
+
+    def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
+                          init: str = "random", folds: int = 1):
+        """PPCATrainer.select_state_size with HPPCAModel fits under this trainer's precisions, which also are the held entries'
+        (the split follows the values): [(state_size, HeldOutScore, HPPCAModel)]."""
+        ds = self.dataset
+        prec = self.precisions
+        if not isinstance(prec, Dataset):
+            p = np.ascontiguousarray(prec, dtype=np.float64)
+            if p.shape != (len(ds), ds._d):
+                raise ValueError(f"precisions have shape {p.shape} but the dataset is {len(ds)} x {ds._d}")
+            prec = Dataset(p, ctx=ds._ctx)  # (uploaded once)
+        return _select_state_size(ds, state_sizes, fraction, seed, lambda tr, k: HPPCATrainer(tr, prec).train(
+            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init)[0], folds,
+            score=lambda model, train, held: model.score_heldout(train, held, prec))
 
 
 # --------------------------------------------------------------------------- mixture

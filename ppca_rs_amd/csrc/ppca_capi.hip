@@ -1506,8 +1506,14 @@ extern "C" int ppca_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, const ppca_m
 // ------------------------------------------------------------------ held-out scoring
 extern "C" int ppca_dataset_holdout(ppca_ctx *ctx, ppca_dataset *ds, double fraction, uint64_t seed, int64_t row_offset,
                                     ppca_dataset **train_out, ppca_dataset **held_out, double *counts_host) {
-    if (!ctx || !ds || !train_out || !held_out) return fail(PPCA_ERR_INVALID, "null argument");
     if (!(fraction >= 0.0 && fraction <= 1.0)) return fail(PPCA_ERR_INVALID, "fraction must lie in [0, 1]");
+    return ppca_dataset_holdout_range(ctx, ds, 0.0, fraction, seed, row_offset, train_out, held_out, counts_host);
+}
+
+extern "C" int ppca_dataset_holdout_range(ppca_ctx *ctx, ppca_dataset *ds, double lo, double hi, uint64_t seed, int64_t row_offset,
+                                          ppca_dataset **train_out, ppca_dataset **held_out, double *counts_host) {
+    if (!ctx || !ds || !train_out || !held_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (!(lo >= 0.0 && lo <= hi && hi <= 1.0)) return fail(PPCA_ERR_INVALID, "the range must satisfy 0 <= lo <= hi <= 1");
     if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
     if (int rc = check_same_device(ds, ctx)) return rc;
     USE_CTX(ctx);
@@ -1521,7 +1527,7 @@ extern "C" int ppca_dataset_holdout(ppca_ctx *ctx, ppca_dataset *ds, double frac
         Partials part;
         const int grid = holdout_grid(n, d, ctx->n_cu);
         if (int rc = part.alloc(grid, 2)) return rc;
-        HIP_TRY(launch_holdout(ds->X, ds->d, n, d, fraction, seed, row_offset, static_cast<double *>(tr->xbuf->p),
+        HIP_TRY(launch_holdout(ds->X, ds->d, n, d, lo, hi, seed, row_offset, static_cast<double *>(tr->xbuf->p),
                                static_cast<double *>(he->xbuf->p), part.p, grid, ctx->stream));
         if (counts_host) {
             HIP_TRY(part.reduce(ctx->stream));
@@ -1564,11 +1570,19 @@ static void held_totals(const double *sums, int d, double *totals) {
 
 // The end of a held-out pass over n rows (n = 0: zeros, nothing is read): the reduced sums (red: 4 d column sums | 2 counts) and the
 // rows' scores (rowv; per_row nullable, a host or device destination as ppca_llk's per-sample output) come down, then held_totals.
+// prec: red has a third count behind the two, the held precisions that are negative or +inf at a finite x; when it is not 0 the call
+// fails with no output written (so the rows' scores leave only once the sums are here).
 static int held_finish(ppca_ctx *ctx, int64_t n, int d, const double *red, const double *rowv, double *totals_host,
-                       double *col_sums_host, double *per_row) {
-    std::vector<double> sums((size_t)4 * d + 2, 0.0);
+                       double *col_sums_host, double *per_row, bool prec = false) {
+    std::vector<double> sums((size_t)4 * d + (prec ? 3 : 2), 0.0);
     if (n > 0) {
         HIP_TRY(hipMemcpyAsync(sums.data(), red, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+        if (prec) {
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            if (sums.back() > 0.0)
+                return fail(PPCA_ERR_INVALID, "%.0f held precisions are negative or +inf at a finite value (a precision is > 0 and finite; "
+                            "0 or NaN marks an entry as not observed)", sums.back());
+        }
         if (per_row) HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDefault, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
@@ -3289,6 +3303,55 @@ extern "C" int ppca_t_em_step(ppca_ctx *ctx, ppca_dataset *ds, int32_t d, int32_
     return PPCA_OK;
 }
 
+// The predictive t of a held entry: tbl[m] = ln Gamma((nu_m + 1) / 2) - ln Gamma(nu_m / 2) - 1/2 ln(nu_m pi),
+// nu_m = nu + m -- t_log_norm at a = nu_m / 2, h = 1/2, so from nu_m >= 2e4 on the difference is taken term by term.
+extern "C" int ppca_t_pred_table_host(int32_t d, double dof, double *tbl_out) {
+    if (d < 0 || !tbl_out) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_dof(dof)) return rc;
+    for (int m = 0; m <= d; ++m) tbl_out[m] = t_log_norm(0.5 * (dof + m), 0.5);
+    return PPCA_OK;
+}
+
+// ppca_heldout_score with the t predictive: the Gaussian posterior of a chunk of train rows (the loop of ppca_heldout_score), then the
+// t arm of the scoring kernel, which takes the row's m and delta from the train rows itself.
+extern "C" int ppca_t_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *held, const ppca_model *model, double dof,
+                                    double *totals_host, double *col_sums_host, double *per_row) {
+    if (!ctx || !totals_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_held_pair(train, held)) return rc;
+    if (int rc = t_check(train, model, dof)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = train->n;
+    const int d = train->d, k = model->k;
+    PostChunks pc;
+    BufRef pr, tb;
+    Partials part;
+    double *rowv = nullptr;
+    std::vector<double> tbl((size_t)d + 1);  // (read by the upload until held_finish's synchronisation)
+    StreamGuard guard{ctx->stream};
+    if (n > 0) {
+        if (int rc = ppca_t_pred_table_host(d, dof, tbl.data())) return rc;
+        if (int rc = dev_alloc(sizeof(double) * tbl.size(), &tb)) return rc;
+        HIP_TRY(hipMemcpyAsync(tb->p, tbl.data(), sizeof(double) * tbl.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = pc.alloc(n, held_chunk_rows(n, d, k, 0), k)) return rc;
+        if (int rc = part.alloc(heldout_family_grid((int64_t)pc.rows, ctx->n_cu), heldout_family_part_len(d, false))) return rc;
+        if (per_row) {
+            if (int rc = dev_alloc(sizeof(double) * (size_t)n, &pr)) return rc;
+            rowv = static_cast<double *>(pr->p);
+        }
+        if (int rc = pc.each(train, [&](ppca_dataset &tp, int64_t r0) -> int {
+                ppca_dataset hp = row_slice(held, r0, pc.chunk);
+                if (int rc = run_post(ctx, &tp, model, nullptr, pc.states, pc.covs, nullptr, 0, nullptr)) return rc;
+                const int g = heldout_family_grid(tp.n, ctx->n_cu);  // (<= part.grid: the last chunk may be shorter)
+                HIP_TRY(launch_heldout_score_t(hp.X, hp.d, tp.X, tp.d, tp.w, d, k, tp.n, model->p(), pc.states, pc.covs,
+                                               static_cast<const double *>(tb->p), dof, rowv ? rowv + r0 : nullptr, part.p, g, ctx->stream));
+                HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+                return PPCA_OK;
+            }))
+            return rc;
+    }
+    return held_finish(ctx, n, d, part.red, rowv, totals_host, col_sums_host, per_row);
+}
+
 // ------------------------------------------------------------------ heteroscedastic PPCA
 static int check_h_covers(int d, int k) {  // k: the caller's state size (0 is not covered)
     if (hetero_covers(d, k)) return PPCA_OK;
@@ -3480,4 +3543,54 @@ extern "C" int ppca_h_em_step(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *pre
     if (int rc = ppca_h_finalize_host(d, k, sigma, transform, mean, sw.res.data(), sigma_out, transform_out, mean_out)) return rc;
     if (llk_in) *llk_in = sw.res[(size_t)sw.slen + 1];
     return PPCA_OK;
+}
+
+// ppca_heldout_score with a known precision per entry: per chunk of rows the E-step sweep of ppca_h_estep on
+// (train, train_prec) into the posterior scratch, then the known-precision arm of the scoring kernel on (held, held_prec).  Bad train
+// precisions are the sweep's count, bad held precisions the scoring kernel's: either fails the call with no output written.
+extern "C" int ppca_h_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *train_prec, ppca_dataset *held, ppca_dataset *held_prec,
+                                    const ppca_model *model, double *totals_host, double *col_sums_host, double *per_row) {
+    if (!ctx || !totals_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = check_held_pair(train, held)) return rc;
+    if (int rc = h_check(train, train_prec, model)) return rc;
+    if (int rc = h_check(held, held_prec, model)) return rc;
+    USE_CTX(ctx);
+    const int64_t n = train->n;
+    const int d = train->d, k = model->k;
+    PostChunks pc;
+    BufRef pr, tabb;
+    Partials part, scal;
+    double *rowv = nullptr;
+    if (n > 0) {
+        StreamGuard guard{ctx->stream};
+        if (int rc = dev_alloc(sizeof(double) * (size_t)d * hetero_ntp(k), &tabb)) return rc;
+        double *tab = static_cast<double *>(tabb->p);
+        HIP_TRY(launch_hetero_table(model->p(), d, k, tab, ctx->stream));
+        if (int rc = pc.alloc(n, held_chunk_rows(n, d, k, 0), k)) return rc;
+        if (int rc = scal.alloc(hetero_sweep_grid((int64_t)pc.rows, ctx->n_cu), 4)) return rc;
+        if (int rc = part.alloc(heldout_family_grid((int64_t)pc.rows, ctx->n_cu), heldout_family_part_len(d, true))) return rc;
+        if (per_row) {
+            if (int rc = dev_alloc(sizeof(double) * (size_t)n, &pr)) return rc;
+            rowv = static_cast<double *>(pr->p);
+        }
+        if (int rc = pc.each(train, [&](ppca_dataset &tp, int64_t r0) -> int {
+                const double *P = train_prec->X + r0 * d, *H = held->X + r0 * d, *Q = held_prec->X + r0 * d;
+                const int gs = hetero_sweep_grid(tp.n, ctx->n_cu);
+                HIP_TRY(launch_hetero_sweep(tp.X, d, P, d, tp.w, tp.n, d, k, model->p(), tab, nullptr, pc.states, pc.covs, nullptr, scal.p,
+                                            gs, ctx->stream));
+                HIP_TRY(scal.reduce(ctx->stream, r0 > 0, gs));
+                const int g = heldout_family_grid(tp.n, ctx->n_cu);  // (<= part.grid: the last chunk may be shorter)
+                HIP_TRY(launch_heldout_score_prec(H, d, Q, d, tp.w, d, k, tp.n, model->p(), pc.states, pc.covs, rowv ? rowv + r0 : nullptr,
+                                                  part.p, g, ctx->stream));
+                HIP_TRY(part.reduce(ctx->stream, r0 > 0, g));
+                return PPCA_OK;
+            }))
+            return rc;
+        HSweep sw;  // (the train side's count, reported as ppca_h_estep reports it)
+        sw.res.assign(4, 0.0);
+        HIP_TRY(hipMemcpyAsync(sw.res.data(), scal.red, sizeof(double) * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (sw.bad() > 0.0) return h_bad_precisions(sw);
+    }
+    return held_finish(ctx, n, d, part.red, rowv, totals_host, col_sums_host, per_row, true);
 }

@@ -2,7 +2,8 @@
 //
 //   holdout_kernel   one sweep over an N x d dataset (row stride ldx): one read, two writes.  Entry (i, j) of global row
 //                    g = row_offset + i draws u = (row_word(row_key(seed, 8, g), j) >> 11) 2^-53 from the counter-based generator of
-//                    ppca_sweep.hpp (u01_floor, STREAM_HOLDOUT); an observed (finite) entry is HELD iff u < fraction:
+//                    ppca_sweep.hpp (u01_floor, STREAM_HOLDOUT); an observed (finite) entry is HELD iff lo <= u < hi (a fraction f is
+//                    the range [0, f); the K folds are the ranges between neighbouring edges f / K):
 //                      held:   train = NaN, held = x (the bits as they are)        kept:   train = x, held = NaN
 //                      masked (any non-finite value): NaN in both
 //                    part[workgroup][2] = the workgroup's [kept, held] entry counts (integers, as doubles).  Nothing depends on the
@@ -20,6 +21,16 @@
 //                    w e^2 / v] and [entries | rows with an entry] accumulate in LDS over the workgroup's rows in row order (a column is
 //                    listed once per row, one lane owns it: no atomics) and leave as part[workgroup][4 d + 2].  The mixture runs the
 //                    same kernel once per component in a form that folds (m, v, l) into per-entry state, then a form that sums it.
+//                    Two further density arms of the one-model form, for k <= 16 and d <= 1024:
+//                      known precisions   the wave also reads the row of the held precisions q; an entry is listed iff x is finite
+//                                         and q is finite and > 0, with q as the list's third array; v = sigma^2 / q + c_j^T Sigma c_j.
+//                                         A q < 0 or +inf at a finite x is counted (part[4 d + 2]) and not listed.
+//                      Student-t          a prologue reads the row of `train` 64 columns at a time: m = its finite entries (ballot),
+//                                         |r|^2 = sum (x - mean_j - c_j^T z)^2 with the z in LDS (per lane in column order, then a
+//                                         butterfly), delta = (|r|^2 + sigma^2 |z|^2) / sigma^2.  With nu_m = nu + m:
+//                                         s = (sigma^2 + c_j^T Sigma c_j) (nu + delta) / nu_m,
+//                                         l = tbl[m] - 1/2 ln s - 1/2 (nu_m + 1) log1p(e^2 / (nu_m s)), and the z^2 sum takes
+//                                         e^2 / (s nu_m / (nu_m - 2)), 0 when nu_m <= 2 (no variance).
 #include <algorithm>
 
 #include "ppca_sweep.hpp"
@@ -34,7 +45,7 @@ struct HoldArgs {
     const double *X;
     int64_t ldx, n;
     int d;
-    double fraction;
+    double lo, hi;  // held: lo <= u < hi
     uint64_t seed;
     int64_t row_offset;
     double *train, *held;  // n x d each (row stride d)
@@ -79,7 +90,7 @@ __global__ __launch_bounds__(HOLD_THREADS) void holdout_kernel(HoldArgs a) {
                     const double xv = x[u].v[v];
                     const bool obs = __builtin_isfinite(xv);
                     const double uu = u01_floor(row_word(key, (uint64_t)(j + v)));
-                    const bool hold = obs && uu < a.fraction;
+                    const bool hold = obs && uu >= a.lo && uu < a.hi;
                     tv.v[v] = (obs && !hold) ? xv : qnan;
                     hv.v[v] = hold ? xv : qnan;
                     kept += (obs && !hold) ? 1u : 0u;
@@ -128,9 +139,18 @@ struct HeldArgs {
     const double *logpost;
     int comp, nm, first;
     double *mx, *sm, *fa, *fv, *fq;
+    // the family arms (HELD_MODEL only).  HELD_PREC: the chunk's rows of the held precisions.  HELD_T: the chunk's rows of `train`,
+    // tbl[0 .. d] (ppca_t_pred_table_host) and the degrees of freedom
+    const double *Q;
+    int64_t ldq;
+    const double *T;
+    int64_t ldt;
+    const double *tbl;
+    double dof;
 };
 
 enum { HELD_MODEL = 0, HELD_FOLD = 1, HELD_FINISH = 2 };
+enum { HELD_GAUSS = 0, HELD_PREC = 1, HELD_T = 2 };  // the density of a held entry (the mixture forms are Gaussian)
 
 // MODE HELD_MODEL: the score of one model.  HELD_FOLD: the same per-entry (m, v, l) of mixture component a.comp, folded into the
 // per-entry state instead of summed (the first component initialises it; a component of weight 0 contributes nothing).
@@ -140,18 +160,24 @@ enum { HELD_MODEL = 0, HELD_FOLD = 1, HELD_FINISH = 2 };
 // columns (HELD_LIST ints) | when they fit 64 KiB with the rest (sums_in_lds): the column sums (4 d), l of the row's columns (d).
 // Otherwise those 5 d doubles are the workgroup's own partial in global memory, [sums (4 d) | 2 counts | l slots (d, back at 0 when
 // the kernel ends)], read and written by this wave alone with a barrier between a write and the next read of a slot.
-template <int MODE>
+// FAM (HELD_MODEL only) HELD_PREC: the list has a third array, the entries' precisions, behind its values, and the partial one more
+// count, [sums (4 d) | 2 counts | bad precisions].  HELD_PREC and HELD_T cover k <= 16 and d <= 1024, where the sums always fit in
+// LDS (under 46 KiB in all): their instantiations take that branch at compile time and the global-partial one does not exist in them.
+template <int MODE, int FAM = HELD_GAUSS>
 __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
+    static_assert(FAM == HELD_GAUSS || MODE == HELD_MODEL, "the family arms are forms of the one-model score");
     extern __shared__ double lds[];
     const int k = a.k, d = a.d, kq = pad16(k), lane = threadIdx.x;
+    const bool in_lds = FAM != HELD_GAUSS ? true : a.sums_in_lds != 0;
     double *S = lds, *Z = S + (size_t)k * kq, *lx = Z + kq;
-    int *lj = reinterpret_cast<int *>(lx + HELD_LIST);
+    double *lq = lx + HELD_LIST;  // (HELD_PREC)
+    int *lj = reinterpret_cast<int *>(lx + (FAM == HELD_PREC ? 2 : 1) * HELD_LIST);
     double *part = nullptr, *cs = nullptr, *L = nullptr;
-    double n_entries = 0.0, n_rows_held = 0.0;  // (lane 0's are the workgroup's)
+    double n_entries = 0.0, n_rows_held = 0.0, n_bad = 0.0;  // (lane 0's are the workgroup's)
     if constexpr (MODE != HELD_FOLD) {
-        part = a.part + (int64_t)blockIdx.x * ((int64_t)(a.sums_in_lds ? 4 : 5) * d + 2);
-        cs = a.sums_in_lds ? lx + HELD_LIST + HELD_LIST / 2 : part;
-        L = a.sums_in_lds ? cs + (size_t)4 * d : part + (size_t)4 * d + 2;
+        part = a.part + (int64_t)blockIdx.x * ((int64_t)(in_lds ? 4 : 5) * d + (FAM == HELD_PREC ? 3 : 2));
+        cs = in_lds ? reinterpret_cast<double *>(lj) + HELD_LIST / 2 : part;
+        L = in_lds ? cs + (size_t)4 * d : part + (size_t)4 * d + 2;
         for (int e = lane; e < 4 * d; e += 64) cs[e] = 0.0;
         for (int e = lane; e < d; e += 64) L[e] = 0.0;
         __syncthreads();
@@ -173,16 +199,49 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
         const double *h = a.H + r * a.ldh;
         int cnt = 0, row_cnt = 0;  // (wave-uniform)
         __syncthreads();
+        double t_num = 0.0, t_scale = 1.0, t_norm = 0.0;  // HELD_T (wave-uniform): nu_m, (nu + delta) / nu_m, tbl[m]
+        if constexpr (FAM == HELD_T) {
+            const double *tr = a.T + r * a.ldt;
+            int m = 0;
+            double rr = 0.0;
+            for (int j0 = 0; j0 < d; j0 += 64) {
+                const int j = j0 + lane;
+                const double xv = j < d ? __builtin_nontemporal_load(tr + j) : __builtin_nan("");
+                const bool fin = __builtin_isfinite(xv);
+                m += __popcll(__ballot(fin));
+                if (fin) {
+                    const double *cj = C + (int64_t)j * k;
+                    double dot = 0.0;
+                    for (int i = 0; i < k; ++i) dot = fma(cj[i], Z[i], dot);
+                    const double res = (xv - mu[j]) - dot;
+                    rr = fma(res, res, rr);
+                }
+            }
+            for (int off = 32; off > 0; off >>= 1) rr += __shfl_xor(rr, off, 64);  // (the same sum on every lane)
+            double zz = 0.0;
+            for (int i = 0; i < k; ++i) zz = fma(Z[i], Z[i], zz);
+            const double delta = fma(sig2, zz, rr) / sig2;
+            t_num = a.dof + (double)m;
+            t_scale = (a.dof + delta) / t_num;
+            t_norm = a.tbl[m];
+        }
         for (int j0 = 0; j0 < d || cnt > 0; j0 += 64) {
             if (j0 < d) {
                 const int j = j0 + lane;
                 const double xv = j < d ? __builtin_nontemporal_load(h + j) : __builtin_nan("");
-                const bool fin = __builtin_isfinite(xv);
+                bool fin = __builtin_isfinite(xv);
+                double qv = 1.0;
+                if constexpr (FAM == HELD_PREC) {
+                    qv = j < d ? __builtin_nontemporal_load(a.Q + r * a.ldq + j) : 0.0;
+                    n_bad += (double)__popcll(__ballot(fin && (qv < 0.0 || qv == __builtin_inf())));
+                    fin = fin && qv > 0.0 && qv < __builtin_inf();  // (NaN or 0: not observed)
+                }
                 const unsigned long long bal = __ballot(fin);
                 if (fin) {
                     const int at = cnt + __popcll(bal & ((1ull << lane) - 1ull));
                     lx[at] = xv;
                     lj[at] = j;
+                    if constexpr (FAM == HELD_PREC) lq[at] = qv;
                 }
                 cnt += __popcll(bal);
                 row_cnt += __popcll(bal);
@@ -217,9 +276,14 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
                             if (b0 + b < k) q = fma(acc[b], cj[b0 + b], q);
                     }
                     const double m = mu[j] + dot, e = xv - m;
-                    v = sig2 + q;
                     e2 = __dmul_rn(e, e);
-                    l = -0.5 * (LOG_2PI + log(v) + e2 / v);
+                    if constexpr (FAM == HELD_T) {
+                        v = (sig2 + q) * t_scale;  // the scale s of the predictive t
+                        l = t_norm - 0.5 * log(v) - 0.5 * (t_num + 1.0) * log1p(e2 / (t_num * v));
+                    } else {
+                        v = (FAM == HELD_PREC ? sig2 / lq[lane] : sig2) + q;
+                        l = -0.5 * (LOG_2PI + log(v) + e2 / v);
+                    }
                     if constexpr (MODE == HELD_FOLD) {
                         double M = a.first ? -INFINITY : a.mx[o], Sm = a.first ? 0.0 : a.sm[o];
                         double A = a.first ? 0.0 : a.fa[o], V = a.first ? 0.0 : a.fv[o], Q = a.first ? 0.0 : a.fq[o];
@@ -250,7 +314,8 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
                     l = a.mx[o] + log(a.sm[o]);
                 }
                 if constexpr (MODE != HELD_FOLD) {
-                    const double z2 = e2 / v;
+                    // (HELD_T: over the variance s nu_m / (nu_m - 2); none when nu_m <= 2, and the entry adds 0)
+                    const double z2 = FAM == HELD_T ? (t_num > 2.0 ? e2 / (v * (t_num / (t_num - 2.0))) : 0.0) : e2 / v;
                     L[j] = l;
                     cs[j] += wr;
                     cs[d + j] = fma(wr, l, cs[d + j]);
@@ -261,16 +326,18 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
             __syncthreads();
             // what is left of the list moves to its front
             const int rest = cnt - take;
-            double mvx = 0.0;
+            double mvx = 0.0, mvq = 0.0;
             int mvj = 0;
             if (lane < rest) {
                 mvx = lx[take + lane];
                 mvj = lj[take + lane];
+                if constexpr (FAM == HELD_PREC) mvq = lq[take + lane];
             }
             __syncthreads();
             if (lane < rest) {
                 lx[lane] = mvx;
                 lj[lane] = mvj;
+                if constexpr (FAM == HELD_PREC) lq[lane] = mvq;
             }
             cnt = rest;
             __syncthreads();
@@ -292,11 +359,12 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
         __syncthreads();  // S, Z and L are the next row's
     }
     if constexpr (MODE != HELD_FOLD) {
-        if (a.sums_in_lds)
+        if (in_lds)
             for (int e = lane; e < 4 * d; e += 64) part[e] = cs[e];
         if (lane == 0) {
             part[4 * d] = n_entries;
             part[4 * d + 1] = n_rows_held;
+            if constexpr (FAM == HELD_PREC) part[4 * d + 2] = n_bad;
         }
     }
 }
@@ -305,11 +373,11 @@ __global__ __launch_bounds__(64) void heldout_score_kernel(HeldArgs a) {
 
 int holdout_grid(int64_t n, int d, int n_cu) { return scale_grid(n, d, n_cu); }
 
-hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double fraction, uint64_t seed, int64_t row_offset,
+hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double lo, double hi, uint64_t seed, int64_t row_offset,
                           double *train, double *held, double *part, int grid, hipStream_t s) {
     if (n <= 0 || grid <= 0) return hipSuccess;
     const SweepCut cut = sweep_cut(d, ldx % 2 == 0, {X, train, held});
-    HoldArgs a{X, ldx, n, d, fraction, seed, row_offset, train, held, part, cut.tpr_log2, (n + grid - 1) / grid};
+    HoldArgs a{X, ldx, n, d, lo, hi, seed, row_offset, train, held, part, cut.tpr_log2, (n + grid - 1) / grid};
     if (cut.vec)
         hipLaunchKernelGGL(holdout_kernel<2>, dim3((unsigned)grid), dim3(HOLD_THREADS), 0, s, a);
     else
@@ -317,9 +385,9 @@ hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double
     return hipGetLastError();
 }
 
-static size_t held_lds_base(int k) {
+static size_t held_lds_base(int k, int lists = 1) {  // lists: the list's arrays of doubles (values; HELD_PREC: and precisions)
     const int kq = pad16(k);
-    return sizeof(double) * ((size_t)k * kq + kq + HELD_LIST) + sizeof(int) * HELD_LIST;
+    return sizeof(double) * ((size_t)k * kq + kq + (size_t)lists * HELD_LIST) + sizeof(int) * HELD_LIST;
 }
 static bool held_sums_in_lds(int d, int k) { return held_lds_base(k) + sizeof(double) * (size_t)5 * d <= 64 * 1024; }
 size_t heldout_score_lds_bytes(int d, int k) { return held_lds_base(k) + (held_sums_in_lds(d, k) ? sizeof(double) * (size_t)5 * d : 0); }
@@ -334,11 +402,40 @@ int heldout_score_grid(int64_t n_rows, int d, int k, int n_cu) {
     return (int)std::min<int64_t>(n_rows, std::max<int64_t>(cu, std::min<int64_t>(cu * 16, cap)));
 }
 
-template <int MODE>
+template <int MODE, int FAM = HELD_GAUSS>
 static hipError_t launch_held(const HeldArgs &a, size_t lds, int grid, hipStream_t s) {
-    if (hipError_t e = lds > 64 * 1024 ? ensure_dynamic_lds<heldout_score_kernel<MODE>>(lds) : hipSuccess; e != hipSuccess) return e;
-    hipLaunchKernelGGL(heldout_score_kernel<MODE>, dim3((unsigned)grid), dim3(64), lds, s, a);
+    if (hipError_t e = lds > 64 * 1024 ? ensure_dynamic_lds<heldout_score_kernel<MODE, FAM>>(lds) : hipSuccess; e != hipSuccess) return e;
+    hipLaunchKernelGGL((heldout_score_kernel<MODE, FAM>), dim3((unsigned)grid), dim3(64), lds, s, a);
     return hipGetLastError();
+}
+
+// The family arms: k <= 16 and d <= 1024 (the callers' checks), so the column sums and the l slots are in LDS.
+bool heldout_family_covers(int d, int k) { return k >= 1 && k <= 16 && d >= 1 && d <= 1024; }
+int64_t heldout_family_part_len(int d, bool prec) { return (int64_t)4 * d + (prec ? 3 : 2); }
+int heldout_family_grid(int64_t n_rows, int n_cu) {
+    return n_rows <= 0 ? 0 : (int)std::min<int64_t>(n_rows, (int64_t)std::max(n_cu, 1) * 16);
+}
+
+hipError_t launch_heldout_score_prec(const double *H, int64_t ldh, const double *Q, int64_t ldq, const double *w, int d, int k,
+                                     int64_t n_rows, const double *model, const double *states, const double *covs, double *per_row,
+                                     double *part, int grid, hipStream_t s) {
+    if (n_rows <= 0 || grid <= 0) return hipSuccess;
+    if (!heldout_family_covers(d, k)) return hipErrorInvalidValue;
+    HeldArgs a{};
+    a.H = H, a.ldh = ldh, a.Q = Q, a.ldq = ldq, a.w = w, a.d = d, a.k = k, a.n_rows = n_rows, a.model = model, a.states = states;
+    a.covs = covs, a.per_row = per_row, a.part = part, a.sums_in_lds = 1;
+    return launch_held<HELD_MODEL, HELD_PREC>(a, held_lds_base(k, 2) + sizeof(double) * (size_t)5 * d, grid, s);
+}
+
+hipError_t launch_heldout_score_t(const double *H, int64_t ldh, const double *T, int64_t ldt, const double *w, int d, int k,
+                                  int64_t n_rows, const double *model, const double *states, const double *covs, const double *tbl,
+                                  double dof, double *per_row, double *part, int grid, hipStream_t s) {
+    if (n_rows <= 0 || grid <= 0) return hipSuccess;
+    if (!heldout_family_covers(d, k)) return hipErrorInvalidValue;
+    HeldArgs a{};
+    a.H = H, a.ldh = ldh, a.T = T, a.ldt = ldt, a.w = w, a.d = d, a.k = k, a.n_rows = n_rows, a.model = model, a.states = states;
+    a.covs = covs, a.tbl = tbl, a.dof = dof, a.per_row = per_row, a.part = part, a.sums_in_lds = 1;
+    return launch_held<HELD_MODEL, HELD_T>(a, held_lds_base(k) + sizeof(double) * (size_t)5 * d, grid, s);
 }
 
 hipError_t launch_heldout_score(const double *H, int64_t ldh, const double *w, int d, int k, int64_t n_rows, const double *model,

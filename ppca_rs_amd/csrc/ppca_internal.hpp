@@ -295,8 +295,8 @@ hipError_t launch_mix_loo_var(const double *X, int64_t ldx, int d, int64_t n_row
 // rows with an entry | (scratch)] per workgroup (reduce with launch_reduce_partials; the first 4 d + 2 are the sums); grid =
 // heldout_score_grid.
 int holdout_grid(int64_t n, int d, int n_cu);
-hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double fraction, uint64_t seed, int64_t row_offset,
-                          double *train, double *held, double *part, int grid, hipStream_t s);
+hipError_t launch_holdout(const double *X, int64_t ldx, int64_t n, int d, double lo, double hi, uint64_t seed, int64_t row_offset,
+                          double *train, double *held, double *part, int grid, hipStream_t s);  // held iff lo <= u < hi
 size_t heldout_score_lds_bytes(int d, int k);
 int64_t heldout_part_len(int d, int k);
 int heldout_score_grid(int64_t n_rows, int d, int k, int n_cu);
@@ -310,6 +310,21 @@ hipError_t launch_heldout_fold(const double *H, int64_t ldh, int d, int k, int64
                                const double *covs, const double *logpost, int comp, int nm, double *fold, int grid, hipStream_t s);
 hipError_t launch_heldout_finish(const double *H, int64_t ldh, const double *w, int d, int64_t n_rows, const double *fold,
                                  double *per_row, double *part, int grid, hipStream_t s);
+// The family arms of launch_heldout_score (heldout_family_covers: 1 <= k <= 16, 1 <= d <= 1024, else
+// hipErrorInvalidValue).  _prec: Q = the chunk's rows of the held precisions; an entry is scored iff x is finite and q is finite and
+// > 0, with v = sigma^2 / q + c_j^T Sigma c_j; states / covs: the known-precision posterior of the train rows (launch_hetero_sweep).
+// _t: T = the chunk's rows of `train` (the kernel takes m and delta of the row from them), states / covs the Gaussian posterior,
+// tbl[0 .. d] the device copy of ppca_t_pred_table_host.  part[grid][heldout_family_part_len(d, prec)] = [the 4 d sums | entries |
+// rows with an entry | _prec: held precisions that are negative or +inf at a finite x]; grid = heldout_family_grid.
+bool heldout_family_covers(int d, int k);
+int64_t heldout_family_part_len(int d, bool prec);
+int heldout_family_grid(int64_t n_rows, int n_cu);
+hipError_t launch_heldout_score_prec(const double *H, int64_t ldh, const double *Q, int64_t ldq, const double *w, int d, int k,
+                                     int64_t n_rows, const double *model, const double *states, const double *covs, double *per_row,
+                                     double *part, int grid, hipStream_t s);
+hipError_t launch_heldout_score_t(const double *H, int64_t ldh, const double *T, int64_t ldt, const double *w, int d, int k,
+                                  int64_t n_rows, const double *model, const double *states, const double *covs, const double *tbl,
+                                  double dof, double *per_row, double *part, int grid, hipStream_t s);
 // per-column streaming passes of factor analysis (ppca_scale.hip).  launch_scale_columns: out (nullable, n x d)
 // = x a_j on observed entries, NaN elsewhere; part[grid][3 d] the workgroups' column sums tot / sum / sq of w m, w m (x a - b),
 // w m (x a - b)^2 (reduce with launch_reduce_partials); rowsum (nullable, n) = sum_j m_ij l_j; abl_dev = [a | b | l], 3 d doubles;
