@@ -500,6 +500,53 @@ int ppca_h_em_step(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset *prec, int32_t 
 int ppca_h_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *train_prec, ppca_dataset *held, ppca_dataset *held_prec,
                          const ppca_model *model, double *totals_host, double *col_sums_host, double *per_row);
 
+/* --------------------------------------------------- masked PPCA on row-compressed data */
+/* An extension with no reference counterpart: the dataset as CSR -- row_ptr (int64, n + 1, monotone from 0 to nnz), col (int32, nnz,
+ * strictly increasing within a row, in [0, d)), val (fp64, nnz, finite) -- for data of which 0.1-3 % exists (ratings, assays), where
+ * the n x d form of ppca_dataset does not fit or is mostly NaN.  An entry that is absent is masked.  The model, the packed statistics
+ * (ppca_stats_len) and the M-step are the dense path's: ppca_sparse_em_accumulate produces the same additive buffer from a row pass
+ * over the CSR and a column pass over an inverted index that the constructor builds on the host.  State sizes 0 .. 16 (0 as one zero
+ * column; more: PPCA_ERR_UNSUPPORTED before any launch), any d >= 1; an empty dataset (n = 0): PPCA_ERR_EMPTY from every compute entry.
+ *
+ * Rows are processed in blocks of block_rows, a long column of a block in runs of `segment` entries (0 = the defaults: the records of
+ * a block stay under 1 GiB at k = 16; 512 entries).  The log-density, posterior mean and covariance of a row depend on its entry list
+ * alone: bit-identical under any grid limit, block_rows, weights or position.  For a given (block_rows, segment) the whole statistics
+ * buffer is bit-reproducible under any grid limit (fixed-order sums, no float atomics). */
+typedef struct ppca_sparse ppca_sparse;
+/* Any violation of the format above is PPCA_ERR_INVALID before any device work.  weights: n or NULL (= 1). */
+int ppca_sparse_from_host(ppca_ctx *ctx, int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *col, const double *val,
+                          const double *weights, int64_t block_rows, int32_t segment, ppca_sparse **out);
+/* The inverted index on host buffers (no GPU needed): per block of block_rows rows (0 = the default) a counting sort of the block's
+ * entries by column, stable in row order.  Block b covers the entries [row_ptr[b block_rows], row_ptr[min(n, (b + 1) block_rows)]) and
+ * writes that range of t_row_out (int32: the row within the block) and t_val_out; col_ptr_out (nullable, blocks x (d + 1)): the column
+ * offsets relative to the block's first entry.  Validates like the constructor, which calls the same routine. */
+int ppca_sparse_transpose_host(int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *col, const double *val, int64_t block_rows,
+                               int64_t *col_ptr_out, int32_t *t_row_out, double *t_val_out);
+int ppca_sparse_free(ppca_sparse *sp);
+int64_t ppca_sparse_len(const ppca_sparse *sp);
+int32_t ppca_sparse_output_size(const ppca_sparse *sp);
+int64_t ppca_sparse_nnz(const ppca_sparse *sp);
+double ppca_sparse_build_seconds(const ppca_sparse *sp); /* host time the constructor spent on the index, row lists and work items */
+/* Shares the entries and the index; weights_host: n or NULL (= 1). */
+int ppca_sparse_with_weights(ppca_sparse *sp, const double *weights_host, ppca_sparse **out);
+/* The CSR arrays and the weights back (each nullable). */
+int ppca_sparse_to_host(ppca_sparse *sp, int64_t *row_ptr, int32_t *col, double *val, double *weights);
+/* flags[j] = 1 iff column j has no entry (from the column counts of the index; no device work). */
+int ppca_sparse_empty_dimensions(ppca_sparse *sp, int32_t *flags);
+/* ppca_em_accumulate / ppca_em_step / ppca_stats_raw / ppca_llk / ppca_infer on row-compressed data.  ppca_sparse_em_step leaves its
+ * log-likelihood for ppca_em_last_llk like ppca_em_step.  An empty row has ell = 0, z = 0, Sigma = I. */
+int ppca_sparse_em_accumulate(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, double *stats_dev);
+int ppca_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model_in, const ppca_prior *prior, ppca_model *out,
+                        double *llk_in);
+int ppca_sparse_stats_raw(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, double *stats_host);
+int ppca_sparse_llk(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, double *total_host, double *per_row_host);
+int ppca_sparse_infer(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, double *states_host, double *covs_host);
+/* The predictive of a NEW reading at the query positions (query_row_ptr: n + 1, monotone from 0; query_col in [0, d), any order), given
+ * each row's entries in sp: mean = mean_j + c_j . z_i, var = c_j^T Sigma_i c_j + sigma^2 (the convention of ppca_heldout_score), one
+ * value per query entry in query order.  No n x d buffer exists anywhere. */
+int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr, const int32_t *query_col,
+                        double *mean_host, double *var_host);
+
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every
  * statistic above is a weighted sum over samples, so ONE all-reduce(sum) of the packed buffer per iteration

@@ -171,6 +171,22 @@ SIGNATURES = {
     "ppca_h_reconstruct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, c_void_pp]),
     "ppca_h_finalize_host": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, C.c_void_p, C.c_void_p]),
     "ppca_h_em_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, c_double_p, C.c_void_p, C.c_void_p, c_double_p]),
+    "ppca_sparse_from_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, c_void_pp]),
+    "ppca_sparse_transpose_host": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_sparse_free": (C.c_int, [C.c_void_p]),
+    "ppca_sparse_len": (C.c_int64, [C.c_void_p]),
+    "ppca_sparse_output_size": (C.c_int32, [C.c_void_p]),
+    "ppca_sparse_nnz": (C.c_int64, [C.c_void_p]),
+    "ppca_sparse_build_seconds": (C.c_double, [C.c_void_p]),
+    "ppca_sparse_with_weights": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp]),
+    "ppca_sparse_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_sparse_empty_dimensions": (C.c_int, [C.c_void_p, c_int32_p]),
+    "ppca_sparse_em_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_sparse_em_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Prior), C.c_void_p, c_double_p]),
+    "ppca_sparse_stats_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_sparse_llk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, C.c_void_p]),
+    "ppca_sparse_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_sparse_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppca_mix_em_step": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.POINTER(Prior), c_void_pp, C.c_void_p, c_double_p]),
     "ppca_mix_last_rows_used": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "ppca_mix_llk": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, c_double_p, C.c_void_p, C.c_void_p]),

@@ -421,6 +421,190 @@ class DatasetChunks:
         raise StopIteration
 
 
+# --------------------------------------------------------------------------- row-compressed data
+class SparseDataset:
+    """A dataset in CSR form (an extension with no reference counterpart): of an N x n_columns matrix only the entries
+    that exist are stored, everything else is masked.  For data of which a few percent exists (ratings, purchases, assays), where the
+    dense N x d form of `Dataset` does not fit the device or is almost all NaN.
+
+    `SparseDataset(indptr, indices, values, n_columns, weights=None)`: indptr (N + 1, monotone from 0 to nnz), indices (nnz, strictly
+    increasing within a row, in [0, n_columns)), values (nnz, finite).  Anything else raises ValueError before the library is touched.
+    block_rows / segment: the two tiling lengths of the passes (None: the library's defaults; tests put the seams at small sizes).
+    The entries go to the device, with the inverted index the statistics pass reads, on first use."""
+
+    def __init__(self, indptr, indices, values, n_columns: int, weights=None, *, ctx=None, block_rows: Optional[int] = None,
+                 segment: Optional[int] = None):
+        ip = np.asarray(indptr)
+        ix = np.asarray(indices)
+        v = np.asarray(values)
+        if ip.ndim != 1 or ix.ndim != 1 or v.ndim != 1:
+            raise ValueError("indptr, indices and values must be 1-D")
+        if ip.size < 1 or (ip.size and not np.issubdtype(ip.dtype, np.integer)) or (ix.size and not np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr (at least one element) and indices must be integer arrays")
+        d = int(n_columns)
+        if d < 1 or d >= 2 ** 31:
+            raise ValueError("n_columns must lie in [1, 2^31)")
+        ip = np.ascontiguousarray(ip, dtype=np.int64)
+        n = ip.size - 1
+        if ip[0] != 0 or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0 and be monotone")
+        if ip[-1] != ix.size or ix.size != v.size:
+            raise ValueError("indptr[-1], len(indices) and len(values) differ")
+        if ix.size and (ix.min() < 0 or ix.max() >= d):
+            raise ValueError(f"a column index lies outside [0, {d})")
+        ix = np.ascontiguousarray(ix, dtype=np.int32)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if ix.size > 1:
+            inc = np.diff(ix) > 0
+            inc[ip[1:-1][(ip[1:-1] > 0) & (ip[1:-1] < ix.size)] - 1] = True  # (the step from one row's last entry to the next row's first)
+            if not inc.all():
+                raise ValueError("column indices must be strictly increasing within a row (sorted, no duplicates)")
+        if not np.isfinite(v).all():
+            raise ValueError("values must be finite (an entry that is missing is simply not stored)")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights), dtype=np.float64).ravel()
+            if w.shape[0] != n:
+                raise ValueError("weights and data differ in length")
+        for name, val in (("block_rows", block_rows), ("segment", segment)):
+            if val is not None and int(val) < 1:
+                raise ValueError(f"{name} must be positive")
+        for a in (ip, ix, v):
+            a.setflags(write=False)
+        self._indptr, self._indices, self._values, self._d, self._w = ip, ix, v, d, w
+        self._block_rows, self._segment = int(block_rows or 0), int(segment or 0)
+        self._ctx_arg = ctx
+        self._handle = None
+
+    # -- construction ---------------------------------------------------------
+    @classmethod
+    def from_dense(cls, ndarray, weights=None, **kw) -> "SparseDataset":
+        """The finite entries of an (N, d) array; non-finite ones are dropped (they are what `Dataset` masks)."""
+        x = np.asarray(ndarray, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("from_dense expects a 2-D array")
+        obs = np.isfinite(x)
+        indptr = np.concatenate([[0], np.cumsum(obs.sum(axis=1))]).astype(np.int64)
+        return cls(indptr, np.nonzero(obs)[1].astype(np.int32), x[obs], x.shape[1], weights, **kw)
+
+    @classmethod
+    def from_coo(cls, rows, cols, values, shape, weights=None, **kw) -> "SparseDataset":
+        """From (row, column, value) triplets in any order; a position given twice raises ValueError."""
+        r = np.asarray(rows).astype(np.int64).ravel()
+        c = np.asarray(cols).astype(np.int64).ravel()
+        v = np.asarray(values, dtype=np.float64).ravel()
+        n, d = int(shape[0]), int(shape[1])
+        if not (r.size == c.size == v.size):
+            raise ValueError("rows, cols and values differ in length")
+        if r.size and (r.min() < 0 or r.max() >= n):
+            raise ValueError(f"a row index lies outside [0, {n})")
+        order = np.lexsort((c, r))
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))]).astype(np.int64)
+        return cls(indptr, c[order], v[order], d, weights, **kw)
+
+    # -- the device handle ----------------------------------------------------
+    @property
+    def _ctx(self) -> _lib.Context:
+        if self._ctx_arg is None:
+            self._ctx_arg = _ctx(None)
+        return self._ctx_arg
+
+    @property
+    def _h(self):
+        # every pass written for the dense layout reaches its dataset through _h
+        raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
+                        "predict and PPCATrainer are")
+
+    @property
+    def _sh(self):
+        if self._handle is None:
+            h = C.c_void_p()
+            check(lib().ppca_sparse_from_host(self._ctx.handle, len(self), self._d, ptr(self._indptr), ptr(self._indices), ptr(self._values),
+                                              ptr(self._w), self._block_rows, self._segment, C.byref(h)))
+            self._handle = h
+        return self._handle
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                lib().ppca_sparse_free(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    # -- accessors ------------------------------------------------------------
+    def __len__(self) -> int:
+        return int(self._indptr.size - 1)
+
+    def output_size(self) -> Optional[int]:
+        return self._d if len(self) > 0 else None
+
+    @property
+    def nnz(self) -> int:
+        return int(self._values.size)
+
+    def csr(self):
+        """(indptr int64, indices int32, values float64): copies."""
+        return self._indptr.copy(), self._indices.copy(), self._values.copy()
+
+    def weights(self) -> np.ndarray:
+        return np.ones(len(self)) if self._w is None else self._w.copy()
+
+    def with_weights(self, weights) -> "SparseDataset":
+        """Same entries (and, once built, the same device copy and index), new weights."""
+        w = np.ascontiguousarray(np.asarray(weights), dtype=np.float64).ravel()
+        if w.shape[0] != len(self):
+            raise ValueError("weights and data differ in length")
+        out = SparseDataset.__new__(SparseDataset)
+        out.__dict__.update(self.__dict__)
+        out._w, out._handle = w, None
+        if self._handle is not None:
+            h = C.c_void_p()
+            check(lib().ppca_sparse_with_weights(self._handle, ptr(w), C.byref(h)))
+            out._handle = h
+        return out
+
+    def empty_dimensions(self) -> List[int]:
+        """Columns without an entry."""
+        if len(self) == 0:
+            return []
+        return np.flatnonzero(np.bincount(self._indices, minlength=self._d) == 0).tolist()
+
+    def index_build_seconds(self) -> float:
+        """Host time the constructor of the device copy spent on the inverted index, the row lists and the work items."""
+        return float(lib().ppca_sparse_build_seconds(self._sh))
+
+    def _dense(self) -> np.ndarray:
+        x = np.full((len(self), self._d), np.nan)
+        x[np.repeat(np.arange(len(self)), np.diff(self._indptr)), self._indices] = self._values
+        return x
+
+    def to_dense(self) -> Dataset:
+        """The same data as a `Dataset` (NaN where there is no entry), with the same weights."""
+        return Dataset(self._dense(), self._w, ctx=self._ctx)
+
+    def __repr__(self):
+        return f"SparseDataset(n={len(self)}, output_size={self.output_size()}, nnz={self.nnz})"
+
+
+def _query_pattern(sparse: SparseDataset, query):
+    """(indptr int64, indices int32) of a predict query: a SparseDataset or an (indptr, indices) pair with the rows of `sparse`."""
+    if isinstance(query, SparseDataset):
+        ip, ix = query._indptr, query._indices
+        if query._d != sparse._d:
+            raise ValueError("query and data differ in the number of columns")
+    else:
+        ip = np.ascontiguousarray(np.asarray(query[0]), dtype=np.int64)
+        ix = np.ascontiguousarray(np.asarray(query[1]), dtype=np.int32)
+    if ip.ndim != 1 or ip.size != len(sparse) + 1:
+        raise ValueError("query and data differ in the number of rows")
+    if ip[0] != 0 or np.any(np.diff(ip) < 0) or ip[-1] != ix.size:
+        raise ValueError("query indptr must be monotone from 0 to len(indices)")
+    if ix.size and (ix.min() < 0 or ix.max() >= sparse._d):
+        raise ValueError(f"a query column lies outside [0, {sparse._d})")
+    return ip, ix
+
+
 # --------------------------------------------------------------------------- pairwise second moments
 class PairwiseMoments:
     """What `Dataset.pairwise_moments` returns, host arrays: `center` (d) and the d x d matrices `sums`, `counts` and (optional)
@@ -759,6 +943,8 @@ class PPCAModel:
         # :399-402) is accepted as the reference accepts it: the library carries it as ONE zero transform column, with
         # which every pass reproduces the k = 0 model exactly (include/ppca_hip.h, ppca_model_create)
         if method == "pca":
+            if isinstance(dataset, SparseDataset):
+                raise ValueError("method='pca' is not available on a SparseDataset: the d x d moments are not built from row-compressed data")
             return PPCAModel.from_moments(state_size, dataset.pairwise_moments())
         if method != "random":
             raise ValueError("method must be 'random' or 'pca'")
@@ -809,12 +995,18 @@ class PPCAModel:
     def llk(self, dataset: Dataset) -> float:
         """Weighted log-likelihood (ppca_model.rs:142-149)."""
         tot = C.c_double(0.0)
+        if isinstance(dataset, SparseDataset):
+            check(lib().ppca_sparse_llk(dataset._ctx.handle, dataset._sh, self._device(dataset._ctx).h, C.byref(tot), None))
+            return tot.value
         check(lib().ppca_llk(dataset._ctx.handle, dataset._h, self._device(dataset._ctx).h, C.byref(tot), None))
         return tot.value
 
     def llks(self, dataset: Dataset) -> np.ndarray:
         """Per-sample log-likelihood (ppca_model.rs:152-159)."""
         out = np.empty(len(dataset))
+        if isinstance(dataset, SparseDataset):
+            check(lib().ppca_sparse_llk(dataset._ctx.handle, dataset._sh, self._device(dataset._ctx).h, None, ptr(out)))
+            return out
         check(lib().ppca_llk(dataset._ctx.handle, dataset._h, self._device(dataset._ctx).h, None, ptr(out)))
         return out
 
@@ -823,10 +1015,27 @@ class PPCAModel:
         n, k = len(dataset), self.state_size
         states = np.empty((n, k))
         covs = np.empty((n, k, k))
-        check(lib().ppca_infer(dataset._ctx.handle, dataset._h, self._device(dataset._ctx).h, ptr(states), ptr(covs)))
+        fn, h = (lib().ppca_sparse_infer, dataset._sh) if isinstance(dataset, SparseDataset) else (lib().ppca_infer, dataset._h)
+        check(fn(dataset._ctx.handle, h, self._device(dataset._ctx).h, ptr(states), ptr(covs)))
         return InferredMasked(self, states, covs)
 
+    def predict(self, sparse: "SparseDataset", query):
+        """The predictive of a new reading at chosen positions of row-compressed data: `query` is a SparseDataset (its values are
+        ignored) or an (indptr, indices) pair with the rows of `sparse`.  Returns (mean, var), one value per query entry in query
+        order: mean = mean_j + c_j . z_i and var = c_j^T Sigma_i c_j + sigma^2 with (z_i, Sigma_i) the row's posterior given its
+        entries in `sparse` -- the convention of `heldout_score`.  No N x d array is formed."""
+        if not isinstance(sparse, SparseDataset):
+            raise TypeError("predict takes a SparseDataset (on a Dataset: smooth / extrapolate / heldout_score)")
+        ip, ix = _query_pattern(sparse, query)
+        mean, var = np.empty(ix.size), np.empty(ix.size)
+        ctx = sparse._ctx
+        check(lib().ppca_sparse_predict(ctx.handle, sparse._sh, self._device(ctx).h, ptr(ip), ptr(ix), ptr(mean), ptr(var)))
+        return mean, var
+
     def _recon(self, dataset: Dataset, mode: int, fn) -> Dataset:
+        if isinstance(dataset, SparseDataset):
+            raise TypeError("smooth / extrapolate would write an N x d output, which is what a SparseDataset exists to avoid: use "
+                            "predict(sparse, query) at the positions that are wanted")
         h = C.c_void_p()
         check(fn(dataset._ctx.handle, dataset._h, self._device(dataset._ctx).h, mode, C.byref(h)))
         return Dataset._wrap(h, dataset._ctx)
@@ -896,8 +1105,8 @@ class PPCAModel:
         dev_out = _DevModel(out)
         pref, keep = _prior_ref(prior)
         llk = C.c_double(0.0)
-        check(lib().ppca_em_step(ctx.handle, dataset._h, self._device(ctx).h, pref, dev_out.h,
-                                 C.byref(llk) if want_llk else None))
+        fn, h = (lib().ppca_sparse_em_step, dataset._sh) if isinstance(dataset, SparseDataset) else (lib().ppca_em_step, dataset._h)
+        check(fn(ctx.handle, h, self._device(ctx).h, pref, dev_out.h, C.byref(llk) if want_llk else None))
         new = PPCAModel._from_device(dev_out, ctx, self.output_size, self.state_size)
         return new, (llk.value if want_llk else None)
 

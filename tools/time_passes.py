@@ -20,7 +20,8 @@ the sweep alone (HPPCAModel.llks), a whole HPPCAModel.iterate, PPCAModel.llks an
 device-to-device copy of X whose rate prices the traffic floor of the iteration (X and P read twice, the records written and read
 once).  `--heldout` runs ONLY the legs of held-out scoring, in one process, alternating: the device split, the
 score, PPCAModel.loo_llks and the scale pass with output for comparison, and the composition the feature replaces (extrapolate, the
-extrapolated covariance diagonal and both downloads)."""
+extrapolated covariance diagonal and both downloads).  `--sparse DENSITY` / `--sparse-rows M [--k2 K2]` run ONLY the legs of
+SparseDataset (see sparse_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,6 +30,128 @@ from ppca_rs_amd import _lib
 
 n, d, k = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 ctx = _lib.default_context()
+
+
+def sparse_legs(reps=5):
+    """SparseDataset, in one process, alternating, every repetition timed on its own.  `--sparse DENSITY`: every entry
+    of N x d exists with that probability; the sparse llks / iterate next to PPCAModel.llks / iterate on the same data as a dense
+    Dataset and the device-to-device copy of that array.  `--sparse-rows M`: a shape the dense layout cannot hold -- row lengths
+    log-normal with mean M (long-tailed), columns uniform; the sparse legs alone, at state size K and (with `--k2 K2`) K2, and the host
+    time of the index build.  The data is made on the device (before the dense dataset of the other legs, which this leg never
+    builds).  Floor: per entry 12 B of CSR, 8 k B of C, 12 B of index and 8 (k + k' + 1) B of record gathered; per row the record
+    written once; priced at the copy's rate."""
+    import torch
+
+    dev = "cuda"
+    torch.manual_seed(11)
+    rows_mode = "--sparse-rows" in sys.argv
+    kt = k
+    ct = torch.randn((d, kt), dtype=torch.float64, device=dev)
+    mt = torch.randn(d, dtype=torch.float64, device=dev)
+    if rows_mode:
+        per = float(sys.argv[sys.argv.index("--sparse-rows") + 1])
+        lengths = torch.exp(torch.randn(n, device=dev) + (np.log(per) - 0.5)).floor().clamp(1, d).long()
+        rows = torch.repeat_interleave(torch.arange(n, device=dev), lengths)
+        key = torch.unique(rows * d + torch.randint(0, d, (rows.numel(),), device=dev), sorted=True)  # sorted by (row, column), no duplicates
+        rows, cols = key // d, key % d
+        del key
+        counts = torch.bincount(rows, minlength=n)
+    else:
+        density = float(sys.argv[sys.argv.index("--sparse") + 1])
+        mask = torch.rand((n, d), device=dev) < density
+        nz = mask.nonzero()
+        rows, cols = nz[:, 0].contiguous(), nz[:, 1].contiguous()
+        del nz
+        counts = mask.sum(dim=1)
+    zt = torch.randn((n, kt), dtype=torch.float64, device=dev)
+    vals = torch.empty(rows.numel(), dtype=torch.float64, device=dev)
+    step = 1 << 25
+    for a in range(0, rows.numel(), step):
+        r, c = rows[a:a + step], cols[a:a + step]
+        vals[a:a + step] = (ct[c] * zt[r]).sum(dim=1) + mt[c] + 0.5 * torch.randn(r.numel(), dtype=torch.float64, device=dev)
+    indptr = np.concatenate([[0], np.cumsum(counts.cpu().numpy())]).astype(np.int64)
+    nnz = int(rows.numel())
+    lens = np.diff(indptr)
+    print(f"SparseDataset legs: N = {n}, d = {d}, nnz = {nnz} ({nnz / n / d:.4%} of N x d; {nnz / n:.1f} per row, median {np.median(lens):.0f}, "
+          f"max {lens.max()}); dense form {8.0 * n * d / 1e9:.1f} GB", flush=True)
+    t0 = time.perf_counter()
+    sp = P.SparseDataset(indptr, cols.int().cpu().numpy(), vals.cpu().numpy(), d, ctx=ctx)
+    sp._sh
+    print(f"  host: validation, index build and upload {time.perf_counter() - t0:.2f} s, of which the index, row lists and work items "
+          f"{sp.index_build_seconds():.2f} s", flush=True)
+
+    def series(fn):
+        fn(); fn(); ctx.synchronize()  # warm-up: code objects, the block cache
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    def floor_ms(kk, rate, em):
+        rec = kk * (kk + 1) // 2 + kk + 1
+        per_entry = 12 + 8 * kk + ((12 + 8 * rec) if em else 0)
+        return (nnz * per_entry + (n * 8.0 * rec if em else 8.0 * n)) / rate / 1e6
+
+    hip = C.CDLL(_lib.LIB_PATH)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipDeviceSynchronize.argtypes = []
+    if rows_mode:
+        del rows, cols, vals, zt
+        nbytes = 1 << 32
+        src, dst = torch.empty(nbytes // 8, dtype=torch.float64, device=dev), torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        def copy():
+            assert hip.hipMemcpy(dst.data_ptr(), src.data_ptr(), C.c_size_t(nbytes), 3) == 0
+            assert hip.hipDeviceSynchronize() == 0
+        ks = [k] + ([int(sys.argv[sys.argv.index("--k2") + 1])] if "--k2" in sys.argv else [])
+        models = {kk: P.PPCAModel.init(kk, sp, seed=3).iterate(sp) for kk in ks}
+        legs = [("hipMemcpy device to device (4 GiB)", copy)]
+        for kk in ks:
+            legs += [(f"sparse llks, k = {kk}", lambda kk=kk: models[kk].llks(sp)), (f"sparse iterate, k = {kk}", lambda kk=kk: models[kk].iterate(sp))]
+    else:
+        xd = torch.full((n, d), float("nan"), dtype=torch.float64, device=dev)
+        xd[mask] = vals
+        del mask, rows, cols, vals, zt
+        torch.cuda.synchronize()
+        dense = P.Dataset.from_device(xd.data_ptr(), n, d, ctx=ctx, keepalive=xd)
+        spare = torch.empty((n, d), dtype=torch.float64, device=dev)
+        nbytes = 8 * n * d
+        def copy():
+            assert hip.hipMemcpy(spare.data_ptr(), xd.data_ptr(), C.c_size_t(nbytes), 3) == 0
+            assert hip.hipDeviceSynchronize() == 0
+        ks = [k]
+        model = P.PPCAModel.init(k, sp, seed=3).iterate(sp)
+        legs = [("hipMemcpy device to device (N x d)", copy),
+                ("PPCAModel.llks on to_dense()", lambda: model.llks(dense)), ("sparse llks", lambda: model.llks(sp)),
+                ("PPCAModel.iterate on to_dense()", lambda: model.iterate(dense)), ("sparse iterate", lambda: model.iterate(sp))]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn))
+    med = {name: report(name, np.concatenate(got[name])) for name, _ in legs}
+    rate = 2.0 * nbytes / med[legs[0][0]] / 1e6  # GB/s of the copy (a read and a write)
+    print(f"  copy rate {rate:.0f} GB/s")
+    for kk in ks:
+        tag = f", k = {kk}" if rows_mode else ""
+        fl, fi = floor_ms(kk, rate, False), floor_ms(kk, rate, True)
+        print(f"  k = {kk}: llks floor {fl:.3f} ms, achieved fraction {fl / med['sparse llks' + tag]:.3f};  iterate floor {fi:.3f} ms, "
+              f"achieved fraction {fi / med['sparse iterate' + tag]:.3f}")
+    if not rows_mode:
+        print(f"  sparse / dense: llks {med['sparse llks'] / med['PPCAModel.llks on to_dense()']:.3f}, "
+              f"iterate {med['sparse iterate'] / med['PPCAModel.iterate on to_dense()']:.3f}  (below 1: the sparse path is faster)")
+
+
+if "--sparse" in sys.argv or "--sparse-rows" in sys.argv:
+    sparse_legs()
+    sys.exit(0)
+
 truth = P.PPCAModel(0.1, np.random.default_rng(1).standard_normal((d, k)), np.random.default_rng(2).standard_normal(d))
 spec = _lib.SynthSpec(0, n, d, k, 0.1, 0.3, 0, 0, 1033, truth._c.ctypes.data_as(_lib.c_double_p),
                       truth._mean.ctypes.data_as(_lib.c_double_p))
