@@ -1025,8 +1025,10 @@ static int em_accumulate_impl(ppca_ctx *ctx, ppca_dataset *ds, const ppca_model 
         {
             const double tl = (double)((n + FUSED_TILE - 1) / FUSED_TILE) / grid;
             // (em9: "P2" = the Gram's last two digit pairs, "b-loop" = b = X~ C, "gram-1" = mask bytes + the first two digit pairs)
-            static const char *fn[16] = {"P2", "wait-back", "stores", "barrier", "b-loop", "barrier", "factor", "solve", "columns", "scalars",
-                                         "wg-barrier", "P4a", "barrier", "staging", "barrier", "gram-1"};
+            // ("F1", "F3", "F4": the front role's barriers in front of phase beta, behind P4a and behind the staging; "solved": the wait
+            //  for the trip's solver inside P4a, behind its table and mean requests)
+            static const char *fn[16] = {"P2", "wait-back", "stores", "F1", "b-loop", "solved", "factor", "solve", "columns", "scalars",
+                                         "wg-barrier", "P4a", "F3", "staging", "F4", "gram-1"};
             static const char *bn[16] = {"wg-barrier", "digitise", "barrier", "contract", "-", "-", "-", "-", "-", "-", "-", "-", "-", "-", "-", "-"};
             for (int w = 0; w < 8; ++w) {
                 double tw[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};

@@ -59,6 +59,38 @@
 // per-dimension sample masks of the last four tiles are kept (16 bytes per dimension), so the staging of tile t + 1
 // never touches what the contraction of earlier tiles reads.
 //
+// Ledger of the counters (OFF_BAR, all monotonic from 0; every spin is unbounded, so every target is a closed form in the trip).
+// T = tiles of the workgroup; the front role makes trips rel = 0 .. T, trip T is the extra trip (no tile: `cur` false, no P2, no
+// solver, no P4a, no staging); solver(rel) = wave rel mod 4; the back role makes iterations r = 0 .. T - 1.
+//
+//   counter  who adds, how much, where                                          waiter: target
+//   fbar     every front wave 1 at each of: the prologue barrier; F1 (in front   the same four waves, 4 per barrier passed: prologue
+//            of phase beta) of trips 0 .. T; F3 (behind P4a) and F4 (behind      4; F1 of trip rel 4 (3 rel + 2); F3 4 (3 rel + 3);
+//            the staging) of trips < T; the epilogue barrier                     F4 4 (3 rel + 4); epilogue 4 (3 T + 3)
+//   cbar     every column wave 1 behind its factor loads, trips 1 .. T           the column waves, in front of their wP stores: 3 rel
+//   solved   solver(rel) 1 behind its last store of the trip, trips < T          the other three waves of trip rel < T, behind P4a's
+//                                                                                table / mean requests, in front of its first read of
+//                                                                                the tile's [wz | w]: rel + 1
+//   wready   every front wave 1 behind its OWN phase-beta stores, trips 1 .. T   back, top of iteration r: 4 (r + 1)
+//   digdone  every back wave 1 behind its last read of tile r's W rows           front, in front of its [G | b] stores of trip
+//                                                                                rel >= 2: 4 (rel - 1)
+//   itdone   every back wave 1 at the end of iteration r                         front, in front of the staging of trip rel >= 2:
+//                                                                                4 (rel - 1)
+//   bbar     every back wave 1 per barrier of its role (2 per attempt, more on   the same four waves: 4 per barrier passed
+//            the cold paths)
+//
+// Walk.  T = 0: prologue barrier (fbar 4), trip 0 is the extra trip: F1 (8), rel = 0 adds nothing to wready, break; epilogue (12 =
+// 4 (3 T + 3)); the back role makes no iteration; solved, wready, cbar stay 0 and nobody waits on them.  T = 1: prologue staging
+// of tile 0 (no reader of the x~ tile yet), barrier (4); trip 0: F1 (8), wave 0 solves and adds solved = 1, no column waves, no
+// wready; waves 1-3 wait solved >= 1; P4a; F3 (12); staging; F4 (16); trip 1 (extra): F1 (20), waves 2, 3, 0 are column waves
+// (cbar 3 >= 3), wave 1 -- the trip's solver -- has no tile; all four add wready = 4, break; epilogue (24); back iteration 0 waits
+// wready >= 4, adds digdone 4, itdone 4 (nobody waits: rel < 2).  T = 2: as T = 1 through F4 of trip 0; trip 1: F1 (20), wave 1
+// solves (solved = 2), waves 2, 3, 0 form the columns of tile 0 (cbar 3), wready = 4 as each wave's stores are out -- back
+// iteration 0 may start while the solver still works: it reads the OTHER parity's buffer --, waves 0, 2, 3 wait solved >= 2, F3
+// (24), F4 (28); trip 2 (extra): F1 (32), columns of tile 1 (cbar 6), wready = 8, back iteration 1 waits wready >= 8; epilogue
+// (36).  The first waits on digdone / itdone are at trip 2 of T >= 3: 4 (rel - 1) = 4 = back iteration 0 over.  The same ledger is
+// run under random schedules in tests/test_em_role_sync_host.py.
+//
 // Replaces in the reference: infer (ppca/src/ppca_model.rs:221-227), the cross moment (:281-293), the d second-moment
 // scans (:294-306), the noise 4-tuple (:328-358) and llk (:142-149) -- as pass_kernel, whose per-sample arithmetic,
 // tile order and summation orders the front role keeps (cross, sumx, the scalars and the llk are bit-identical to it).
@@ -95,6 +127,13 @@ constexpr int E9_FLUSH_GROUPS = 100;
 //    rows of tile rel + 2 at the top of phase beta (one nt dword per 128-byte line through the tile's clamped descriptor: 94.1-94.2,
 //    the solver's loads and the column waves' trip grew from 0.26 / 2.5 k to 1.1 / 5.1 k cycles per tile);
 //    profiles/em9_load_order/README.md.
+//  - the barrier behind phase beta is a one-way signal from the solver (`solved`) and wready is added per wave: 108.06 against
+//    106.47 EM it/s (+1.5 %, medians of five alternating runs; as a switch build in two earlier jobs 108.25-108.37 against
+//    106.19-106.35).  Measured in those jobs and NOT kept: the barrier in
+//    front of phase beta as a wait of the solver alone (107.95 alone, 107.95 with `solved`), the barrier behind P4a as a
+//    split-phase barrier whose wait stands behind the first row's arithmetic of the staging (107.68 alone, 107.52 with `solved`;
+//    behind two rows 107.64 with both others), all three 107.86-108.01: each gains alone, none adds to `solved`;
+//    profiles/em9_role_sync/README.md.
 //  - both roles run at the default wave priority, and a wave that polls a role barrier sleeps one s_sleep(1) per look.
 constexpr int E9_X_AUX = 2;  // cache policy of the row loads of X: nt (L2-served: the rows are read once and would only push the digit table and the
                              // third column group of C out of the 32 KB L1).  Measured on layout B, two rounds interleaved: 103.9-104.1 against
@@ -183,7 +222,15 @@ __device__ __forceinline__ void wait_counter(const unsigned *ctr, unsigned need)
     }
     asm volatile("" ::: "memory");
 }
-
+// One-way hand-off: the wave's add follows its earlier LDS reads and stores (in order, as above) without waiting for them;
+// neither the compiler nor the scheduler may move an LDS access across it.
+__device__ __forceinline__ void arrive_counter(unsigned *ctr, int lane) {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (lane == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+}
 
 // WEIGHTED: the dataset carries sample weights (PassArgs::w).  A template parameter because the weighted pass takes a
 // logarithm per sample and tile (the unweighted one multiplies the determinants up and takes one per lane per kernel):
@@ -211,7 +258,8 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
     double *scl = sm + cfg::OFF_L;
     int *Ex = reinterpret_cast<int *>(sm + cfg::OFF_E);
     unsigned *ctr = reinterpret_cast<unsigned *>(sm + cfg::OFF_BAR);
-    unsigned *fbar = ctr, *bbar = ctr + 1, *digdone = ctr + 2, *vstamp = ctr + 3, *wready = ctr + 4, *itdone = ctr + 5, *cbar = ctr + 6;
+    unsigned *fbar = ctr, *bbar = ctr + 1, *digdone = ctr + 2, *vstamp = ctr + 3, *wready = ctr + 4, *itdone = ctr + 5, *cbar = ctr + 6,
+             *solved = ctr + 7;
 
     if (p.qflag) {  // qprep's dynamic-range guard: the fp64-Gram pass_kernel runs instead
         int unsafe = 0;
@@ -1154,10 +1202,12 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
             sq_run += sc_sq;
         }
         if (wave == solver) { E9_FINE(6) } else { E9_FINE(8) }  // "factor": the solver's trip; "columns": a column wave's
-        // the factor, z and [wz | w] of tile rel and the W rows of tile rel - 1 are final
-        role_barrier(fbar, fbar_target, lane_entry);
-        E9_FINE(5)
-        if (rel > 0 && lane_entry == 0) __hip_atomic_fetch_add(wready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        // No barrier behind phase beta (it made the solver wait for the column waves and every column wave for the slowest: 1.5 k
+        // cycles per tile in the phase table).  What this wave stored is handed on one way: the solver's [wz | w] to P4a of the other
+        // three (solved), every wave's share of the W rows of tile rel - 1 to the back role (wready: 4 per trip from trip 1 on).
+        // Nothing in P4a reads what the column waves wrote; the barrier behind P4a orders the rest of the trip.
+        if (cur && wave == solver) arrive_counter(solved, lane_entry);
+        if (rel > 0) arrive_counter(wready, lane_entry);
         if (!cur) break;
         // ------------------------------------------------------------ P4a: cross / sumx += X~^T [wz | w]
         // the only reader of the x~ tile; the next tile's rows are requested one per k-step behind the MFMAs
@@ -1171,6 +1221,13 @@ __global__ __launch_bounds__(512) void em9_kernel(PassArgs p) {
             // k = sample 4 s + l4 of the step; A: x~[sample][dim 16 r + (lane & 15)] (rows 4 b + i of block b: the operand the
             // 16x16x4 form read); B: [wz | w][sample][column 4 c + (lane & 3)], the same for the four blocks
             const int j4 = lane & 3;
+            // the solver's [wz | w] of this trip, waited for BEHIND the requests above: none of them depends on the solver, and a
+            // wave that finishes its columns early queues them early
+            E9_FINE(11)
+            __builtin_amdgcn_sched_barrier(0);
+            if (wave != solver) wait_counter(solved, (unsigned)(rel + 1));
+            __builtin_amdgcn_sched_barrier(0);
+            E9_FINE(5)  // "solved"
 #pragma unroll
             for (int s0 = 0; s0 < AH; ++s0) {
                 const int smp = 4 * s0 + l4;
