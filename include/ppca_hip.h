@@ -511,7 +511,8 @@ int ppca_h_heldout_score(ppca_ctx *ctx, ppca_dataset *train, ppca_dataset *train
  * Rows are processed in blocks of block_rows, a long column of a block in runs of `segment` entries (0 = the defaults: the records of
  * a block stay under 1 GiB at k = 16; 512 entries).  The log-density, posterior mean and covariance of a row depend on its entry list
  * alone: bit-identical under any grid limit, block_rows, weights or position.  For a given (block_rows, segment) the whole statistics
- * buffer is bit-reproducible under any grid limit (fixed-order sums, no float atomics). */
+ * buffer is bit-reproducible under any grid limit (fixed-order sums, no float atomics).  Hold-out splits and held-out scores of such
+ * data: ppca_heldout_split_csr_host and ppca_heldout_score_sparse, at the end of this section. */
 typedef struct ppca_sparse ppca_sparse;
 /* Any violation of the format above is PPCA_ERR_INVALID before any device work.  weights: n or NULL (= 1). */
 int ppca_sparse_from_host(ppca_ctx *ctx, int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *col, const double *val,
@@ -546,6 +547,28 @@ int ppca_sparse_infer(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, d
  * value per query entry in query order.  No n x d buffer exists anywhere. */
 int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr, const int32_t *query_col,
                         double *mean_host, double *var_host);
+/* The hold-out split of ppca_dataset_holdout_range on the pattern of row-compressed data, on host buffers (no GPU needed; DESIGN.md
+ * 4.21).  row_ptr (n + 1, from 0, monotone) and col (>= 0) as above.  Entry e of row i, column j = col[e], global row
+ * g = row_offset + i draws the word of the dense split, u = (row_word(row_key(seed, 8, g), j) >> 11) 2^-53, and
+ * held_flag_out[e] = 1 iff lo <= u < hi, else 0: the entries held are exactly those the dense split holds in the same matrix.
+ * counts_out (nullable, 2) = [entries kept, entries held].  Requires 0 <= lo <= hi <= 1 (anything else, or NaN), row_offset >= 0 and a
+ * monotone row_ptr, else PPCA_ERR_INVALID. */
+int ppca_heldout_split_csr_host(int64_t n, const int64_t *row_ptr, const int32_t *col, double lo, double hi, uint64_t seed,
+                                int64_t row_offset, uint8_t *held_flag_out, int64_t *counts_out);
+/* ppca_heldout_score on row-compressed data: (z, Sigma) is the posterior of row i given its entries in `train`
+ * (ppca_sparse_infer; an empty row: 0, I) and every entry x of `held` in that row is scored as a new reading of column j,
+ *   m = mean_j + c_j^T z,  v = sigma^2 + c_j^T Sigma c_j,  e = x - m,  l = -1/2 (ln 2 pi + ln v + e^2 / v)
+ * whatever `train` has at j.  Weights are train's; held's are ignored.  Outputs as ppca_heldout_score (all host memory): per_row
+ * (nullable, n) = sum_j l, 0 for a row without held entries; col_sums_host (nullable, 4 d) = per column [sum w, sum w l, sum w e^2,
+ * sum w e^2 / v]; totals_host (6) = those four added over the columns in index order, the unweighted entry count, the rows with a
+ * held entry.  A `held` without entries gives zeros.  State size 0 runs as one zero column: (mean_j, sigma^2).
+ * Preconditions: k <= 16 (else PPCA_ERR_UNSUPPORTED before any launch); equal n, d, device and block_rows of the two datasets (else
+ * PPCA_ERR_INVALID: block b of each must cover the same rows); n = 0: PPCA_ERR_EMPTY.
+ * No n x d buffer and no float atomics; the scratch is one block's states and covariances.  per_row[i] depends on the row's train
+ * and held entry lists alone: bit-identical under any grid limit, block_rows, weights or position.  For a given (block_rows,
+ * segment) of `held` the column sums are bit-identical under any grid limit. */
+int ppca_heldout_score_sparse(ppca_ctx *ctx, ppca_sparse *train, ppca_sparse *held, const ppca_model *model, double *totals_host,
+                              double *col_sums_host, double *per_row);
 
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every

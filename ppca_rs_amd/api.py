@@ -430,7 +430,9 @@ class SparseDataset:
     `SparseDataset(indptr, indices, values, n_columns, weights=None)`: indptr (N + 1, monotone from 0 to nnz), indices (nnz, strictly
     increasing within a row, in [0, n_columns)), values (nnz, finite).  Anything else raises ValueError before the library is touched.
     block_rows / segment: the two tiling lengths of the passes (None: the library's defaults; tests put the seams at small sizes).
-    The entries go to the device, with the inverted index the statistics pass reads, on first use."""
+    The entries go to the device, with the inverted index the statistics pass reads, on first use.
+    `holdout` / `holdout_range` / `kfold` split the entries on the host exactly as Dataset's split the same matrix, and
+    PPCAModel.heldout_score takes the two parts."""
 
     def __init__(self, indptr, indices, values, n_columns: int, weights=None, *, ctx=None, block_rows: Optional[int] = None,
                  segment: Optional[int] = None):
@@ -513,7 +515,7 @@ class SparseDataset:
     def _h(self):
         # every pass written for the dense layout reaches its dataset through _h
         raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
-                        "predict and PPCATrainer are")
+                        "predict / heldout_score and PPCATrainer are")
 
     @property
     def _sh(self):
@@ -569,6 +571,59 @@ class SparseDataset:
         if len(self) == 0:
             return []
         return np.flatnonzero(np.bincount(self._indices, minlength=self._d) == 0).tolist()
+
+    # -- hold-out splits ---------------------------------------
+    def _select(self, keep: np.ndarray) -> "SparseDataset":
+        """The entries flagged in `keep` (bool, nnz) as a SparseDataset with this one's weights, n_columns, ctx and tiling; values keep
+        their bits.  No device work: the part uploads on first use."""
+        out = SparseDataset.__new__(SparseDataset)
+        out.__dict__.update(self.__dict__)
+        out._handle = None
+        out._indptr = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])[self._indptr]
+        out._indices, out._values = self._indices[keep], self._values[keep]
+        for a in (out._indptr, out._indices, out._values):
+            a.setflags(write=False)
+        return out
+
+    def _split(self, lo: float, hi: float, seed: Optional[int], row_offset: int):
+        """The call of ppca_heldout_split_csr_host (host code) and the two parts."""
+        if row_offset < 0:
+            raise ValueError("row_offset must be >= 0")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        flags, counts = np.zeros(self.nnz, dtype=np.uint8), np.zeros(2, dtype=np.int64)
+        check(lib().ppca_heldout_split_csr_host(len(self), ptr(self._indptr), ptr(self._indices), float(lo), float(hi),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), ptr(flags), ptr(counts)))
+        held = flags.view(np.bool_)
+        train, heldp = self._select(~held), self._select(held)
+        train.holdout_counts = heldp.holdout_counts = (int(counts[0]), int(counts[1]))
+        return train, heldp
+
+    def holdout(self, fraction: float, seed: Optional[int] = None, *, row_offset: int = 0):
+        """(train, held): Dataset.holdout on row-compressed data.  Every entry is held with probability `fraction`, decided by the
+        same word of the counter-based generator, keyed by (seed, row_offset + row, column): SparseDataset.from_dense(x).holdout(f, s)
+        holds exactly the entries Dataset(x).holdout(f, s) holds.  Both parts are SparseDatasets with this one's weights, n_columns
+        and tiling; the split is host work and touches no device.  seed=None draws a fresh seed.
+        train.holdout_counts = held.holdout_counts = (entries kept, entries held)."""
+        if not 0.0 <= float(fraction) <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError("fraction must lie in [0, 1]")
+        return self._split(0.0, fraction, seed, row_offset)
+
+    def holdout_range(self, lo: float, hi: float, seed: Optional[int] = None, *, row_offset: int = 0):
+        """`holdout` with the held entries those whose uniform u lies in [lo, hi) (Dataset.holdout_range).  Requires 0 <= lo <= hi <= 1."""
+        if not 0.0 <= float(lo) <= float(hi) <= 1.0:  # (NaN fails the comparisons)
+            raise ValueError("the range must satisfy 0 <= lo <= hi <= 1")
+        return self._split(lo, hi, seed, row_offset)
+
+    fold_edges = staticmethod(Dataset.fold_edges)
+
+    def kfold(self, n_folds: int, seed: Optional[int] = None, *, row_offset: int = 0):
+        """The n_folds (train, held) pairs of entry-wise K-fold cross-validation (Dataset.kfold): every entry is held in exactly one
+        fold.  seed=None draws one fresh seed for all of them."""
+        edges = Dataset.fold_edges(n_folds)
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        return [self.holdout_range(lo, hi, seed, row_offset=row_offset) for lo, hi in zip(edges, edges[1:])]
 
     def index_build_seconds(self) -> float:
         """Host time the constructor of the device copy spent on the inverted index, the row lists and the work items."""
@@ -1091,7 +1146,19 @@ class PPCAModel:
     def heldout_score(self, train: Dataset, held: Dataset) -> "HeldOutScore":
         """How this model predicts the finite entries of `held` from the rows of `train` (the two parts of Dataset.holdout; any two
         datasets of one shape will do): per entry the predictive N(mean_j + c_j^T z, sigma^2 + c_j^T Sigma c_j) of a new reading
-        of column j under the row's posterior (z, Sigma) given `train`.  One GPU pass over each dataset; no N x d output."""
+        of column j under the row's posterior (z, Sigma) given `train`.  One GPU pass over each dataset; no N x d output.
+        Two SparseDatasets (the parts of SparseDataset.holdout) are scored the same way from their entry lists; they
+        need one block_rows.  A Dataset with a SparseDataset raises TypeError."""
+        sparse = isinstance(train, SparseDataset), isinstance(held, SparseDataset)
+        if sparse[0] != sparse[1]:
+            raise TypeError("heldout_score takes two Datasets or two SparseDatasets, not one of each")
+        if sparse[0]:  # (the checks come before the first touch of a device)
+            if len(train) == len(held) and train._d == held._d and train._block_rows != held._block_rows:
+                raise ValueError(f"the train part is tiled with block_rows={train._block_rows or None} and the held part with "
+                                 f"block_rows={held._block_rows or None}: the score walks both block by block, so build them with one "
+                                 "block_rows tiling")
+            return _heldout_call(train, held, lambda t, c, r: lib().ppca_heldout_score_sparse(
+                train._ctx.handle, train._sh, held._sh, self._device(train._ctx).h, t, c, r))
         ctx = train._ctx
         return _heldout_call(train, held, lambda t, c, r: lib().ppca_heldout_score(ctx.handle, train._h, held._h, self._device(ctx).h,
                                                                                   t, c, r))
@@ -1381,7 +1448,10 @@ def heldout_score(model, train: Dataset, held: Dataset, precisions=None, held_pr
     """The held-out score of a model of ANY family on one split, so that families are compared on identical held entries:
     model.heldout_score(train, held) for PPCAModel, PPCAMix, FAModel and FAMix; TPPCAModel.score_heldout(train, held) (the t
     predictive); HPPCAModel.score_heldout(train, held, precisions, held_precisions) (an entry at its own noise level).  `precisions`
-    are required for an HPPCAModel and refused for every other family."""
+    are required for an HPPCAModel and refused for every other family.  Two SparseDatasets are scored by a PPCAModel only."""
+    if (isinstance(train, SparseDataset) or isinstance(held, SparseDataset)) and not isinstance(model, PPCAModel):
+        raise TypeError(f"{type(model).__name__} does not score a SparseDataset: on row-compressed data only PPCAModel.heldout_score exists "
+                        "(DESIGN.md section 7)")
     if isinstance(model, HPPCAModel):
         if precisions is None:
             raise ValueError("an HPPCAModel is scored under precisions")
@@ -1418,7 +1488,10 @@ def cross_validate(dataset: Dataset, fit, *, folds: int = 5, seed: Optional[int]
     model = fit(train) -- fit(train, precisions) when `precisions` (a Dataset or an array of the dataset's shape) is given -- and
     heldout_score(model, train, held[, precisions]).  Returns (the folds' scores, HeldOutScore.pooled of them, the folds' models).
     The folds depend on (seed, shape) alone, so fits of different families with the same seed are compared on identical held
-    entries.  `fit` may return the model or a tuple that starts with it (HPPCATrainer.train's (model, metrics))."""
+    entries.  `fit` may return the model or a tuple that starts with it (HPPCATrainer.train's (model, metrics)).  `dataset` may be a
+    SparseDataset (the folds of SparseDataset.kfold, PPCAModel fits; no precisions)."""
+    if isinstance(dataset, SparseDataset) and precisions is not None:
+        raise ValueError("precisions are not available with a SparseDataset: the known-precision model takes a dense Dataset")
     if precisions is not None and not isinstance(precisions, Dataset):
         p = np.ascontiguousarray(precisions, dtype=np.float64)
         if p.shape != (len(dataset), dataset._d):
@@ -1486,7 +1559,8 @@ class PPCATrainer:
         """Entry-wise cross-validation of the state size: one Dataset.holdout(fraction, seed), then for every size one `train` on the
         train part (quiet; model seed = `seed`) and one `heldout_score`.  Returns [(state_size, HeldOutScore, PPCAModel)]: choose the
         size whose score.mean_llk is largest.  folds > 1: the split is Dataset.kfold(folds, seed) instead (`fraction` is not used),
-        one fit per size and fold; the score is the pooled one and the third element the list of the folds' models."""
+        one fit per size and fold; the score is the pooled one and the third element the list of the folds' models.  On a
+        SparseDataset the split is SparseDataset.holdout / kfold (the same entries as the dense split) and init="pca" raises."""
         return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: PPCATrainer(tr).train(
             state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init, prior=prior), folds)
 

@@ -26,6 +26,20 @@
 //     entry's record from scratch with one coalesced read per group.  A whole column adds its sum to the statistics (the blocks run one
 //     after the other on the stream: block order); a run writes its partial, and sparse_fix_kernel adds a column's runs in run order.
 // sparse_predict_kernel mean_j + c_j . z_i and c_j^T Sigma_i c_j + sigma^2 per query entry from the states / covariances of the block.
+//
+// Held-out scoring (ppca_heldout_split_csr_host, ppca_heldout_score_sparse).  The split is host code: entry
+// (g, j) draws the word of the dense split (ppca_heldout.hip) and is flagged held iff lo <= u < hi.  The score takes two datasets of
+// equal n, d and block_rows, so that block b of `train` and block b of `held` cover the same rows.  Per block: sparse_row_kernel<K>
+// writes z and Sigma of train's rows to scratch, then
+// sparse_held_row_kernel<K>  runs over held's CSR with held's row lists and the groups of the row pass (W = 4 / 16 / 64 by the HELD
+//     row's length).  Lane s takes the row's held entries s, s + W, ..., computes l of each (held_entry<K>: m, v by the k^2
+//     multiply-adds of sparse_predict_kernel, in its order) and adds them in that order; one butterfly adds the lanes.  per_row of a
+//     row depends on its train entry list (z, Sigma) and its held entry list alone.
+// sparse_held_col_kernel<K>  runs over held's inverted index and work items.  An item belongs to a group of 16 lanes; lane s takes
+//     the entries s, s + 16, ... of the item (ascending row), recomputes (m, v) from the row's (z, Sigma) with the same held_entry<K>
+//     and forms [w | w l | w e^2 | w e^2 / v] (w: train's weight of the row).  Each chunk of 16 entries is added by one butterfly and
+//     the chunks in order: a sum is a fixed function of the item's entry list.  A whole column adds into the 4 x d sums (blocks in
+//     stream order); a run writes a partial and sparse_held_fix_kernel adds a column's runs in run order.  No float atomics.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -34,6 +48,7 @@
 #include <vector>
 
 #include "ppca_handles.hpp"
+#include "ppca_sweep.hpp"
 
 using namespace ppca;
 using namespace ppca_host;
@@ -64,7 +79,7 @@ struct SpBlock {
 };
 
 struct SpCore {
-    int64_t n = 0, nnz = 0, block_rows = 0, max_rows = 0, max_runs = 0;
+    int64_t n = 0, nnz = 0, block_rows = 0, max_rows = 0, max_runs = 0, nonempty_rows = 0;
     int d = 0, segment = 0;
     BufRef row_ptr, col, val, trow, tval;
     std::vector<SpBlock> blocks;
@@ -353,6 +368,144 @@ __global__ __launch_bounds__(256) void sparse_predict_kernel(const int64_t *qptr
     }
 }
 
+// ---- held-out scoring
+// One held entry x of column j (cj = c_j, muj = mean_j) in a row whose posterior given `train` is (z, S): e^2, v and l of the new
+// reading.  m and v are sparse_predict_kernel's, multiply-add for multiply-add; l is heldout_score_kernel's expression.
+template <int K>
+__device__ __forceinline__ void held_entry(const double *cj, const double *z, const double *S, double x, double muj, double s2, double &e2,
+                                           double &v, double &l) {
+    double c[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) c[t] = cj[t];
+    double dot = 0.0, q = 0.0;
+    // One row of S at a time, the rows in a rolled loop: unrolled, the compiler keeps all K^2 elements of a row's S in registers across
+    // the entries of sparse_held_row_kernel (512 VGPRs and spills from K = 15 on).
+#pragma unroll 1
+    for (int t = 0; t < K; ++t) {
+        const double ct = cj[t];
+        dot = fma(ct, z[t], dot);
+        double sc = 0.0;
+#pragma unroll
+        for (int u = 0; u < K; ++u) sc = fma(S[t * K + u], c[u], sc);
+        q = fma(ct, sc, q);
+    }
+    const double e = x - (muj + dot);
+    e2 = __dmul_rn(e, e);
+    v = q + s2;
+    l = -0.5 * (LOG_2PI + log(v) + e2 / v);
+}
+
+struct SpHeldRowArgs {
+    const int64_t *row_ptr;  // held's CSR
+    const int32_t *col;
+    const double *val;
+    const int32_t *rows;  // a bin of held's rows, local to the block
+    int64_t nrows, row0;
+    int W, d;
+    const double *model;
+    const double *states, *covs;  // of train's rows, indexed by the row within the block
+    double *per_row;              // indexed by global row
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void sparse_held_row_kernel(SpHeldRowArgs a) {
+    const int lane = threadIdx.x & 63, W = a.W, sub = lane & (W - 1), gpw = 64 / W;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    const double s2 = a.model[1];
+    const double *C = a.model + MODEL_HDR, *mu = C + (int64_t)a.d * K;
+    for (int64_t base = wave * gpw; base < a.nrows; base += nwaves * gpw) {  // (uniform over the wave)
+        const int64_t slot = base + lane / W;
+        const bool live = slot < a.nrows;
+        const int64_t lr = live ? a.rows[slot] : 0, r = a.row0 + lr;
+        const int64_t e0 = live ? a.row_ptr[r] : 0, e1 = live ? a.row_ptr[r + 1] : 0;
+        const double *z = a.states + lr * K, *S = a.covs + lr * (K * K);
+        double lsum = 0.0;
+        for (int64_t e = e0 + sub; e < e1; e += W) {
+            const int j = a.col[e];
+            double e2, v, l;
+            held_entry<K>(C + (int64_t)j * K, z, S, a.val[e], mu[j], s2, e2, v, l);
+            lsum += l;
+        }
+        // the group's lanes, one butterfly: the same tree for every row of the bin
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1)
+            if (o < W) lsum += __shfl_xor(lsum, o, 64);
+        if (live && sub == 0) a.per_row[r] = lsum;
+    }
+}
+
+constexpr int SP_HELD_GW = 16;  // lanes of an item's group in sparse_held_col_kernel
+constexpr int SP_HELD_NO = 4;   // sums per column: w | w l | w e^2 | w e^2 / v
+
+struct SpHeldColArgs {
+    const SpItem *items;  // held's work items, inverted index
+    int64_t n_items;
+    const int32_t *trow;
+    const double *tval;
+    const double *w;  // train's weights (nullable), indexed by global row
+    int64_t row0;
+    const double *states, *covs;  // of train's rows, indexed by the row within the block
+    const double *model;
+    int d;
+    double *colsum;  // 4 x d
+    double *runpart;
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void sparse_held_col_kernel(SpHeldColArgs a) {
+    constexpr int GW = SP_HELD_GW, GPW = 64 / GW;
+    const int lane = threadIdx.x & 63, sub = lane & (GW - 1);
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    const double s2 = a.model[1];
+    const double *C = a.model + MODEL_HDR, *mu = C + (int64_t)a.d * K;
+    for (int64_t base = wave * GPW; base < a.n_items; base += nwaves * GPW) {  // (uniform over the wave)
+        const int64_t ii = base + lane / GW;
+        const bool live = ii < a.n_items;
+        const SpItem it = live ? a.items[ii] : SpItem{0, -1, 0, 0};
+        const double *cj = C + (int64_t)it.col * K;
+        const double muj = mu[it.col];
+        double acc[SP_HELD_NO] = {0.0, 0.0, 0.0, 0.0};
+        for (int t = 0; t < it.len; t += GW) {  // (uniform over the group) one chunk of GW entries, ascending row
+            double p[SP_HELD_NO] = {0.0, 0.0, 0.0, 0.0};  // (past the end: exact zeros, which change no sum)
+            if (t + sub < it.len) {
+                const int64_t li = a.trow[it.start + t + sub];
+                const double w = a.w ? a.w[a.row0 + li] : 1.0;
+                double e2, v, l;
+                held_entry<K>(cj, a.states + li * K, a.covs + li * (K * K), a.tval[it.start + t + sub], muj, s2, e2, v, l);
+                p[0] = w;
+                p[1] = w * l;
+                p[2] = w * e2;
+                p[3] = w * (e2 / v);
+            }
+#pragma unroll
+            for (int o = 1; o < GW; o <<= 1)
+#pragma unroll
+                for (int q = 0; q < SP_HELD_NO; ++q) p[q] += __shfl_xor(p[q], o, 64);
+#pragma unroll
+            for (int q = 0; q < SP_HELD_NO; ++q) acc[q] += p[q];
+        }
+        if (live && sub < SP_HELD_NO) {
+            const double s = sub == 0 ? acc[0] : sub == 1 ? acc[1] : sub == 2 ? acc[2] : acc[3];
+            if (it.dest < 0)
+                a.colsum[(int64_t)sub * a.d + it.col] += s;
+            else
+                a.runpart[it.dest * SP_HELD_NO + sub] = s;
+        }
+    }
+}
+
+// column sums of a long column += its runs' partials, added in run order: one thread per (column, sum)
+__global__ __launch_bounds__(256) void sparse_held_fix_kernel(const SpLong *longs, int64_t n_long, const double *runpart, int d, double *colsum) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_long * SP_HELD_NO; t += stride) {
+        const SpLong lc = longs[t / SP_HELD_NO];
+        const int q = (int)(t % SP_HELD_NO);
+        double s = 0.0;
+        for (int r = 0; r < lc.nruns; ++r) s += runpart[(lc.first + r) * SP_HELD_NO + q];
+        colsum[(int64_t)q * d + lc.col] += s;
+    }
+}
+
 #define SP_DISPATCH(k, F, ...)                  \
     switch (k) {                                \
         case 1: return F<1>(__VA_ARGS__);       \
@@ -387,6 +540,21 @@ hipError_t col_t(const SpColArgs &a, int n_cu, hipStream_t s) {
     hipLaunchKernelGGL((sparse_col_kernel<K>), dim3((unsigned)grid), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+template <int K>
+hipError_t held_row_t(const SpHeldRowArgs &a, int grid, hipStream_t s) {
+    hipLaunchKernelGGL((sparse_held_row_kernel<K>), dim3((unsigned)grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+template <int K>
+hipError_t held_col_t(const SpHeldColArgs &a, int n_cu, hipStream_t s) {
+    constexpr int per_wg = 4 * (64 / SP_HELD_GW);
+    const int64_t want = (a.n_items + per_wg - 1) / per_wg;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)std::max(n_cu, 1) * 8));
+    hipLaunchKernelGGL((sparse_held_col_kernel<K>), dim3((unsigned)grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_held_row(int k, const SpHeldRowArgs &a, int grid, hipStream_t s) { SP_DISPATCH(k, held_row_t, a, grid, s); }
+hipError_t launch_held_col(int k, const SpHeldColArgs &a, int n_cu, hipStream_t s) { SP_DISPATCH(k, held_col_t, a, n_cu, s); }
 hipError_t launch_row(int k, const SpRowArgs &a, int grid, hipStream_t s) { SP_DISPATCH(k, row_t, a, grid, s); }
 hipError_t launch_col(int k, const SpColArgs &a, int n_cu, hipStream_t s) { SP_DISPATCH(k, col_t, a, n_cu, s); }
 
@@ -608,6 +776,7 @@ extern "C" int ppca_sparse_from_host(ppca_ctx *ctx, int64_t n, int32_t d, const 
         core->blocks.push_back(b);
         hb.push_back(std::move(h));
     }
+    for (int64_t i = 0; i < n; ++i) core->nonempty_rows += row_ptr[i + 1] > row_ptr[i] ? 1 : 0;
     core->build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     auto sp = std::make_unique<ppca_sparse>();
     sp->ctx = ctx;
@@ -819,5 +988,116 @@ extern "C" int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_mo
     const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's buffers)
     if (rc) return rc;
     if (e != hipSuccess) return fail(PPCA_ERR_HIP, "predict failed: %s", hipGetErrorString(e));
+    return PPCA_OK;
+}
+
+// ------------------------------------------------------------------ held-out scoring
+extern "C" int ppca_heldout_split_csr_host(int64_t n, const int64_t *row_ptr, const int32_t *col, double lo, double hi, uint64_t seed,
+                                           int64_t row_offset, uint8_t *held_flag_out, int64_t *counts_out) {
+    if (n < 0 || !row_ptr) return fail(PPCA_ERR_INVALID, "bad shape or null row_ptr");
+    if (!(lo >= 0.0 && lo <= hi && hi <= 1.0)) return fail(PPCA_ERR_INVALID, "the range must satisfy 0 <= lo <= hi <= 1");
+    if (row_offset < 0) return fail(PPCA_ERR_INVALID, "row_offset must be >= 0");
+    if (row_ptr[0] != 0) return fail(PPCA_ERR_INVALID, "row_ptr must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (row_ptr[i + 1] < row_ptr[i]) return fail(PPCA_ERR_INVALID, "row_ptr is not monotone at row %lld", (long long)i);
+    if (row_ptr[n] > 0 && (!col || !held_flag_out)) return fail(PPCA_ERR_INVALID, "null col or output");
+    int64_t held = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t key = row_key(seed, STREAM_HOLDOUT, (uint64_t)(row_offset + i));
+        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            if (col[e] < 0) return fail(PPCA_ERR_INVALID, "column %d of row %lld is negative", col[e], (long long)i);
+            const double u = u01_floor(row_word(key, (uint64_t)col[e]));
+            const bool hold = u >= lo && u < hi;
+            held_flag_out[e] = hold ? 1 : 0;
+            held += hold ? 1 : 0;
+        }
+    }
+    if (counts_out) {
+        counts_out[0] = row_ptr[n] - held;
+        counts_out[1] = held;
+    }
+    return PPCA_OK;
+}
+
+extern "C" int ppca_heldout_score_sparse(ppca_ctx *ctx, ppca_sparse *train, ppca_sparse *held, const ppca_model *model, double *totals_host,
+                                         double *col_sums_host, double *per_row) {
+    if (!held || !totals_host) return fail(PPCA_ERR_INVALID, "null argument");
+    if (int rc = sp_check(ctx, train, model)) return rc;
+    const SpCore &tc = *train->core, &hc = *held->core;
+    if (tc.n != hc.n || tc.d != hc.d)
+        return fail(PPCA_ERR_INVALID, "the train part (%lld x %d) and the held part (%lld x %d) differ in shape", (long long)tc.n, tc.d,
+                    (long long)hc.n, hc.d);
+    if (train->ctx->device != held->ctx->device) return fail(PPCA_ERR_INVALID, "the two datasets live on different devices");
+    if (tc.block_rows != hc.block_rows)
+        return fail(PPCA_ERR_INVALID, "the train part is tiled in blocks of %lld rows and the held part in blocks of %lld: build both with one "
+                    "block_rows", (long long)tc.block_rows, (long long)hc.block_rows);
+    USE_CTX(ctx);
+    const int k = model->k, d = tc.d;
+    const int64_t n = tc.n;
+    static const int widths[3] = {4, 16, 64};
+    BufRef st, cv, rows, sums, runpart;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)tc.max_rows * k, &st)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)tc.max_rows * k * k, &cv)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)n, &rows)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)SP_HELD_NO * d, &sums)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)std::max<int64_t>(hc.max_runs, 1) * SP_HELD_NO, &runpart)) return rc;
+    double *stp = static_cast<double *>(st->p), *cvp = static_cast<double *>(cv->p), *rowv = static_cast<double *>(rows->p);
+    double *colsum = static_cast<double *>(sums->p);
+    HIP_TRY(hipMemsetAsync(rowv, 0, sizeof(double) * (size_t)n, ctx->stream));
+    HIP_TRY(hipMemsetAsync(colsum, 0, sizeof(double) * (size_t)SP_HELD_NO * d, ctx->stream));
+    for (size_t bi = 0; bi < hc.blocks.size(); ++bi) {
+        const SpBlock &tb = tc.blocks[bi], &hb = hc.blocks[bi];  // (the same rows: equal n and block_rows)
+        if (hb.nnz == 0) continue;                               // nothing held in these rows: their scores stay 0
+        if (int rc = sp_rows_of_block(ctx, train, tb, model, nullptr, stp, cvp, nullptr, nullptr)) return rc;
+        for (int bin = 0; bin < 3; ++bin) {
+            if (hb.nbin[bin] == 0) continue;
+            SpHeldRowArgs a{};
+            a.row_ptr = static_cast<const int64_t *>(hc.row_ptr->p);
+            a.col = static_cast<const int32_t *>(hc.col->p);
+            a.val = static_cast<const double *>(hc.val->p);
+            a.rows = static_cast<const int32_t *>(hb.rowlist->p) + hb.bin_off[bin];
+            a.nrows = hb.nbin[bin];
+            a.row0 = hb.row0;
+            a.W = widths[bin];
+            a.d = d;
+            a.model = model->p();
+            a.states = stp;
+            a.covs = cvp;
+            a.per_row = rowv;
+            HIP_TRY(launch_held_row(k, a, sp_row_grid(a.nrows, a.W, ctx->n_cu), ctx->stream));
+        }
+        SpHeldColArgs a{};
+        a.items = static_cast<const SpItem *>(hb.items->p);
+        a.n_items = hb.n_items;
+        a.trow = static_cast<const int32_t *>(hc.trow->p);
+        a.tval = static_cast<const double *>(hc.tval->p);
+        a.w = train->w;
+        a.row0 = hb.row0;
+        a.states = stp;
+        a.covs = cvp;
+        a.model = model->p();
+        a.d = d;
+        a.colsum = colsum;
+        a.runpart = static_cast<double *>(runpart->p);
+        HIP_TRY(launch_held_col(k, a, ctx->n_cu, ctx->stream));
+        if (hb.n_long > 0) {
+            const int grid = (int)std::min<int64_t>((hb.n_long * SP_HELD_NO + 255) / 256, (int64_t)std::max(ctx->n_cu, 1) * 8);
+            hipLaunchKernelGGL(sparse_held_fix_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream,
+                               static_cast<const SpLong *>(hb.longs->p), hb.n_long, static_cast<const double *>(runpart->p), d, colsum);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    std::vector<double> cs((size_t)SP_HELD_NO * d);
+    HIP_TRY(hipMemcpyAsync(cs.data(), colsum, sizeof(double) * cs.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (per_row) HIP_TRY(hipMemcpyAsync(per_row, rowv, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < SP_HELD_NO; ++q) {  // the column sums added in index order, as ppca_heldout_score's totals
+        double s = 0.0;
+        for (int j = 0; j < d; ++j) s += cs[(size_t)q * d + j];
+        totals_host[q] = s;
+    }
+    totals_host[4] = (double)hc.nnz;
+    totals_host[5] = (double)hc.nonempty_rows;
+    if (col_sums_host) std::memcpy(col_sums_host, cs.data(), sizeof(double) * cs.size());
     return PPCA_OK;
 }

@@ -12,7 +12,8 @@ namespace ppca {
 
 // ------------------------------------------------------------------ the generator
 // Every stream of the library: draws are keyed by (seed, stream, global row, index), and two streams never meet as long as every id
-// is given out here.
+// is given out here.  smix64, row_key, row_word and u01_floor are host code too: the host-side split of row-compressed data
+// (ppca_sparse.hip, ppca_heldout_split_csr_host) draws the words of holdout_kernel.
 enum RngStream : uint64_t {
     STREAM_SYNTH_LATENT = 1,  // synthetic data: z
     STREAM_SYNTH_NOISE = 2,   //   the noise of x
@@ -24,20 +25,20 @@ enum RngStream : uint64_t {
     STREAM_HOLDOUT = 8,       // the hold-out split
 };
 
-__device__ __forceinline__ uint64_t smix64(uint64_t x) {  // splitmix64's finaliser
+__host__ __device__ __forceinline__ uint64_t smix64(uint64_t x) {  // splitmix64's finaliser
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
 }
 // once per row and stream
-__device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t stream, uint64_t grow) {
+__host__ __device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t stream, uint64_t grow) {
     return smix64(smix64(seed ^ (stream * 0xD1342543DE82EF95ull)) + grow);
 }
 // word p of a row's stream
-__device__ __forceinline__ uint64_t row_word(uint64_t key, uint64_t p) { return smix64(key + p * 0xA0761D6478BD642Full); }
+__host__ __device__ __forceinline__ uint64_t row_word(uint64_t key, uint64_t p) { return smix64(key + p * 0xA0761D6478BD642Full); }
 // The two uniforms in use, from the top 53 bits of a word.  They are different draws: which one a stream takes is part of it.
-__device__ __forceinline__ double u01_floor(uint64_t w) { return (double)(w >> 11) * (1.0 / 9007199254740992.0); }         // [0, 1)
+__host__ __device__ __forceinline__ double u01_floor(uint64_t w) { return (double)(w >> 11) * (1.0 / 9007199254740992.0); }         // [0, 1)
 __device__ __forceinline__ double u01_open(uint64_t w) { return ((double)(w >> 11) + 0.5) * (1.0 / 9007199254740992.0); }  // (0, 1)
 
 // ------------------------------------------------------------------ 16-byte column pairs

@@ -21,7 +21,8 @@ device-to-device copy of X whose rate prices the traffic floor of the iteration 
 once).  `--heldout` runs ONLY the legs of held-out scoring, in one process, alternating: the device split, the
 score, PPCAModel.loo_llks and the scale pass with output for comparison, and the composition the feature replaces (extrapolate, the
 extrapolated covariance diagonal and both downloads).  `--sparse DENSITY` / `--sparse-rows M [--k2 K2]` run ONLY the legs of
-SparseDataset (see sparse_legs)."""
+SparseDataset (see sparse_legs); with `--sparse-heldout` beside either, ONLY the legs of held-out scoring on that
+data (see sparse_heldout_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -32,19 +33,16 @@ n, d, k = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 ctx = _lib.default_context()
 
 
-def sparse_legs(reps=5):
-    """SparseDataset (DESIGN.md 4.20), in one process, alternating, every repetition timed on its own.  `--sparse DENSITY`: every entry
-    of N x d exists with that probability; the sparse llks / iterate next to PPCAModel.llks / iterate on the same data as a dense
-    Dataset and the device-to-device copy of that array.  `--sparse-rows M`: a shape the dense layout cannot hold -- row lengths
-    log-normal with mean M (long-tailed), columns uniform; the sparse legs alone, at state size K and (with `--k2 K2`) K2, and the host
-    time of the index build.  The data is made on the device (before the dense dataset of the other legs, which this leg never
-    builds).  Floor: per entry 12 B of CSR, 8 k B of C, 12 B of index and 8 (k + k' + 1) B of record gathered; per row the record
-    written once; priced at the copy's rate."""
+def sparse_data():
+    """The data of the SparseDataset legs, made on the device: (torch, device, rows_mode, rows, cols, vals, mask, indptr, nnz).
+    `--sparse DENSITY`: every entry of N x d exists with that probability (mask: the N x d pattern); `--sparse-rows M`: row lengths
+    log-normal with mean M (long-tailed), columns uniform (mask: None).  Values from a true model of state size K with noise 0.5."""
     import torch
 
     dev = "cuda"
     torch.manual_seed(11)
     rows_mode = "--sparse-rows" in sys.argv
+    mask = None
     kt = k
     ct = torch.randn((d, kt), dtype=torch.float64, device=dev)
     mt = torch.randn(d, dtype=torch.float64, device=dev)
@@ -74,6 +72,19 @@ def sparse_legs(reps=5):
     lens = np.diff(indptr)
     print(f"SparseDataset legs: N = {n}, d = {d}, nnz = {nnz} ({nnz / n / d:.4%} of N x d; {nnz / n:.1f} per row, median {np.median(lens):.0f}, "
           f"max {lens.max()}); dense form {8.0 * n * d / 1e9:.1f} GB", flush=True)
+    del zt
+    return torch, dev, rows_mode, rows, cols, vals, mask, indptr, nnz
+
+
+def sparse_legs(reps=5):
+    """SparseDataset (DESIGN.md 4.20), in one process, alternating, every repetition timed on its own.  `--sparse DENSITY`: every entry
+    of N x d exists with that probability; the sparse llks / iterate next to PPCAModel.llks / iterate on the same data as a dense
+    Dataset and the device-to-device copy of that array.  `--sparse-rows M`: a shape the dense layout cannot hold -- row lengths
+    log-normal with mean M (long-tailed), columns uniform; the sparse legs alone, at state size K and (with `--k2 K2`) K2, and the host
+    time of the index build.  The data is made on the device (before the dense dataset of the other legs, which this leg never
+    builds).  Floor: per entry 12 B of CSR, 8 k B of C, 12 B of index and 8 (k + k' + 1) B of record gathered; per row the record
+    written once; priced at the copy's rate."""
+    torch, dev, rows_mode, rows, cols, vals, mask, indptr, nnz = sparse_data()
     t0 = time.perf_counter()
     sp = P.SparseDataset(indptr, cols.int().cpu().numpy(), vals.cpu().numpy(), d, ctx=ctx)
     sp._sh
@@ -104,7 +115,7 @@ def sparse_legs(reps=5):
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     hip.hipDeviceSynchronize.argtypes = []
     if rows_mode:
-        del rows, cols, vals, zt
+        del rows, cols, vals
         nbytes = 1 << 32
         src, dst = torch.empty(nbytes // 8, dtype=torch.float64, device=dev), torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
         def copy():
@@ -118,7 +129,7 @@ def sparse_legs(reps=5):
     else:
         xd = torch.full((n, d), float("nan"), dtype=torch.float64, device=dev)
         xd[mask] = vals
-        del mask, rows, cols, vals, zt
+        del mask, rows, cols, vals
         torch.cuda.synchronize()
         dense = P.Dataset.from_device(xd.data_ptr(), n, d, ctx=ctx, keepalive=xd)
         spare = torch.empty((n, d), dtype=torch.float64, device=dev)
@@ -148,6 +159,73 @@ def sparse_legs(reps=5):
               f"iterate {med['sparse iterate'] / med['PPCAModel.iterate on to_dense()']:.3f}  (below 1: the sparse path is faster)")
 
 
+def sparse_heldout_legs(reps=5, fraction=0.1):
+    """Held-out scoring of a SparseDataset (`--sparse-heldout` beside `--sparse DENSITY` or `--sparse-rows M`), in one
+    process, alternating, every repetition timed on its own: the host split (SparseDataset.holdout at `fraction`), heldout_score(train,
+    held), sparse llks on train (the same row pass) and the composition the score replaces -- predict(train, held) and the numpy
+    sums by row and by column.  The two device copies (index builds, uploads) are made once, before the timed legs."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    sp = P.SparseDataset(indptr, cols.int().cpu().numpy(), vals.cpu().numpy(), d, ctx=ctx)
+    del cols, vals
+    t0 = time.perf_counter()
+    train, held = sp.holdout(fraction, 5)
+    t_split = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    train._sh, held._sh
+    print(f"  held {held.nnz} of {nnz} entries ({held.nnz / nnz:.4f}); host: first split {t_split:.2f} s, index builds and uploads of the two "
+          f"parts {time.perf_counter() - t0:.2f} s", flush=True)
+    model = P.PPCAModel.init(k, train, seed=3).iterate(train)
+    w = train.weights()
+
+    def composition():
+        mean, var = model.predict(train, held)
+        hp, hc, hv = held._indptr, held._indices, held._values
+        e = hv - mean
+        e2 = e * e
+        z2 = e2 / var
+        l = -0.5 * (np.log(2.0 * np.pi) + np.log(var) + z2)
+        rows = np.repeat(np.arange(n), np.diff(hp))
+        per_row = np.bincount(rows, weights=l, minlength=n)
+        we = w[rows]
+        return per_row, [np.bincount(hc, weights=t, minlength=d) for t in (we, we * l, we * e2, we * z2)]
+
+    def series(fn, r, warm):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    sc = model.heldout_score(train, held)
+    per_row, sums = composition()
+    print(f"  score {sc!r}; against the composition: per row {np.abs(sc.llks - per_row).max():.1e}, llk sum "
+          f"{abs(sc.llk - sums[1].sum()) / abs(sc.llk):.1e} (relative)", flush=True)
+    legs = [("host split (SparseDataset.holdout)", lambda: sp.holdout(fraction, 5), max(2, reps // 2), 0),
+            ("heldout_score(train, held)", lambda: model.heldout_score(train, held), reps, 2),
+            ("sparse llks on train", lambda: model.llks(train), reps, 2),
+            ("predict(train, held) + numpy sums by row and column", composition, reps, 1)]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn, r, warm in legs:
+            got.setdefault(name, []).append(series(fn, r, warm))
+    med = {name: report(name, np.concatenate(got[name])) for name, _, _, _ in legs}
+    s, c_, l_ = med["heldout_score(train, held)"], med["predict(train, held) + numpy sums by row and column"], med["sparse llks on train"]
+    print(f"  score / composition {s / c_:.3f} (below 1: the score is faster);  score / llks {s / l_:.3f}")
+
+
+if "--sparse-heldout" in sys.argv:
+    sparse_heldout_legs()
+    sys.exit(0)
 if "--sparse" in sys.argv or "--sparse-rows" in sys.argv:
     sparse_legs()
     sys.exit(0)
