@@ -547,6 +547,18 @@ int ppca_sparse_infer(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, d
  * value per query entry in query order.  No n x d buffer exists anywhere. */
 int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr, const int32_t *query_col,
                         double *mean_host, double *var_host);
+/* The n_top best columns of every row: the score of column j for row i is mean + kappa sqrt(var) with ppca_sparse_predict's
+ * (mean, var) of position (i, j), evaluated fma(kappa, sqrt(var), mean); kappa = 0 ranks by the mean and reads no covariance.  Ranked
+ * are the candidate columns (candidates: n_candidates strictly increasing columns in [0, d), or NULL = all d) -- with exclude_observed
+ * != 0 those of them the row has no entry in -- by score descending, equal scores by ascending column; a score that is NaN or -inf
+ * is not ranked.  cols_host (int32, n x n_top) and scores_host (fp64, n x n_top), host memory: the row's list, padded at the end with
+ * -1 and NaN where it has fewer than n_top candidates.  Row weights play no part; an empty row ranks with z = 0, Sigma = I; state size 0
+ * runs as one zero column (the score is mean_j).  The scores are ppca_sparse_predict's bit for bit and the order is total: the result
+ * is bit-identical under any grid limit and block_rows.  No n x d buffer and no float atomics.
+ * Preconditions, all checked before any device work: 1 <= n_top <= 64, kappa finite, candidates as above (else PPCA_ERR_INVALID);
+ * k <= 16 (else PPCA_ERR_UNSUPPORTED); n = 0: PPCA_ERR_EMPTY.  (Named with the family first, like ppca_heldout_score_sparse.) */
+int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, int32_t n_top, double kappa, int32_t exclude_observed,
+                     const int32_t *candidates, int64_t n_candidates, int32_t *cols_host, double *scores_host);
 /* The hold-out split of ppca_dataset_holdout_range on the pattern of row-compressed data, on host buffers (no GPU needed; DESIGN.md
  * 4.21).  row_ptr (n + 1, from 0, monotone) and col (>= 0) as above.  Entry e of row i, column j = col[e], global row
  * g = row_offset + i draws the word of the dense split, u = (row_word(row_key(seed, 8, g), j) >> 11) 2^-53, and

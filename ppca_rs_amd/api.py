@@ -1087,6 +1087,46 @@ class PPCAModel:
         check(lib().ppca_sparse_predict(ctx.handle, sparse._sh, self._device(ctx).h, ptr(ip), ptr(ix), ptr(mean), ptr(var)))
         return mean, var
 
+    def recommend(self, sparse: "SparseDataset", n: int, *, kappa: float = 0.0, exclude_observed: bool = True, candidates=None):
+        """For every row of row-compressed data the n columns the model ranks highest, in one device pass.  The score
+        of column j for row i is mean_ij + kappa sqrt(var_ij) with exactly `predict`'s two values: kappa = 0 ranks by the predictive
+        mean, kappa > 0 by an upper confidence bound (exploration), kappa < 0 by a lower one.  Ranked are the row's candidate columns
+        -- `candidates` (a strictly increasing int array of columns, e.g. the items in stock; None: all), without the columns the row has
+        an entry in unless exclude_observed=False -- by score descending, equal scores by ascending column.  Returns (columns int32
+        (N, n), scores float64 (N, n)); a row with fewer than n candidates is padded at the end with -1 and NaN.  1 <= n <= 64.  Row
+        weights play no part, an empty row ranks with z = 0, Sigma = I, and no N x d array is formed.  Rows are independent: a shard
+        calls this on its own rows."""
+        if not isinstance(sparse, SparseDataset):
+            raise TypeError("recommend takes a SparseDataset (from a Dataset or an array: SparseDataset.from_dense)")
+        n = int(n)
+        if not 1 <= n <= 64:
+            raise ValueError("n must lie in [1, 64]")
+        kappa = float(kappa)
+        if not math.isfinite(kappa):
+            raise ValueError("kappa must be finite")
+        cand = None
+        if candidates is not None:
+            cand = np.asarray(candidates)
+            if cand.ndim != 1 or (cand.size and not np.issubdtype(cand.dtype, np.integer)):
+                raise ValueError("candidates must be a 1-D integer array")
+            if cand.size and (cand.min() < 0 or cand.max() >= sparse._d):
+                raise ValueError(f"a candidate column lies outside [0, {sparse._d})")
+            if np.any(np.diff(cand) <= 0):
+                raise ValueError("candidates must be strictly increasing (sorted, no duplicates)")
+            cand = np.ascontiguousarray(cand, dtype=np.int32)
+        if self.output_size != sparse._d:
+            raise ValueError(f"dataset has {sparse._d} columns but the model has output size {self.output_size}")
+        if self.state_size > 16:  # (the library's own answer, given here so that it comes before the first touch of a device)
+            raise _lib.PPCAError(-3, f"state size {self.state_size} is not supported on sparse data: the kernels cover k <= 16")
+        cols, scores = np.empty((len(sparse), n), dtype=np.int32), np.empty((len(sparse), n))
+        if len(sparse) == 0:
+            return cols, scores
+        ctx = sparse._ctx
+        cbuf = cand if cand is None or cand.size else np.zeros(1, dtype=np.int32)  # (an empty list is not NULL = every column)
+        check(lib().ppca_topn_sparse(ctx.handle, sparse._sh, self._device(ctx).h, n, kappa, 1 if exclude_observed else 0, ptr(cbuf),
+                                     0 if cand is None else cand.size, ptr(cols), ptr(scores)))
+        return cols, scores
+
     def _recon(self, dataset: Dataset, mode: int, fn) -> Dataset:
         if isinstance(dataset, SparseDataset):
             raise TypeError("smooth / extrapolate would write an N x d output, which is what a SparseDataset exists to avoid: use "

@@ -40,8 +40,16 @@
 //     and forms [w | w l | w e^2 | w e^2 / v] (w: train's weight of the row).  Each chunk of 16 entries is added by one butterfly and
 //     the chunks in order: a sum is a fixed function of the item's entry list.  A whole column adds into the 4 x d sums (blocks in
 //     stream order); a run writes a partial and sparse_held_fix_kernel adds a column's runs in run order.  No float atomics.
+//
+// Top-n ranking (ppca_topn_sparse).  Per block: sparse_row_kernel<K> writes z (and Sigma when kappa != 0), then
+// sparse_topn_kernel<K, VAR, R>  a wave takes a tile of R rows and a chunk of candidate positions and walks the chunk 64 at a time: a
+//     lane holds c_j and mean_j of one column, z and Sigma of a row are wave-uniform, the score is sparse_predict_kernel's (mean, var)
+//     multiply-add for multiply-add, and a row's list of n <= 64 (score, column) is held one entry per lane behind a wave-uniform
+//     threshold.  The order (score descending, column ascending) is total, so the result depends on nothing else.
+// sparse_topn_merge_kernel  when the columns were split into chunks: one wave per row offers the row's chunk lists in chunk order.
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -506,6 +514,212 @@ __global__ __launch_bounds__(256) void sparse_held_fix_kernel(const SpLong *long
     }
 }
 
+// ---- top-n ranking
+constexpr int SP_TOP_MAX = 64;           // n_top: a row's list is held one entry per lane
+constexpr int SP_TOP_R = 16;             // rows of a wave's tile when the score is the mean ...
+constexpr int SP_TOP_RV = 4;             // ... and when it needs the variance (k^2 multiply-adds per score)
+constexpr int SP_TOP_MINCHUNK = 1024;    // fewest candidate positions of a column chunk
+
+struct SpTopDims {
+    int64_t row0, rows;  // the block
+    int d, nc;           // columns; candidate positions (d without a candidate list)
+    int chunk, nchunks;  // candidate positions per column chunk (a multiple of 64)
+    int n_top, exclude, final;
+    double kappa;
+};
+
+// v of lane l (l uniform) as a wave-uniform value
+__device__ __forceinline__ double lane_f64(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+// A row's list, entry p on lane p (p < n): score descending, equal scores in ascending column; empty entries (-inf, -1) at the end;
+// thr = the score of entry n - 1.  (s, j) goes in iff s > thr.  The callers offer columns in ascending order, so a score equal to a
+// stored one goes behind it -- and one equal to thr stays out.
+__device__ __forceinline__ void top_insert(double &ls, int &lc, double &thr, double s, int j, int lane, int n) {
+    if (!(s > thr)) return;  // (uniform)
+    const int p = __popcll(__ballot(ls >= s));
+    const double us = __shfl_up(ls, 1, 64);
+    const int uc = __shfl_up(lc, 1, 64);
+    if (lane == p) {
+        ls = s;
+        lc = j;
+    } else if (lane > p && lane < n) {
+        ls = us;
+        lc = uc;
+    }
+    thr = lane_f64(ls, n - 1);
+}
+
+// The row's own columns, for exclude_observed: a window of 64 of its m sorted CSR columns is kept in a register, lane l of rc =
+// col[e0 + w + l] (INT_MAX past the row's end), w a multiple of 64.  Columns are offered in ascending order, so the window only moves
+// forward: a row of at most 64 entries is read once per work item, a longer one at most m / 64 times.
+__device__ __forceinline__ int top_window(const int32_t *col, int64_t e0, int m, int w, int lane) {
+    return w + lane < m ? col[e0 + w + lane] : INT_MAX;
+}
+// the window a chunk that starts at column jstart begins with: the last one whose first column is <= jstart (uniform)
+__device__ __forceinline__ int top_window_start(const int32_t *col, int64_t e0, int m, int jstart) {
+    int lo = 0, hi = (m - 1) / 64;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        if (col[e0 + (int64_t)mid * 64] <= jstart)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo * 64;
+}
+
+// The lanes flagged in `beat` hold a score above the row's threshold (their columns span [jlo, jhi]): drop the columns the row has
+// an entry in, then insert the others in ascending lane = ascending column.
+__device__ __forceinline__ void top_offer(double &ls, int &lc, double &thr, bool beat, double score, int j, bool exclude, int &rc, int &w,
+                                          const int32_t *col, int64_t e0, int m, int lane, int n) {
+    uint64_t bm = __ballot(beat);
+    if (exclude) {
+        const int jlo = __builtin_amdgcn_readlane(j, __builtin_ctzll(bm)), jhi = __builtin_amdgcn_readlane(j, 63 - __builtin_clzll(bm));
+        bool obs = false;
+        for (;;) {  // (uniform)
+            uint64_t in = __ballot(rc >= jlo && rc <= jhi);
+            while (in) {
+                obs |= j == __builtin_amdgcn_readlane(rc, __builtin_ctzll(in));
+                in &= in - 1;
+            }
+            if (w + 64 >= m || __builtin_amdgcn_readlane(rc, 63) > jhi) break;
+            w += 64;
+            rc = top_window(col, e0, m, w, lane);
+        }
+        bm = __ballot(beat && !obs);
+    }
+    while (bm) {  // (uniform)
+        const int l = __builtin_ctzll(bm);
+        bm &= bm - 1;
+        top_insert(ls, lc, thr, lane_f64(score, l), __builtin_amdgcn_readlane(j, l), lane, n);
+    }
+}
+
+// A work item = (tile of R rows, column chunk), one wave each; tiles vary fastest, so the waves of a workgroup read the same rows of C.
+// Lane l holds c_j and mean_j of candidate position base + l for the whole tile; z (and Sigma) of a row are wave-uniform operands.
+// mean and var are sparse_predict_kernel's expressions, multiply-add for multiply-add.  Output: the item's list per row, at
+// [(row * nchunks + chunk) * n_top + p]; with one chunk that is the result (empty entries as -1 / NaN).
+template <int K, bool VAR, int R>
+__global__ __launch_bounds__(256) void sparse_topn_kernel(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
+                                                          const int32_t *__restrict__ cand, const double *__restrict__ model,
+                                                          const double *__restrict__ states, const double *__restrict__ covs,
+                                                          double *__restrict__ ps, int32_t *__restrict__ pc, SpTopDims g) {
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = g.n_top;
+    const int64_t ntiles = (g.rows + R - 1) / R, nitems = ntiles * g.nchunks;
+    const double s2 = model[1];
+    const double *C = model + MODEL_HDR, *mu = C + (int64_t)g.d * K;
+    for (int64_t item = (int64_t)blockIdx.x * 4 + wid; item < nitems; item += (int64_t)gridDim.x * 4) {  // (uniform over the wave)
+        const int ch = (int)(item / ntiles);
+        const int64_t r0 = (item % ntiles) * R;
+        const int nr = (int)(g.rows - r0 < R ? g.rows - r0 : R);
+        double ls[R], thr[R];
+        int lc[R], rc[R], win[R];  // (rc, win: the window of each row's own columns, for exclude_observed)
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            ls[r] = -INFINITY;
+            thr[r] = -INFINITY;
+            lc[r] = -1;
+            rc[r] = INT_MAX;
+            win[r] = 0;
+        }
+        const int64_t p0 = (int64_t)ch * g.chunk, p1 = p0 + g.chunk < g.nc ? p0 + g.chunk : g.nc;
+        if (g.exclude && p0 < p1) {
+            const int jstart = cand ? cand[p0] : (int)p0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= nr) continue;  // (uniform)
+                const int64_t row = g.row0 + r0 + r, e0 = row_ptr[row];
+                const int m = (int)(row_ptr[row + 1] - e0);
+                win[r] = (m > 64 && p0 > 0) ? top_window_start(col, e0, m, jstart) : 0;
+                rc[r] = top_window(col, e0, m, win[r], lane);
+            }
+        }
+        // the tile after the one being ranked is loaded while that one is ranked
+        auto load = [&](int64_t base, bool &valid, int &j, double *c, double &muj) {
+            const int64_t idx = base + lane;
+            valid = idx < p1;
+            j = valid ? (cand ? cand[idx] : (int)idx) : 0;
+            const double *cj = C + (int64_t)j * K;
+#pragma unroll
+            for (int t = 0; t < K; ++t) c[t] = cj[t];
+            muj = mu[j];
+        };
+        bool valid, nvalid = false;
+        int j, nj = 0;
+        double c[K], ncv[K], muj, nmuj = 0.0;
+        if (p0 < p1) load(p0, valid, j, c, muj);
+        for (int64_t base = p0; base < p1; base += 64) {
+            if (base + 64 < p1) load(base + 64, nvalid, nj, ncv, nmuj);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= nr) continue;  // (uniform)
+                const double *z = states + (r0 + r) * K;
+                double dot = 0.0, q = 0.0;
+#pragma unroll
+                for (int t = 0; t < K; ++t) dot = fma(c[t], z[t], dot);
+                double score = muj + dot;
+                if (VAR) {
+                    const double *S = covs + (r0 + r) * (K * K);
+#pragma unroll
+                    for (int t = 0; t < K; ++t) {
+                        double sc = 0.0;
+#pragma unroll
+                        for (int u = 0; u < K; ++u) sc = fma(S[t * K + u], c[u], sc);
+                        q = fma(c[t], sc, q);
+                    }
+                    score = fma(g.kappa, sqrt(q + s2), score);
+                }
+                const bool beat = valid && score > thr[r];
+                if (__ballot(beat)) {
+                    const int64_t row = g.row0 + r0 + r, e0 = row_ptr[row];
+                    top_offer(ls[r], lc[r], thr[r], beat, score, j, g.exclude != 0, rc[r], win[r], col, e0, (int)(row_ptr[row + 1] - e0), lane, n);
+                }
+            }
+            valid = nvalid;
+            j = nj;
+            muj = nmuj;
+#pragma unroll
+            for (int t = 0; t < K; ++t) c[t] = ncv[t];
+        }
+        if (lane < n) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= nr) continue;
+                const int64_t at = ((r0 + r) * g.nchunks + ch) * n + lane;
+                ps[at] = (g.final && lc[r] < 0) ? (double)NAN : ls[r];
+                pc[at] = lc[r];
+            }
+        }
+    }
+}
+
+// One wave per row: the row's chunk lists, offered in chunk order (ascending columns) entry by entry.
+__global__ __launch_bounds__(256) void sparse_topn_merge_kernel(const double *__restrict__ ps, const int32_t *__restrict__ pc, int64_t rows,
+                                                                int nchunks, int n, double *__restrict__ os, int32_t *__restrict__ oc) {
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows; row += (int64_t)gridDim.x * 4) {  // (uniform over the wave)
+        double ls = -INFINITY, thr = -INFINITY;
+        int lc = -1;
+        for (int ch = 0; ch < nchunks; ++ch) {
+            const int64_t at = (row * nchunks + ch) * n + lane;
+            const double s = lane < n ? ps[at] : -INFINITY;
+            const int j = lane < n ? pc[at] : -1;
+            for (int p = 0; p < n; ++p) {
+                const double sp = lane_f64(s, p);
+                if (!(sp > thr)) break;  // (uniform; the list is sorted: nothing behind it gets in either)
+                top_insert(ls, lc, thr, sp, __builtin_amdgcn_readlane(j, p), lane, n);
+            }
+        }
+        if (lane < n) {
+            os[row * n + lane] = lc < 0 ? (double)NAN : ls;
+            oc[row * n + lane] = lc;
+        }
+    }
+}
+
+
 #define SP_DISPATCH(k, F, ...)                  \
     switch (k) {                                \
         case 1: return F<1>(__VA_ARGS__);       \
@@ -557,6 +771,30 @@ hipError_t launch_held_row(int k, const SpHeldRowArgs &a, int grid, hipStream_t 
 hipError_t launch_held_col(int k, const SpHeldColArgs &a, int n_cu, hipStream_t s) { SP_DISPATCH(k, held_col_t, a, n_cu, s); }
 hipError_t launch_row(int k, const SpRowArgs &a, int grid, hipStream_t s) { SP_DISPATCH(k, row_t, a, grid, s); }
 hipError_t launch_col(int k, const SpColArgs &a, int n_cu, hipStream_t s) { SP_DISPATCH(k, col_t, a, n_cu, s); }
+struct SpTopPtrs {
+    const int64_t *row_ptr;
+    const int32_t *col, *cand;
+    const double *model, *states, *covs;
+    double *ps;
+    int32_t *pc;
+};
+inline int64_t sp_top_tiles(int64_t rows, bool var) {
+    const int r = var ? SP_TOP_RV : SP_TOP_R;
+    return (rows + r - 1) / r;
+}
+template <int K>
+hipError_t topn_t(const SpTopPtrs &p, const SpTopDims &g, bool var, int n_cu, hipStream_t s) {
+    const int64_t items = sp_top_tiles(g.rows, var) * g.nchunks;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((items + 3) / 4, (int64_t)std::max(n_cu, 1) * 8));
+    if (var)
+        hipLaunchKernelGGL((sparse_topn_kernel<K, true, SP_TOP_RV>), dim3((unsigned)grid), dim3(256), 0, s, p.row_ptr, p.col, p.cand, p.model,
+                           p.states, p.covs, p.ps, p.pc, g);
+    else
+        hipLaunchKernelGGL((sparse_topn_kernel<K, false, SP_TOP_R>), dim3((unsigned)grid), dim3(256), 0, s, p.row_ptr, p.col, p.cand, p.model,
+                           p.states, p.covs, p.ps, p.pc, g);
+    return hipGetLastError();
+}
+hipError_t launch_topn(int k, const SpTopPtrs &p, const SpTopDims &g, bool var, int n_cu, hipStream_t s) { SP_DISPATCH(k, topn_t, p, g, var, n_cu, s); }
 
 // ------------------------------------------------------------------ host: validation and the inverted index
 int sp_validate(int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *col, const double *val) {
@@ -988,6 +1226,101 @@ extern "C" int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_mo
     const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's buffers)
     if (rc) return rc;
     if (e != hipSuccess) return fail(PPCA_ERR_HIP, "predict failed: %s", hipGetErrorString(e));
+    return PPCA_OK;
+}
+
+// ------------------------------------------------------------------ top-n ranking
+extern "C" int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, int32_t n_top, double kappa, int32_t exclude_observed,
+                                const int32_t *candidates, int64_t n_candidates, int32_t *cols_host, double *scores_host) {
+    if (int rc = sp_check(ctx, sp, model)) return rc;
+    const SpCore &c = *sp->core;
+    if (n_top < 1 || n_top > SP_TOP_MAX) return fail(PPCA_ERR_INVALID, "n_top = %d is outside [1, %d]", n_top, SP_TOP_MAX);
+    if (!std::isfinite(kappa)) return fail(PPCA_ERR_INVALID, "kappa must be finite");
+    if (!cols_host || !scores_host) return fail(PPCA_ERR_INVALID, "null output");
+    if (n_candidates < 0 || n_candidates > c.d) return fail(PPCA_ERR_INVALID, "n_candidates = %lld is outside [0, %d]", (long long)n_candidates, c.d);
+    if (candidates)
+        for (int64_t i = 0; i < n_candidates; ++i) {
+            if (candidates[i] < 0 || candidates[i] >= c.d) return fail(PPCA_ERR_INVALID, "candidate column %d is outside [0, %d)", candidates[i], c.d);
+            if (i > 0 && candidates[i] <= candidates[i - 1]) return fail(PPCA_ERR_INVALID, "candidate columns are not strictly increasing at %lld", (long long)i);
+        }
+    USE_CTX(ctx);
+    const int k = model->k, nc = candidates ? (int)n_candidates : c.d;
+    const bool var = kappa != 0.0;
+    // the column split: chunks so that (row tiles) x (chunks) fills the device, none under SP_TOP_MINCHUNK positions.  The order of the
+    // list is total, so the result does not depend on this choice.
+    auto chunks_of = [&](int64_t rows, int *chunk) {
+        const int64_t target = (int64_t)std::max(ctx->n_cu, 1) * 32;
+        int64_t nch = std::max<int64_t>(1, std::min<int64_t>(target / sp_top_tiles(rows, var), nc / SP_TOP_MINCHUNK));
+        const int64_t per = std::max<int64_t>(64, ((nc + nch - 1) / nch + 63) / 64 * 64);
+        *chunk = (int)per;
+        return (int)std::max<int64_t>(1, (nc + per - 1) / per);
+    };
+    int64_t part_len = 0;
+    for (const SpBlock &b : c.blocks) {
+        int chunk;
+        const int nch = chunks_of(b.rows, &chunk);
+        if (nch > 1) part_len = std::max(part_len, b.rows * nch * n_top);
+    }
+    BufRef st, cv, cd, os, oc, ps, pc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * k, &st)) return rc;
+    if (var)
+        if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * k * k, &cv)) return rc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * n_top, &os)) return rc;
+    if (int rc = dev_alloc(sizeof(int32_t) * (size_t)c.max_rows * n_top, &oc)) return rc;
+    if (part_len > 0) {
+        if (int rc = dev_alloc(sizeof(double) * (size_t)part_len, &ps)) return rc;
+        if (int rc = dev_alloc(sizeof(int32_t) * (size_t)part_len, &pc)) return rc;
+    }
+    int rc = PPCA_OK;
+    if (candidates) rc = sp_upload(ctx, candidates, sizeof(int32_t) * (size_t)n_candidates, &cd);
+    for (size_t bi = 0; bi < c.blocks.size() && !rc; ++bi) {
+        const SpBlock &b = c.blocks[bi];
+        rc = sp_rows_of_block(ctx, sp, b, model, nullptr, static_cast<double *>(st->p), var ? static_cast<double *>(cv->p) : nullptr, nullptr,
+                              nullptr);
+        if (rc) break;
+        SpTopDims g{};
+        g.row0 = b.row0;
+        g.rows = b.rows;
+        g.d = c.d;
+        g.nc = nc;
+        g.nchunks = chunks_of(b.rows, &g.chunk);
+        g.n_top = n_top;
+        g.exclude = exclude_observed ? 1 : 0;
+        g.final = g.nchunks == 1;
+        g.kappa = kappa;
+        SpTopPtrs p{};
+        p.row_ptr = static_cast<const int64_t *>(c.row_ptr->p);
+        p.col = static_cast<const int32_t *>(c.col->p);
+        p.cand = candidates ? static_cast<const int32_t *>(cd->p) : nullptr;
+        p.model = model->p();
+        p.states = static_cast<const double *>(st->p);
+        p.covs = var ? static_cast<const double *>(cv->p) : nullptr;
+        p.ps = static_cast<double *>(g.final ? os->p : ps->p);
+        p.pc = static_cast<int32_t *>(g.final ? oc->p : pc->p);
+        if (launch_topn(k, p, g, var, ctx->n_cu, ctx->stream) != hipSuccess) {
+            rc = fail(PPCA_ERR_HIP, "top-n launch failed");
+            break;
+        }
+        if (!g.final) {
+            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((b.rows + 3) / 4, (int64_t)std::max(ctx->n_cu, 1) * 8));
+            hipLaunchKernelGGL(sparse_topn_merge_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, static_cast<const double *>(ps->p),
+                               static_cast<const int32_t *>(pc->p), b.rows, g.nchunks, (int)n_top, static_cast<double *>(os->p),
+                               static_cast<int32_t *>(oc->p));
+            if (hipGetLastError() != hipSuccess) {
+                rc = fail(PPCA_ERR_HIP, "top-n merge launch failed");
+                break;
+            }
+        }
+        if (hipMemcpyAsync(scores_host + b.row0 * n_top, os->p, sizeof(double) * (size_t)b.rows * n_top, hipMemcpyDeviceToHost, ctx->stream) !=
+                hipSuccess ||
+            hipMemcpyAsync(cols_host + b.row0 * n_top, oc->p, sizeof(int32_t) * (size_t)b.rows * n_top, hipMemcpyDeviceToHost, ctx->stream) !=
+                hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)  // (the next block overwrites the scratch)
+            rc = fail(PPCA_ERR_HIP, "top-n failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the upload reads the caller's buffer)
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(PPCA_ERR_HIP, "top-n failed: %s", hipGetErrorString(e));
     return PPCA_OK;
 }
 

@@ -22,7 +22,8 @@ once).  `--heldout` runs ONLY the legs of held-out scoring, in 
 score, PPCAModel.loo_llks and the scale pass with output for comparison, and the composition the feature replaces (extrapolate, the
 extrapolated covariance diagonal and both downloads).  `--sparse DENSITY` / `--sparse-rows M [--k2 K2]` run ONLY the legs of
 SparseDataset (see sparse_legs); with `--sparse-heldout` beside either, ONLY the legs of held-out scoring on that
-data (see sparse_heldout_legs)."""
+data (see sparse_heldout_legs); with `--sparse-topn N_TOP` beside either, ONLY the legs of PPCAModel.recommend on that
+data (see sparse_topn_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -223,6 +224,79 @@ def sparse_heldout_legs(reps=5, fraction=0.1):
     print(f"  score / composition {s / c_:.3f} (below 1: the score is faster);  score / llks {s / l_:.3f}")
 
 
+def sparse_topn_legs(reps=5):
+    """PPCAModel.recommend on a SparseDataset (`--sparse-topn N_TOP [--n2 N2] [--kappa KAPPA] [--slice ROWS] [--reps R]` beside
+    `--sparse DENSITY` or `--sparse-rows M`), in one process, alternating, every repetition timed on its own: sparse llks (the row pass
+    the call shares), recommend at N_TOP (and at N2, and at N_TOP with KAPPA), and what the call replaces -- predict at all positions of
+    a slice of ROWS rows (default: 2^24 positions) and np.argpartition, scaled to N.  Floor (a): N d k multiply-adds (N d (k^2 + 2 k)
+    with kappa) at 78.6 TFLOP/s, plus the llks time."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    sp = P.SparseDataset(indptr, cols.int().cpu().numpy(), vals.cpu().numpy(), d, ctx=ctx)
+    del cols, vals
+    sp._sh
+    n_top = int(sys.argv[sys.argv.index("--sparse-topn") + 1])
+    tops = [(n_top, 0.0)]
+    if "--n2" in sys.argv:
+        tops.append((int(sys.argv[sys.argv.index("--n2") + 1]), 0.0))
+    if "--kappa" in sys.argv:
+        tops.append((n_top, float(sys.argv[sys.argv.index("--kappa") + 1])))
+    rows = int(sys.argv[sys.argv.index("--slice") + 1]) if "--slice" in sys.argv else max(1, min(n, (1 << 24) // d))
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    model = P.PPCAModel.init(k, sp, seed=3).iterate(sp)
+    q_indptr = np.zeros(n + 1, dtype=np.int64)
+    q_indptr[1:rows + 1] = d
+    q_indptr = np.cumsum(q_indptr)
+    q_cols = np.tile(np.arange(d, dtype=np.int32), rows)
+
+    def composition():
+        mean, _ = model.predict(sp, (q_indptr, q_cols))
+        mean = mean.reshape(rows, d)
+        mean[np.repeat(np.arange(rows), np.diff(indptr[:rows + 1])), sp._indices[:indptr[rows]]] = -np.inf
+        return np.argpartition(mean, d - min(n_top, d), axis=1)[:, d - min(n_top, d):]
+
+    def series(fn, r, warm):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    got_cols, _ = model.recommend(sp, n_top)
+    want = np.sort(composition(), axis=1)
+    same = float(np.mean(np.sort(got_cols[:rows], axis=1) == want)) if n_top <= d else float("nan")
+    print(f"  recommend against the composition on the first {rows} rows: {same:.6f} of the columns agree (ties and last bits apart)", flush=True)
+    name_of = lambda t, kap: f"recommend n = {t}" + (f", kappa = {kap:g}" if kap else "")
+    legs = [("sparse llks", lambda: model.llks(sp), reps, 2)]
+    legs += [(name_of(t, kap), lambda t=t, kap=kap: model.recommend(sp, t, kappa=kap), reps, 2) for t, kap in tops]
+    legs += [(f"predict at all positions of {rows} rows + argpartition", composition, reps, 1)]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn, r, warm in legs:
+            got.setdefault(name, []).append(series(fn, r, warm))
+    med = {name: report(name, np.concatenate(got[name])) for name, _, _, _ in legs}
+    comp = med[legs[-1][0]] * n / rows
+    for t, kap in tops:
+        fl = 2.0 * n * d * (k * k + 2 * k if kap else k) / 78.6e12 * 1e3
+        m = med[name_of(t, kap)]
+        print(f"  {name_of(t, kap)}: floor {fl:.3f} ms + llks {med['sparse llks']:.3f} ms = {fl + med['sparse llks']:.3f} ms, achieved fraction "
+              f"{(fl + med['sparse llks']) / m:.3f} (of the ranking alone: {fl / max(m - med['sparse llks'], 1e-9):.3f});  the composition scaled "
+              f"to N: {comp / 1e3:.1f} s = {comp / m:.0f} x")
+
+
+if "--sparse-topn" in sys.argv:
+    sparse_topn_legs()
+    sys.exit(0)
 if "--sparse-heldout" in sys.argv:
     sparse_heldout_legs()
     sys.exit(0)
