@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libppca_hip.so")
 SOURCES = ["ppca_kernels.hip", "ppca_em9.hip", "ppca_em16.hip", "ppca_llk.hip", "ppca_generic.hip", "ppca_solve4.hip", "ppca_sample.hip", "ppca_loo.hip", "ppca_heldout.hip", "ppca_scale.hip", "ppca_kmeans.hip", "ppca_moments.hip", "ppca_robust.hip", "ppca_hetero.hip", "ppca_sparse.hip", "ppca_capi.hip", "ppca_comm.hip"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]  # (tools/devbuild.py compiles with the same line)
 DEPS = SOURCES + ["ppca_small.hpp", "ppca_internal.hpp", "ppca_solve.hpp", "ppca_handles.hpp", "ppca_device.hpp", "ppca_sweep.hpp", os.path.join("..", "..", "include", "ppca_hip.h")]
 
 
@@ -48,8 +49,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), lib_path: 
         newest = max(os.path.getmtime(f) for f in [os.path.join(CSRC, src)] + headers)
         if not force and not extra_flags and os.path.exists(obj) and os.path.getmtime(obj) > newest:
             continue  # this object is current: only what changed is recompiled (the kernels take ~2 minutes)
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *extra_flags, "-c", os.path.join(CSRC, src),
-               "-o", obj]
+        cmd = [hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((subprocess.Popen(cmd), cmd))

@@ -1173,7 +1173,7 @@ extern "C" int ppca_em_finalize_host(int32_t d, int32_t k, double sigma, const d
 }
 
 // with_table: the plain EM steps (ppca_em_step, _sharded, _group) -- the finalisation also builds the slice table, guard flags and
-// padded C of the NEW model in the same launch (fused path), so that the next pass of `out` on this context starts at once
+// operand-ordered C of the NEW model in the same launch (fused path), so that the next pass of `out` on this context starts at once
 static int em_finalize_impl(ppca_ctx *ctx, const ppca_model *model_in, const double *stats_dev, const ppca_prior *prior, ppca_model *out,
                             bool with_table) {
     if (!ctx || !model_in || !stats_dev || !out) return fail(PPCA_ERR_INVALID, "null argument");

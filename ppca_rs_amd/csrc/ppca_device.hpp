@@ -33,12 +33,10 @@ struct Cfg {
                                                      // then xx[B] doubles, m[B] ints
     // running per-solver-lane scalars (kept out of registers: at this pressure hipcc parks loop-carried
     // once-per-tile values in scratch and reloads them with an exposed vmcnt(0)):
-    // sq[NW <= 8 waves][B] | dev[B] | llk[B] | sumw[B] | nonempty[B] | det mantissa[B] | det exponent[B]
+    // sq[4 waves][2 B] | dev[B] | llk[B] | sumw[B] | nonempty[B] | det mantissa[B] | det exponent[B]
+    // (sq has two slots per solver sample: the EM pass's waves pair lanes)
     static constexpr int OFF_L = OFF_S + 2 * B;
-    // L takes [0, 14 B) (sq has two slots per solver sample when the waves pair lanes).  The B (8 + K + 1) + 16 NTM + 2 doubles behind
-    // it were the regions of the four-wave int8 form of the mask-side statistics contraction (removed): no kernel touches them, and
-    // they stay in the size so that every launch asks for exactly the LDS it was measured with.
-    static constexpr int LDS_DOUBLES = OFF_L + 22 * B + B * (K + 1) + 16 * NTM + 2;
+    static constexpr int LDS_DOUBLES = OFF_L + 14 * B;
     static_assert(K > FUSED_MAX_K || LDS_DOUBLES * 8 <= 160 * 1024, "LDS budget");  // (k > 10: only KP / NTP are used, by qprep_kernel)
 };
 
@@ -238,20 +236,19 @@ __device__ __forceinline__ double lean_log(double x) {
 template <int K>
 constexpr size_t qtab_bytes() { return (size_t)Cfg<K>::NTP * QS * 4 * 1024; }
 
-// One model's block of fused_qtab_bytes(): [64 scales | 8 doubles of guard words | digit table (sized for k = FUSED_MAX_K) | zero-padded
-// C | C in em9_kernel's operand order].  The host's fused_qtab_layout and the multi-component kernels (one block per mixture
+// One model's block of fused_qtab_bytes(): [64 scales | 8 doubles of guard words | digit table (sized for k = FUSED_MAX_K) | C in
+// em9_kernel's operand order].  The host's fused_qtab_layout and the multi-component kernels (one block per mixture
 // component, MixLlkArgs::tab) point a PassArgs at it with this.
 __host__ __device__ inline void fused_qtab_view(void *base, PassArgs &a) {
     a.qscale = static_cast<double *>(base);
     a.qflag = reinterpret_cast<int *>(a.qscale + 64);
     a.qtab = reinterpret_cast<signed char *>(a.qscale + 72);
-    a.cpad = reinterpret_cast<const double *>(a.qtab + qtab_bytes<FUSED_MAX_K>());  // (behind the largest table)
-    a.cpb = a.cpad + FUSED_MAX_D * (FUSED_MAX_K + 1);
+    a.cpb = reinterpret_cast<const double *>(a.qtab + qtab_bytes<FUSED_MAX_K>());  // (behind the largest table)
 }
 
 // Host side: EXPR with KK = k as a constant, for every state size the fused kernels are instantiated for.
 #ifdef PPCA_DEV_K10
-// kernel-tuning builds (tools/devbuild.py): only the k = 10 int8-Gram variants are instantiated
+// kernel-tuning builds (tools/devbuild.py -DPPCA_DEV_K10): the library as it is, instantiated for k = 10 only
 #define PPCA_DISPATCH_K(k, EXPR)                         \
     switch (k) {                                         \
         case 10: { constexpr int KK = 10; EXPR; } break; \

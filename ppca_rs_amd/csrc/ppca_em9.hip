@@ -1343,13 +1343,7 @@ hipError_t em9_debug_counters(unsigned long long *out4, int reset, hipStream_t s
     return hipSuccess;
 }
 
-bool em9_covers(int k) {
-#ifdef PPCA_DEV_K10
-    return k == 10;
-#else
-    return k >= 1 && k <= FUSED_MAX_K;
-#endif
-}
+bool em9_covers(int k) { return k >= 1 && k <= FUSED_MAX_K; }
 
 hipError_t launch_em9(int k, int grid, const PassArgs &a, hipStream_t s) {
     const bool gather = a.rows != nullptr;

@@ -75,7 +75,7 @@ struct ppca_ctx {
     BufRef errb;  // [grid + 1][W_GUARD_NCOL] rounding bounds of the int8 mask-side statistics and their column sums, then 2 x [grid]
                   // ints: the workgroups whose slices the fp64 fallback recomputes, as flags and as a list (reduce_wguard_kernel)
     size_t errb_cap = 0;
-    // which model the slice table / guard flags / padded C behind qtab belong to (base pointer of the table, device buffer and
+    // which model the slice table / guard flags / operand-ordered C behind qtab belong to (base pointer of the table, device buffer and
     // write stamp of the model): a pass of that model launches no qprep_kernel (PassArgs::skip_qprep)
     const void *qtab_base = nullptr, *qtab_model = nullptr;
     uint64_t qtab_stamp = 0;

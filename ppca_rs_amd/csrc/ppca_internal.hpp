@@ -52,7 +52,6 @@ struct PassArgs {
     // EM mode, the guard of the int8 form of the mask-side statistics (launch_em_wguard):
     double *errb;         // [grid][W_GUARD_NCOL]: per workgroup and column of [wP | wz | w], a bound of the rounding the fixed-point
                           // cut added to any sum of that column (written by em9_kernel; nullptr: not collected)
-    const double *cpad;   // zero-padded copy of C, [256][k + 1], written by qprep_kernel (read by no kernel since em9_kernel's b product moved to cpb)
     const double *cpb;    // C as the A operands of em9_kernel's b = X~ C on v_mfma_f64_4x4x4, in operand order (CPB_DOUBLES, written
                           // by qprep_kernel: see cpb_index)
     const int *runflag;   // nullable: second stage of a guarded EM pass (launch_em_fallback): the fp64 instantiation of pass_kernel
@@ -63,7 +62,7 @@ struct PassArgs {
     int heavy_max;        // em9_kernel's back role: a tile with at most this many rows that do not fit the fixed-point form of the
                           // mask-side statistics sends those rows round it (exact fp64 adds) instead of raising its exponents; 0: every
                           // such tile raises them (rounds 3-5: ppca_ctx_set_heavy_rows, a test hook)
-    int skip_qprep;       // the slice table / guard flags / padded C behind qtab are already those of `model` (written by
+    int skip_qprep;       // the slice table / guard flags / operand-ordered C behind qtab are already those of `model` (written by
                           // finalize_qprep_kernel at the end of the previous EM step): the pass launches no qprep_kernel
 };
 // Guard words behind PassArgs::qflag (ints): [0, 8) the Gram guard's per-tile flags (qprep_kernel); [8] the fallback's mode (see
@@ -96,7 +95,7 @@ struct MixLlkArgs {  // mix_llk8_kernel (ppca_llk.hip): the llk sweeps of all co
     void *tab[MIX_MAX];           // the component's slice-table block (fused_qtab_view)
     double *llks[MIX_MAX];        // n per component
 };
-struct MixTabArgs {  // qprep_multi_kernel: slice tables + guard flags + padded C of nm models in one launch
+struct MixTabArgs {  // qprep_multi_kernel: slice tables + guard flags + operand-ordered C of nm models in one launch
     int d, nm;
     const double *model[MIX_MAX];
     void *tab[MIX_MAX];
@@ -227,7 +226,7 @@ hipError_t launch_reduce_partials(const double *part, int grid_parts, int64_t le
 hipError_t launch_reduce_wguard(int k, const double *part, int64_t len, double *stats, const GuardArgs &g, hipStream_t s, bool *applies_out);
 hipError_t launch_em_fallback(int k, int grid, PassArgs a, const GuardArgs &g, const double *part, double *part2, int64_t len, double *stats,
                               hipStream_t s);
-// finalize_kernel + the slice table / guard flags / padded C of the NEW model in one launch (the plain EM step: the next pass of
+// finalize_kernel + the slice table / guard flags / operand-ordered C of the NEW model in one launch (the plain EM step: the next pass of
 // that model then runs with PassArgs::skip_qprep)
 hipError_t launch_finalize_qprep(int k, int d, const double *stats, const double *model_in, double *model_out, double tau, int has_ig,
                                  double alpha, double beta, const PassArgs &tab, hipStream_t s);

@@ -143,21 +143,16 @@ __device__ __forceinline__ void qprep_body(CF C, double s2m, int d, double *qsca
         if (j == 0 && t == 0)
             for (int u = (K * (K + 1) / 2 + 15) / 16; u < 8; ++u) qflag[u] = 0;
     }
-    // zero-padded copy of C: round 4's form of em9_kernel's b = X~ C read its B operands from it; no kernel reads it now (its writes stay: they are this
-    // kernel's measured code).  Only
-    // in the layout of fused_qtab_layout (k <= FUSED_MAX_K: the copy sits behind the largest table); the callers with their
-    // own, exactly sized tables (ppca_em16.hip's, k = 11..16) have no room behind them -- round 4 found that the hard way:
-    // the copy went over the two-kernel pass's workspace.
+    // C in the operand order of em9_kernel's b = X~ C on v_mfma_f64_4x4x4 (ppca_internal.hpp, CPB_DOUBLES): one contiguous
+    // 256-byte block per (dimension half, step, column group); the kernel copies the first two groups into LDS.  Only in the
+    // layout of fused_qtab_view (k <= FUSED_MAX_K: qscale is the block's base, the copy sits behind the largest table); the
+    // callers with their own, exactly sized tables (ppca_em16.hip's, k = 11..16) have no room behind them -- round 4 found
+    // that the hard way: a copy went over the two-kernel pass's workspace.
     if constexpr (K <= FUSED_MAX_K) {  // (every block writes its share: block 0 alone was the kernel's tail)
         constexpr int NB = Cfg<K>::NTP;
-        double *cp = reinterpret_cast<double *>(qtab + qtab_bytes<FUSED_MAX_K>());
-        for (int idx = 256 * t + j; idx < FUSED_MAX_D * (K + 1); idx += 256 * NB) {
-            const int jj = idx / (K + 1), a2 = idx - jj * (K + 1);
-            cp[idx] = (jj < d && a2 < K) ? C(jj, a2) : 0.0;
-        }
-        // ... and C in the operand order of em9_kernel's b = X~ C on v_mfma_f64_4x4x4 (ppca_internal.hpp, CPB_DOUBLES): one
-        // contiguous 256-byte block per (dimension half, step, column group); the kernel copies the first two groups into LDS
-        double *cb = cp + FUSED_MAX_D * (FUSED_MAX_K + 1);
+        PassArgs v{};
+        fused_qtab_view(qscale, v);
+        double *cb = const_cast<double *>(v.cpb);
         constexpr int NCGB = (K + 3) / 4;
         for (int idx = 256 * t + j; idx < 2 * 16 * NCGB * 32; idx += 256 * NB) {
             const int e = idx & 31, blk = idx >> 5;
@@ -213,36 +208,31 @@ __global__ __launch_bounds__(256) void qprep_multi_kernel(MixTabArgs m) {
     qprep_body<K>([=](int j, int a) { return model[MODEL_HDR + (int64_t)j * K + a]; }, model[1], m.d, t.qscale, t.qtab, t.qflag);
 }
 
-// Instantiated as <K, false, 4, true> (the int8-Gram output pass), <K, false, 4, false> and <K, true, 4, false> (the fp64-Gram
-// output and EM passes: the pinned fp64 engine and the fallback behind the guards); the int8-Gram EM pass is em9_kernel.
-// NW = waves per workgroup: always 4 (one wave per SIMD, 512 registers each).
-// GI8: Gram on the int8 MFMA (wave t <-> packed-column tile t) instead of fp64 MFMA.
-// GATHER: always false (it marked the gathered variant of the four-wave int8 EM pass); the fp64-Gram EM pass honours
-// PassArgs::rows (sample i = physical row rows[i]) as it is.  NW and GATHER stay in the parameter list because the kernels'
-// names are what profiles and the benchmark's labels are keyed by.
-template <int K, bool EM, int NW, bool GI8, bool GATHER = false>
-__global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
+// Four waves per workgroup (one per SIMD, 512 registers each).  Instantiated as <K, false, true> (the int8-Gram output pass),
+// <K, false, false> and <K, true, false> (the fp64-Gram output and EM passes: the pinned fp64 engine and the fallback behind
+// the guards); the int8-Gram EM pass is em9_kernel.
+// GI8: Gram on the int8 MFMA (wave t <-> packed-column tile t) instead of fp64 MFMA; output passes only.
+// The EM pass honours PassArgs::rows (sample i = physical row rows[i]).
+template <int K, bool EM, bool GI8>
+__global__ __launch_bounds__(256) void pass_kernel(PassArgs p) {
     using cfg = Cfg<K>;
     constexpr int KP = cfg::KP, NTP = cfg::NTP, NTM = cfg::NTM, B = cfg::B, XS = cfg::XS, CS = cfg::CS,
                   GS = cfg::GS, WS = cfg::WS;
-    constexpr int THREADS = 64 * NW;
-    constexpr int RPW = B / NW;          // rows staged per wave in P1
-    constexpr int KS = NW / 2;           // K-splits of the [G | b] contraction (x 2 row tiles = NW waves)
-    constexpr int DPS = cfg::DP / KS;    // dims per split
+    constexpr int THREADS = 256;         // four waves: one per SIMD, 512 registers each
+    constexpr int RPW = B / 4;           // rows staged per wave in P1
+    constexpr int DPS = cfg::DP / 2;     // dims per K-split of the [G | b] contraction (2 splits x 2 row tiles = 4 waves)
     constexpr int STEPS = DPS / 4;       // MFMA k-steps per split
-    constexpr int WPS = DPS / 64;        // mask words per split
-    constexpr int RT = 16 / NW;          // accumulator row tiles (16 dims each) per wave in P4
-    constexpr int DW = cfg::DP / NW;     // dims owned by a wave in P4
+    constexpr int RT = 4;                // accumulator row tiles (16 dims each) per wave in P4
+    constexpr int DW = cfg::DP / 4;      // dims owned by a wave in P4
     // Mask-side columns of P4: k' (vech P) + k (w z) + 1 (w).  When they overflow the k' tiles by at most four
     // columns (k = 10: 66 = 4 x 16 + 2) the first PADS of [w z | w] ride in the padding of the last vech tile and
     // the remaining SMALL_COLS go through v_mfma_f64_4x4x4_4b (four 4 x 4 x 4 blocks, 18 cycles) instead of a
     // fifth 16-column tile of 64-cycle MFMAs: 16 + 4 instead of 20 big MFMAs per k-step and wave.
     constexpr int PADS = 16 * NTP - KP;
     constexpr int SMALL_COLS = K + 1 - PADS;
-    constexpr bool SPLIT = EM && NW == 4 && SMALL_COLS > 0 && SMALL_COLS <= 4 && PADS > 0;
+    constexpr bool SPLIT = EM && SMALL_COLS > 0 && SMALL_COLS <= 4 && PADS > 0;
     constexpr int NTMB = SPLIT ? NTP : NTM;  // big (16-column) mask-side tiles
-    static_assert(NW == 4, "four waves");
-    static_assert(!GI8 || (NW == 4 && NTP <= 4), "int8 Gram: one wave per packed-column tile");
+    static_assert(!GI8 || (!EM && NTP <= 4), "int8 Gram: output pass only, one wave per packed-column tile");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double *Xs = sm + cfg::OFF_X;
     double *Cs = sm + cfg::OFF_C;
@@ -327,9 +317,9 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
     // cost 2.2k of ~35k cycles per tile: its constants live in scratch at this register pressure)
     double *scl = sm + cfg::OFF_L;
     // PAIRS: the M^-1 columns are computed two at a time, by lane i (column 2p) and lane i + 32 (column 2p + 1)
-    constexpr bool PAIRS = EM && NW == 4 && K >= 2;
+    constexpr bool PAIRS = EM && K >= 2;
     constexpr int SQW = PAIRS ? 2 * B : B;  // sq slots per wave
-    constexpr int L_DEV = NW * SQW, L_LLK = L_DEV + B, L_W = L_DEV + 2 * B, L_NE = L_DEV + 3 * B, L_PM = L_DEV + 4 * B,
+    constexpr int L_DEV = 4 * SQW, L_LLK = L_DEV + B, L_W = L_DEV + 2 * B, L_NE = L_DEV + 3 * B, L_PM = L_DEV + 4 * B,
                   L_PX = L_DEV + 5 * B;
     for (int idx = tid; idx < L_DEV + 6 * B; idx += THREADS) scl[idx] = (idx >= L_PM && idx < L_PX) ? 1.0 : 0.0;
     const double inv_s2 = 1.0 / s2;
@@ -369,8 +359,8 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
     // real rows of the workgroup's own tiles, counted from its first row
     const int64_t own = (tile_end - tile_begin) * B;
     const int nmine = tile_end > tile_begin ? (int)(own < nleft ? own : nleft) : 0;
-    constexpr bool CAN_GATHER = EM && NW == 4 && !GI8;
-    const int *rows_wg = (CAN_GATHER && prows) ? prows + tile_begin * B : nullptr;
+    constexpr bool ROW_LIST = EM;  // the EM pass honours PassArgs::rows
+    const int *rows_wg = (ROW_LIST && prows) ? prows + tile_begin * B : nullptr;
     const int lane_entry = lane;
     // Row loads are buffer loads through ONE descriptor per tile (base = the tile's first row, extent = its real rows;
     // rows are contiguous, ldx == d): the row is a scalar offset, the lane offset one constant VGPR, the half an
@@ -386,7 +376,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
     };
     auto load_row = [&](const __amdgpu_buffer_rsrc_t &trs, int64_t tile, int r) {
         typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-        if constexpr (CAN_GATHER) {
+        if constexpr (ROW_LIST) {
             if (rows_wg) {
                 const int rel = (int)(tile - tile_begin) * B + wave * RPW + r;
                 const int rc = rel < nrel ? rel : nrel - 1;
@@ -414,11 +404,8 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
         for (int r = 0; r < RPW; ++r) load_row(trs, tile, r);
     };
     if (tile_begin < tile_end) load_tile(tile_begin);
-    // int8 Gram: the slice table of this wave's column tile (QS x 4 fragments of 16 B per lane, L2-resident)
-    // streams through two register sets in four digit pairs, high to low.  The table does not depend on the
-    // tile, so pair {7,6} of the NEXT tile is requested at the start of P4 and is long there when P2 begins;
-    // {5,4} is requested first thing in P2 (behind the mask-byte expansion), {3,2} and {1,0} as soon as a
-    // register set is free, and they land behind the fp64 b = X~ C loop.  Buffer loads: one scalar resource for the table, a scalar offset per fragment
+    // int8 Gram: the slice table of this wave's column tile (QS x 4 fragments of 16 B per lane, L2-resident) is read
+    // in four digit pairs.  Buffer loads: one scalar resource for the table, a scalar offset per fragment
     // and one lane offset register.  (The wave's table base is made opaque per use: 32 loop-invariant
     // scalar offsets would be hoisted, overflow the SGPR file and come back through v_readlane + s_nop 4.)
     static_assert(!GI8 || QS == 8, "digit grouping below assumes 8 slices");
@@ -426,9 +413,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
     // Waves without a column tile (k' <= 48) run the same loads (out of range of the table: zeros) and MFMAs
     // and skip only the final store: a run-time condition around the loads would make the fragment registers
     // look live around the whole tile loop.
-    const bool gram_wave = GI8 && (NTP >= NW || wave < NTP);  // compile-time true when every wave owns a tile
-    constexpr bool PREFETCH_A = EM;  // (no P4 in the output passes: they request {7,6} at the start of P2 as well)
-    i4_t qbA[2][4];
+    const bool gram_wave = GI8 && (NTP >= 4 || wave < NTP);  // compile-time true when every wave owns a tile
     auto load_pair = [&](i4_t(&dst)[2][4], int sl0) {
         int qbase = wave * QS * 4 * 1024;
         asm volatile("" : "+s"(qbase));
@@ -442,16 +427,13 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
                 dst[u][kc] = i4_t{(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
             }
     };
-    // Output passes: no statistics accumulators, so the wave's whole slice of the table (QS x 4 fragments = 128
-    // registers) is loaded once per workgroup and stays resident -- no table traffic inside the tile loop.
-    constexpr bool RESIDENT = GI8 && !EM;
-    i4_t qt[RESIDENT ? QS : 1][4];
-    if constexpr (RESIDENT) {
+    // The int8 Gram serves output passes only: no statistics accumulators, so the wave's whole slice of the table
+    // (QS x 4 fragments = 128 registers) is loaded once per workgroup and stays resident -- no table traffic inside
+    // the tile loop.
+    i4_t qt[GI8 ? QS : 1][4];
+    if constexpr (GI8) {
 #pragma unroll
         for (int sl = 0; sl < QS; sl += 2) load_pair(*reinterpret_cast<i4_t(*)[2][4]>(&qt[sl]), sl);
-    }
-    if constexpr (GI8) {
-        if (PREFETCH_A) load_pair(qbA, 6);
     }
 #ifdef PPCA_PHASE_TIMING
     long long tph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -581,7 +563,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             const double *cpc = crow + colb;
             // A = mask bytes: lane (sample = 16 rt + l15, dims 64 kc + 16 l4 .. +15); 4 bits -> 4 bytes
             // by one multiply: (x * 0x204081) & 0x01010101 puts bit i of x into byte i.
-            i4_t af[GI8 ? 2 : 1][4];
+            i4_t af[2][4];
             double v[2][4];
             // one digit pair: contract, then fold the (exact) integer digit sums -- |sum| <= 2^14, so two
             // digits fit one i32 with room to spare -- into the running fp64 value, Horner in 128^2
@@ -604,7 +586,6 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
                 }
             };
             double qs = 0.0;
-            i4_t qbB[2][4];
             if constexpr (GI8) {
                 {
                     // (the mask words are requested from LDS first, so that their latency runs under the issue of
@@ -615,10 +596,6 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
 #pragma unroll
                         for (int kc = 0; kc < 4; ++kc) mwd[rt2][kc] = Msc[(16 * rt2 + l15) * 4 + kc];
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (!RESIDENT) {
-                        if (!PREFETCH_A) load_pair(qbA, 6);
-                        load_pair(qbB, 4);
-                    }
                     if (gram_wave) qs = p.qscale[16 * wave + l15];
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -631,15 +608,8 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
                                 af[rt2][kc][u] = (int)((((bits >> (4 * u)) & 0xFu) * 0x00204081u) & 0x01010101u);
                         }
                     PPCA_STAMP(12)
-                    if constexpr (RESIDENT) {
-                        group(qt + 6, true);
-                        group(qt + 4, false);
-                    } else {
-                        group(qbA, true);   // digits {7,6}: requested during the previous P4
-                        load_pair(qbA, 2);
-                        group(qbB, false);  // digits {5,4}
-                        load_pair(qbB, 0);
-                    }
+                    group(qt + 6, true);   // digits {7,6}
+                    group(qt + 4, false);  // digits {5,4}
                 }
             }
             PPCA_STAMP(13)
@@ -681,13 +651,8 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             }
             PPCA_STAMP(14)
             if constexpr (GI8) {
-                if constexpr (RESIDENT) {
-                    group(qt + 2, false);
-                    group(qt + 0, false);
-                } else {
-                    group(qbA, false);  // digits {3,2}
-                    group(qbB, false);  // digits {1,0}
-                }
+                group(qt + 2, false);  // digits {3,2}
+                group(qt + 0, false);  // digits {1,0}
                 if (gram_wave) {
 #pragma unroll
                     for (int rt2 = 0; rt2 < 2; ++rt2)
@@ -696,8 +661,9 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
                             Gp[(16 * rt2 + 4 * l4 + r) * GS + 16 * wave + l15] = v[rt2][r] * qs;
                 }
             }
-            // K-split partials -> two buffers, summed in a fixed order (deterministic):
-            // G = (p0 [+ p2]) + (p1 [+ p3]); the bracketed terms are added in place by their owner
+            // K-split partials -> two buffers, summed by their readers in a fixed order (deterministic): G = p0 + p1
+            // (kq is 0 or 1, which the compiler cannot see behind the readfirstlane of `wave`: the mask and the test are
+            //  instructions of the kernels as measured, so they stay)
             double *g = Gp + (kq & 1) * B * GS;
             constexpr int T0 = GI8 ? NTP : 0;  // int8 Gram: only the b tile comes from the fp64 accumulators
             if (kq < 2) {
@@ -705,15 +671,6 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
                 for (int t = T0; t < NTM; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) g[(16 * rt + l4 + 4 * r) * GS + 16 * t + l15] = acc[t][r];
-            }
-            if constexpr (KS == 4) {
-                __syncthreads();
-                if (kq >= 2) {
-#pragma unroll
-                    for (int t = T0; t < NTM; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) g[(16 * rt + l4 + 4 * r) * GS + 16 * t + l15] += acc[t][r];
-                }
             }
         }
         __syncthreads();
@@ -749,7 +706,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             if constexpr (PAIRS) {
 #pragma unroll
                 for (int pp = 0; pp < (K + 1) / 2; ++pp) {
-                    if (pair_owner(K, pp, NW) != wave) continue;
+                    if (pair_owner(K, pp, 4) != wave) continue;
                     const int c0 = 2 * pp;
                     const double zc = (hi && c0 + 1 < K) ? z[c0 + 1 < K ? c0 + 1 : c0] : z[c0];
                     // P = z z^T + Sigma, Sigma = sigma^2 M^-1 (ppca_model.rs:437-439), weighted;
@@ -761,7 +718,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             }
 #pragma unroll
             for (int c = 0; c < (PAIRS ? 0 : K); ++c) {
-                if (column_owner(K, c, NW) != wave || !need_cov) continue;
+                if (column_owner(K, c, 4) != wave || !need_cov) continue;
                 if constexpr (EM) {
                     // P = z z^T + Sigma, Sigma = sigma^2 M^-1 (ppca_model.rs:437-439), weighted
                     trpart += post.minv_column(
@@ -882,11 +839,6 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             PPCA_STAMP(4)
             // (b) S/U/totals += Mask^T [wP | wz | w], with the staging (P1) of the next tile's rows between the MFMAs
             stage_begin();
-            if constexpr (GI8) {
-                // the next tile's first digit pair (the table is tile-independent); holding the second pair
-                // across P4 as well spills 73 registers
-                if (PREFETCH_A) load_pair(qbA, 6);
-            }
             // mask operand of dims DW wave + 16 r + l15: word 2 (dim / 128) + parity, bit (dim % 128) / 2
             const int mword = 2 * ((DW * wave) >> 7) + (l15 & 1);
             unsigned long long mwc = Msc[l4 * 4 + mword];
@@ -951,7 +903,6 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             //   covariance diagonals (:485-508, :542-577): A = vech(Sigma_i) (K' entries), B_j = c_ja c_jb,
             //   doubled off the diagonal (c_j^T Sigma c_j over the packed half); + sigma^2
             // (the scalar form spent 2 K LDS reads per output element, 2 K^2 for the diagonals)
-            static_assert(EM || NW == 4, "output pass: four waves x four dim tiles");
             constexpr int CT = 4;
             const bool dg = p.recon_mode >= 2;
             // Loads and stores share one in-order counter (vmcnt): a load consumed after a store waits for that
@@ -959,7 +910,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             // passes through bit-exactly -- is issued HERE, before any store of the tile, and the stores at the
             // end run back to back.
             const bool extra = p.recon_mode == 1, zero_obs = p.recon_mode == 3;
-            constexpr int ROWS = B / NW;
+            constexpr int ROWS = B / 4;
             double xin[ROWS][4];
 #pragma unroll
             for (int rr = 0; rr < ROWS; ++rr)
@@ -968,7 +919,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             if (extra) {
 #pragma unroll
                 for (int rr = 0; rr < ROWS; ++rr) {
-                    const int64_t row = tile * B + wave + NW * rr;
+                    const int64_t row = tile * B + wave + 4 * rr;
                     const double *xrow = p.X + (row < n ? row : n - 1) * p.ldx;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) xin[rr][q] = xrow[64 * q + lane < d ? 64 * q + lane : d - 1];
@@ -1036,7 +987,7 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
             __syncthreads();
 #pragma unroll
             for (int rr = 0; rr < ROWS; ++rr) {
-                const int ri = wave + NW * rr;
+                const int ri = wave + 4 * rr;
                 const int64_t row = tile * B + ri;
                 const bool row_ok = row < n;  // wave-uniform
 #pragma unroll
@@ -1065,17 +1016,17 @@ __global__ __launch_bounds__(64 * NW) void pass_kernel(PassArgs p) {
         const double xx_w = wave_sum(xx_run);
         if (lane == 0) {  // xxs is free after the last tile
             xxs[wave] = sq_w;
-            xxs[NW + wave] = xx_w;
+            xxs[4 + wave] = xx_w;
         }
     }
     __syncthreads();
     if (wave == 0) {
         double v0 = 0.0;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) v0 += xxs[w];
+        for (int w = 0; w < 4; ++w) v0 += xxs[w];
         double xx_tot = 0.0;  // sum_i w_i |x~_i|^2 (EM pass)
 #pragma unroll
-        for (int w = 0; w < NW; ++w) xx_tot += xxs[NW + w];
+        for (int w = 0; w < 4; ++w) xx_tot += xxs[4 + w];
         const int li = lane < B ? lane : 0;
         double sc_llk = scl[L_LLK + li];
         if constexpr (EM) sc_llk -= 0.5 * (log(scl[L_PM + li]) + scl[L_PX + li] * LN_2);
@@ -1459,7 +1410,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double *stats, cons
 }
 // The plain EM step's finalisation AND the next pass's qprep_kernel in one launch: grid = the packed-column tiles of the slice
 // table; every workgroup finalises (d row systems, one per thread: redundant and concurrent), workgroup 0 stores the model, then
-// each builds its tile of the table, its guard flag and its share of the padded copy of C from the new transform in LDS.
+// each builds its tile of the table, its guard flag and its share of the operand-ordered copy of C from the new transform in LDS.
 template <int K>
 __global__ __launch_bounds__(256) void finalize_qprep_kernel(const double *stats, const double *min, double *mout, int d, double tau,
                                                              int has_ig, double alpha, double beta, double *qscale, signed char *qtab,
@@ -1895,15 +1846,15 @@ size_t fused_lds_bytes(int k) {
     return 0;
 }
 
-template <int K, bool EM, int NW, bool GI8, bool GATHER = false>
+template <int K, bool EM, bool GI8>
 static hipError_t launch_pass_t(int grid, const PassArgs &a, hipStream_t s) {
     const size_t lds = sizeof(double) * Cfg<K>::LDS_DOUBLES;
-    if (hipError_t e = ensure_dynamic_lds<pass_kernel<K, EM, NW, GI8, GATHER>>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL((pass_kernel<K, EM, NW, GI8, GATHER>), dim3(grid), dim3(64 * NW), lds, s, a);
+    if (hipError_t e = ensure_dynamic_lds<pass_kernel<K, EM, GI8>>(lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((pass_kernel<K, EM, GI8>), dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
-size_t fused_qtab_bytes() { return qtab_bytes<FUSED_MAX_K>() + (72 + FUSED_MAX_D * (FUSED_MAX_K + 1) + CPB_DOUBLES) * sizeof(double); }
+size_t fused_qtab_bytes() { return qtab_bytes<FUSED_MAX_K>() + (72 + CPB_DOUBLES) * sizeof(double); }
 void fused_qtab_layout(void *base, PassArgs &a) { fused_qtab_view(base, a); }  // [64 scales | 8 doubles of guard flags | digit table | ...]
 
 // Gram engine of the fused passes: 0 = int8-sliced MFMA behind the dynamic-range guard, with the fp64-MFMA instantiation
@@ -1927,15 +1878,11 @@ static int gram_mode() {
 // behind the guard, the fp64 variant -- each returns at once unless qflag selects it.
 template <int K, bool EM>
 static hipError_t launch_pass_guarded(int grid, PassArgs a, hipStream_t s) {
-#ifdef PPCA_DEV_K10
-    const int mode = 2;  // kernel-tuning builds instantiate the int8 variants only
-#else
     const int mode = gram_mode();
     if (mode == 1) {
         a.qflag = nullptr;
-        return launch_pass_t<K, EM, 4, false>(grid, a, s);
+        return launch_pass_t<K, EM, false>(grid, a, s);
     }
-#endif
     if (!a.skip_qprep) hipLaunchKernelGGL((qprep_kernel<K>), dim3(Cfg<K>::NTP), dim3(256), 0, s, a.model, a.d, a.qscale, a.qtab, a.qflag);
     auto int8_pass = [&](const PassArgs &b) {
         if constexpr (!EM) {
@@ -1943,32 +1890,23 @@ static hipError_t launch_pass_guarded(int grid, PassArgs a, hipStream_t s) {
             if (recon8_covers(b)) return launch_recon8(K, grid, b, s);  // smooth / extrapolate on the same sweep (round 6)
         }
         if constexpr (EM) return launch_em9(K, grid, b, s);  // eight waves, two roles, the solve pipelined across tiles (ppca_em9.hip)
-        else return launch_pass_t<K, EM, 4, true>(grid, b, s);
+        else return launch_pass_t<K, EM, true>(grid, b, s);
     };
     if (mode == 2) {
         a.qflag = nullptr;
         return int8_pass(a);
     }
-#ifdef PPCA_DEV_K10
-    return hipErrorInvalidValue;
-#else
     if (hipError_t e = int8_pass(a); e != hipSuccess) return e;
     if constexpr (EM) return hipSuccess;  // the fp64 variant of an EM pass runs behind launch_em_wguard, after the reduction
-    return launch_pass_t<K, EM, 4, false>(grid, a, s);
-#endif
+    return launch_pass_t<K, EM, false>(grid, a, s);
 }
 
 hipError_t launch_pass_em(int k, int grid, const PassArgs &a, hipStream_t s) {
-    // (the eight-wave fp64-Gram instantiation of pass_kernel that PPCA_FUSED_WAVES=8 used to select is gone: it ignored
-    //  PassArgs::rows, and the eight-wave kernel of this library is ppca_em9.hip)
     PPCA_DISPATCH_K(k, return (launch_pass_guarded<KK, true>(grid, a, s)));
     return hipErrorInvalidValue;
 }
 hipError_t launch_reduce_wguard(int k, const double *part, int64_t len, double *stats, const GuardArgs &g, hipStream_t s, bool *applies_out) {
     *applies_out = false;
-#ifdef PPCA_DEV_K10
-    return launch_reduce_partials(part, g.grid, len, stats, s);  // kernel-tuning builds instantiate the int8 variants only
-#else
     if (gram_mode() != 0) return launch_reduce_partials(part, g.grid, len, stats, s);  // engine pinned: nothing to decide
     *applies_out = true;
     GuardArgs h = g;
@@ -1979,41 +1917,26 @@ hipError_t launch_reduce_wguard(int k, const double *part, int64_t len, double *
         return hipGetLastError();
     });
     return hipErrorInvalidValue;
-#endif
 }
 hipError_t launch_em_fallback(int k, int grid, PassArgs a, const GuardArgs &g, const double *part, double *part2, int64_t len, double *stats,
                               hipStream_t s) {
-#ifdef PPCA_DEV_K10
-    return hipSuccess;
-#else
     a.runflag = g.qflag + QF_MODE;
     a.who = g.who;
     a.part = part2;
     a.errb = nullptr;
     PPCA_DISPATCH_K(k, {
-        if (hipError_t e = launch_pass_t<KK, true, 4, false>(grid, a, s); e != hipSuccess) return e;
+        if (hipError_t e = launch_pass_t<KK, true, false>(grid, a, s); e != hipSuccess) return e;
     });
     const int blocks = (int)((len + 63) / 64);
     hipLaunchKernelGGL(reduce_fallback_kernel, dim3(blocks), dim3(256), 0, s, part, (const double *)part2, (const int *)g.wgflag, grid, len, stats,
                        (const int *)(g.qflag + QF_MODE));
     return hipGetLastError();
-#endif
 }
 
-int fused_gram_mode() {
-#ifdef PPCA_DEV_K10
-    return 2;
-#else
-    return gram_mode();
-#endif
-}
+int fused_gram_mode() { return gram_mode(); }
 hipError_t launch_pass_post_fp64(int k, int grid, const PassArgs &a, hipStream_t s) {
-#ifdef PPCA_DEV_K10
-    return hipSuccess;
-#else
-    PPCA_DISPATCH_K(k, return (launch_pass_t<KK, false, 4, false>(grid, a, s)));
+    PPCA_DISPATCH_K(k, return (launch_pass_t<KK, false, false>(grid, a, s)));
     return hipErrorInvalidValue;
-#endif
 }
 hipError_t launch_qprep_multi(int k, const MixTabArgs &a, hipStream_t s) {
     PPCA_DISPATCH_K(k, hipLaunchKernelGGL((qprep_multi_kernel<KK>), dim3(Cfg<KK>::NTP, a.nm), dim3(256), 0, s, a));
@@ -2024,9 +1947,6 @@ hipError_t launch_finalize_qprep_multi(int k, const MixFinalArgs &a, hipStream_t
     return hipGetLastError();
 }
 hipError_t launch_reduce_wguard_multi(int k, const MixReduceArgs &a, int grid_parts, hipStream_t s) {
-#ifdef PPCA_DEV_K10
-    return hipErrorInvalidValue;
-#else
     (void)grid_parts;
     MixReduceArgs h = a;
     if (!em9_covers(k))
@@ -2034,7 +1954,6 @@ hipError_t launch_reduce_wguard_multi(int k, const MixReduceArgs &a, int grid_pa
     const int blocks = (int)((a.len + 63) / 64) + (W_GUARD_NCOL + 63) / 64;
     PPCA_DISPATCH_K(k, hipLaunchKernelGGL((reduce_wguard_multi_kernel<KK>), dim3(blocks, a.nm), dim3(256), 0, s, h));
     return hipGetLastError();
-#endif
 }
 
 hipError_t launch_pass_post(int k, int grid, const PassArgs &a, hipStream_t s) {
@@ -2043,17 +1962,12 @@ hipError_t launch_pass_post(int k, int grid, const PassArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_gram_guard(int k, const PassArgs &a, hipStream_t s, int *forced) {
-#ifdef PPCA_DEV_K10
-    *forced = 0;
-    return hipSuccess;
-#else
     const int mode = gram_mode();
     *forced = mode == 1 ? 1 : (mode == 2 ? 0 : -1);
     if (mode != 0) return hipSuccess;
     PPCA_DISPATCH_K(k, hipLaunchKernelGGL((qprep_kernel<KK>), dim3(Cfg<KK>::NTP), dim3(256), 0, s, a.model, a.d, a.qscale,
                                           a.qtab, a.qflag));
     return hipGetLastError();
-#endif
 }
 // slice table + guard flags for the state sizes of ppca_em16.hip
 hipError_t launch_qprep16(int k, const double *model, int d, double *qscale, signed char *qtab, int *qflag, hipStream_t s) {

@@ -32,7 +32,7 @@
 //     its four rows to four other waves through LDS (llk8_run's round comment).
 // Per-sample arithmetic is that of pass_kernel except for the ORDER of the |x~|^2 sum and of the b partials (same
 // int8-sliced Gram behind the same guard, same Cholesky), so the llks agree with it to rounding.  The guard's fallback is
-// pass_kernel<K, false, 4, false>.
+// pass_kernel<K, false, false>.
 // (llk2_kernel, the four-wave form of this sweep of rounds 2-3 -- two tiles per round, every wave a Gram and a b unit -- last existed in commit e1e9872.)
 #include <cstdlib>
 
@@ -596,7 +596,7 @@ __device__ __forceinline__ void llk8_run(const PassArgs &p, double *sm, const in
 template <int K>
 __global__ __launch_bounds__(512) void llk8_kernel(PassArgs p) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if (p.qflag) {  // qprep's dynamic-range guard: pass_kernel<K, false, 4, false> runs instead
+    if (p.qflag) {  // qprep's dynamic-range guard: pass_kernel<K, false, false> runs instead
         int unsafe = 0;
 #pragma unroll
         for (int t = 0; t < CfgL8<K>::NTP; ++t) unsafe |= p.qflag[t];
@@ -613,7 +613,7 @@ __global__ __launch_bounds__(512) void llk8_kernel(PassArgs p) {
 template <int K, int OUT>
 __global__ __launch_bounds__(512) void recon8_kernel(PassArgs p) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if (p.qflag) {  // qprep's dynamic-range guard: pass_kernel<K, false, 4, false> runs instead
+    if (p.qflag) {  // qprep's dynamic-range guard: pass_kernel<K, false, false> runs instead
         int unsafe = 0;
 #pragma unroll
         for (int t = 0; t < CfgL8<K>::NTP; ++t) unsafe |= p.qflag[t];

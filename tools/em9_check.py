@@ -1,5 +1,5 @@
 """Parity of em9_kernel (the eight-wave EM pass with the solve pipelined across tiles) against the oracle: N = 20 000 on the full grid and on 2 / 1 workgroups,
-weighted and not, plus ragged shapes (diagnostic; tools/devbuild.py libraries hold k = 10 only)."""
+weighted and not, plus ragged shapes (diagnostic; k = 10 throughout, so it also runs on a `tools/devbuild.py ... -DPPCA_DEV_K10` library: the real pipeline, guards and fallback included, for k = 10 only)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
