@@ -559,6 +559,33 @@ int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model,
  * k <= 16 (else PPCA_ERR_UNSUPPORTED); n = 0: PPCA_ERR_EMPTY.  (Named with the family first, like ppca_heldout_score_sparse.) */
 int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, int32_t n_top, double kappa, int32_t exclude_observed,
                      const int32_t *candidates, int64_t n_candidates, int32_t *cols_host, double *scores_host);
+/* The mixture (ppca_mix_*) on row-compressed data: n_models components of sp's output size, any state sizes <= 16
+ * (state size 0 as one zero column), any number of them.  ell_c of a row is ppca_sparse_llk's of component c alone, bit for bit: one
+ * row pass computes it for all components of a state size, the row's entries read once.
+ * ppca_mix_sparse_llk: ppca_mix_llk -- per_row_host (n) the mixture log-density of each row, total_host its sum under sp's weights,
+ * log_posteriors_host (n x n_models) the log posterior over the components; each output nullable.  An empty row has ell_c = 0 for
+ * every c: its posterior is the prior weights.
+ * ppca_mix_sparse_component_llks: out_host (n_models x n, component-major) = the ell_c behind the above (for tests and diagnostics).
+ * ppca_mix_sparse_em_step: ppca_mix_em_step -- the same sequence, output-aliasing checks and priors, a row of weight <= 0 contributes
+ * nothing; everything is enqueued on the context stream and the n_models + 1 returned numbers are read back behind one synchronisation
+ * (a mean prior adds its host solve per component).  Where the dense step drops the rows whose weight is below 2^-200 of the
+ * component's largest from that component's pass, this one does not gather rows (the row lists and the inverted index are fixed): such
+ * rows enter with their negligible weight, and the two agree to far below fp64 resolution.
+ * ppca_mix_sparse_predict: ppca_sparse_predict for the mixture.  With r_c the row's posterior given its entries in sp and (m_c, v_c)
+ * ppca_sparse_predict's pair under component c: mean = sum_c r_c m_c, var = sum_c r_c v_c + sum_c r_c (m_c - mean)^2, the components
+ * added in index order by the one thread that owns the query entry: bit-identical under any grid limit and block_rows.  The scratch is
+ * one block's states and covariances of ONE component and n_models means per query entry of the block; no n x d buffer, no float
+ * atomics.
+ * Preconditions of all four, checked before any device work: n_models >= 1, every model of sp's d and on sp's device (else
+ * PPCA_ERR_INVALID); every k <= 16 (else PPCA_ERR_UNSUPPORTED); n = 0: PPCA_ERR_EMPTY.  (Named with the family first, like
+ * ppca_topn_sparse.) */
+int ppca_mix_sparse_llk(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models, const double *log_weights, int32_t n_models,
+                        double *total_host, double *per_row_host, double *log_posteriors_host);
+int ppca_mix_sparse_component_llks(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models, int32_t n_models, double *out_host);
+int ppca_mix_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models_in, const double *log_weights_in, int32_t n_models,
+                            const ppca_prior *prior, ppca_model *const *models_out, double *log_weights_out, double *llk_in);
+int ppca_mix_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models, const double *log_weights, int32_t n_models,
+                            const int64_t *query_row_ptr, const int32_t *query_col, double *mean_host, double *var_host);
 /* The hold-out split of ppca_dataset_holdout_range on the pattern of row-compressed data, on host buffers (no GPU needed; DESIGN.md
  * 4.21).  row_ptr (n + 1, from 0, monotone) and col (>= 0) as above.  Entry e of row i, column j = col[e], global row
  * g = row_offset + i draws the word of the dense split, u = (row_word(row_key(seed, 8, g), j) >> 11) 2^-53, and

@@ -432,7 +432,8 @@ class SparseDataset:
     block_rows / segment: the two tiling lengths of the passes (None: the library's defaults; tests put the seams at small sizes).
     The entries go to the device, with the inverted index the statistics pass reads, on first use.
     `holdout` / `holdout_range` / `kfold` split the entries on the host exactly as Dataset's split the same matrix, and
-    PPCAModel.heldout_score takes the two parts."""
+    PPCAModel.heldout_score takes the two parts.  PPCAMix takes one too: llk / llks / infer_cluster / iterate* /
+    predict and PPCAMixTrainer."""
 
     def __init__(self, indptr, indices, values, n_columns: int, weights=None, *, ctx=None, block_rows: Optional[int] = None,
                  segment: Optional[int] = None):
@@ -515,7 +516,8 @@ class SparseDataset:
     def _h(self):
         # every pass written for the dense layout reaches its dataset through _h
         raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
-                        "predict / heldout_score and PPCATrainer are")
+                        "predict / recommend / heldout_score and PPCATrainer are, and PPCAMix.llk / llks / infer_cluster / iterate* / "
+                        "predict and PPCAMixTrainer")
 
     @property
     def _sh(self):
@@ -640,6 +642,13 @@ class SparseDataset:
 
     def __repr__(self):
         return f"SparseDataset(n={len(self)}, output_size={self.output_size()}, nnz={self.nnz})"
+
+
+def _dense_only(*datasets):
+    """Raises SparseDataset._h's TypeError before anything touches the device."""
+    for ds in datasets:
+        if isinstance(ds, SparseDataset):
+            ds._h
 
 
 def _query_pattern(sparse: SparseDataset, query):
@@ -2358,6 +2367,8 @@ class PPCAMix:
     def init(n_models: int, state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "PPCAMix":
         """mix.rs:76-83.  method="kmeans" (an extension): `from_kmeans(state_size, dataset, dataset.kmeans(n_models, seed=seed))`."""
         if method == "kmeans":
+            if isinstance(dataset, SparseDataset):
+                raise ValueError("method='kmeans' is not available on a SparseDataset: k-means takes a dense Dataset")
             return PPCAMix.from_kmeans(state_size, dataset, dataset.kmeans(n_models, seed=seed))
         if method != "random":
             raise ValueError("method must be 'random' or 'kmeans'")
@@ -2370,6 +2381,8 @@ class PPCAMix:
         """The k-means start: component c is `PPCAModel.from_moments` of the rows of cluster c (the dataset under the weights
         w * (km.labels == c): one moment pass per cluster), log_weights = ln(cluster_weights / their sum).  A cluster of weight 0 takes
         the whole dataset's `from_moments` model and the weight of the lightest cluster that has some."""
+        if isinstance(dataset, SparseDataset):
+            raise ValueError("from_kmeans is not available on a SparseDataset: k-means takes a dense Dataset")
         moms, whole, lw = _kmeans_cluster_moments(dataset, km)
         return PPCAMix([PPCAModel.from_moments(state_size, m if m is not None else whole) for m in moms], lw)
 
@@ -2403,31 +2416,48 @@ class PPCAMix:
         arr = (C.c_void_p * len(devs))(*[d.h for d in devs])
         return devs, arr
 
+    def _mix_llk(self, dataset: Dataset, total, per_row, log_posteriors):
+        """ppca_mix_llk, or ppca_mix_sparse_llk on a SparseDataset; each output nullable."""
+        devs, arr = self._handles(dataset._ctx)
+        fn, h = (lib().ppca_mix_sparse_llk, dataset._sh) if isinstance(dataset, SparseDataset) else (lib().ppca_mix_llk, dataset._h)
+        check(fn(dataset._ctx.handle, h, arr, ptr(self._lw), len(devs), total, per_row, log_posteriors))
+
     def llk(self, dataset: Dataset) -> float:
         """mix.rs:162-174"""
-        devs, arr = self._handles(dataset._ctx)
         tot = C.c_double(0.0)
-        check(lib().ppca_mix_llk(dataset._ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), C.byref(tot), None, None))
+        self._mix_llk(dataset, C.byref(tot), None, None)
         return tot.value
 
     def llks(self, dataset: Dataset) -> np.ndarray:
         """mix.rs:152-159"""
-        devs, arr = self._handles(dataset._ctx)
         out = np.empty(len(dataset))
-        check(lib().ppca_mix_llk(dataset._ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), None, ptr(out), None))
+        self._mix_llk(dataset, None, ptr(out), None)
         return out
 
     def infer_cluster(self, dataset: Dataset) -> np.ndarray:
         """Log posteriors (N, n_models) (mix.rs:179-189)."""
-        devs, arr = self._handles(dataset._ctx)
-        out = np.empty((len(dataset), len(devs)))
-        check(lib().ppca_mix_llk(dataset._ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), None, None, ptr(out)))
+        out = np.empty((len(dataset), len(self._models)))
+        self._mix_llk(dataset, None, None, ptr(out))
         return out
 
+    def predict(self, sparse: "SparseDataset", query):
+        """PPCAModel.predict for the mixture: (mean, var) of a new reading at the query positions of row-compressed data, one value per
+        query entry in query order.  With r_c the row's posterior over the components given its entries in `sparse` and (m_c, v_c)
+        component c's `predict`: mean = sum_c r_c m_c and var = sum_c r_c v_c + sum_c r_c (m_c - mean)^2 -- the convention of
+        InferredMaskedMix.smoothed_covariances_diagonal with sigma^2 included.  No N x d array is formed."""
+        if not isinstance(sparse, SparseDataset):
+            raise TypeError("predict takes a SparseDataset (on a Dataset: smooth / extrapolate / heldout_score)")
+        ip, ix = _query_pattern(sparse, query)
+        mean, var = np.empty(ix.size), np.empty(ix.size)
+        ctx = sparse._ctx
+        devs, arr = self._handles(ctx)
+        check(lib().ppca_mix_sparse_predict(ctx.handle, sparse._sh, arr, ptr(self._lw), len(devs), ptr(ip), ptr(ix), ptr(mean), ptr(var)))
+        return mean, var
+
     def _iterate(self, dataset: Dataset, prior: Optional[Prior], want_llk: bool):
-        ctx = dataset._ctx
         if len(dataset) == 0:
             raise ValueError("dataset is empty")
+        ctx = dataset._ctx
         devs, arr = self._handles(ctx)
         outs = []
         for m in self._models:
@@ -2438,8 +2468,8 @@ class PPCAMix:
         lw_out = np.empty(len(outs))
         llk = C.c_double(0.0)
         pref, keep = _prior_ref(prior)
-        check(lib().ppca_mix_em_step(ctx.handle, dataset._h, arr, ptr(self._lw), len(devs), pref, oarr, ptr(lw_out),
-                                     C.byref(llk) if want_llk else None))
+        fn, h = (lib().ppca_mix_sparse_em_step, dataset._sh) if isinstance(dataset, SparseDataset) else (lib().ppca_mix_em_step, dataset._h)
+        check(fn(ctx.handle, h, arr, ptr(self._lw), len(devs), pref, oarr, ptr(lw_out), C.byref(llk) if want_llk else None))
         models = [PPCAModel._from_device(o, ctx, m.output_size, m.state_size) for o, m in zip(outs, self._models)]
         new = PPCAMix.__new__(PPCAMix)
         new._models, new._lw = models, lw_out
@@ -2464,9 +2494,11 @@ class PPCAMix:
     # -- inference outputs (mix.rs:179-265; src/python_bindings.rs:645-672) ---------------------------
     def infer(self, dataset: Dataset) -> "InferredMaskedMix":
         """Posterior over the components and the per-component state posteriors (mix.rs:206-235)."""
+        _dense_only(dataset)  # (the accessors of InferredMaskedMix form N x d arrays)
         return InferredMaskedMix(self, self.infer_cluster(dataset), [m.infer(dataset) for m in self._models])
 
     def _mix_recon(self, dataset: Dataset, mode: int) -> Dataset:
+        _dense_only(dataset)
         ctx = dataset._ctx
         devs, arr = self._handles(ctx)
         h = C.c_void_p()
@@ -2493,6 +2525,7 @@ class PPCAMix:
             raise ValueError("row_offset must be >= 0")
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1)[0])
+        _dense_only(dataset)
         ctx = dataset._ctx
         devs, arr = self._handles(ctx)
         h = C.c_void_p()
@@ -2504,12 +2537,14 @@ class PPCAMix:
         """PPCAModel.heldout_score for the mixture: per held entry the mixture of the components' predictives, component c weighted
         by its posterior given the row of `train`.  l = logsumexp_c(lp_c + l_c); the error is the mixture mean's, the variance
         sum_c a_c v_c plus the spread of the components' means."""
+        _dense_only(train, held)
         ctx = train._ctx
         devs, arr = self._handles(ctx)
         return _heldout_call(train, held, lambda t, c, r: lib().ppca_mix_heldout_score(ctx.handle, train._h, held._h, arr,
                                                                                       ptr(self._lw), len(devs), t, c, r))
 
     def _loo(self, dataset: Dataset, full: bool, per_sample: bool):
+        _dense_only(dataset)
         ctx = dataset._ctx
         devs, arr = self._handles(ctx)
         return _loo_call(dataset, full, per_sample, lambda mh, vh, tot, ps: lib().ppca_mix_loo_predictive(

@@ -1115,7 +1115,7 @@ static int smooth_mean_host(const ppca_prior *prior, int d, const double *totals
     return PPCA_OK;
 }
 
-static int check_prior(const ppca_prior *prior) {
+int ppca_host::check_prior(const ppca_prior *prior) {
     if (!prior) return PPCA_OK;
     if (prior->has_isotropic_noise_prior && !(prior->isotropic_noise_alpha >= 0.0 && prior->isotropic_noise_beta >= 0.0))
         return fail(PPCA_ERR_INVALID, "isotropic noise prior needs alpha >= 0 and beta >= 0");  // prior.rs:50-51
@@ -1235,6 +1235,9 @@ extern "C" int ppca_em_finalize(ppca_ctx *ctx, const ppca_model *model_in, const
 namespace ppca_host {
 int em_finalize_with_table(ppca_ctx *ctx, const ppca_model *model_in, const double *stats_dev, const ppca_prior *prior, ppca_model *out) {
     return em_finalize_impl(ctx, model_in, stats_dev, prior, out, true);
+}
+int em_finalize_plain(ppca_ctx *ctx, const ppca_model *model_in, const double *stats_dev, const ppca_prior *prior, ppca_model *out) {
+    return em_finalize_impl(ctx, model_in, stats_dev, prior, out, false);
 }
 }  // namespace ppca_host
 
@@ -1645,13 +1648,8 @@ static int mix_check(ppca_dataset *ds, ppca_model *const *models, int32_t nm) {
 
 // The mixture step's small device vectors, sized by the number of components (mix.rs:50-71 has no limit on it):
 // [0, P) maxima -> shifts | [P, 2P) new log-weights, llk | [2P, 3P) the normalised log-weights of the llk sweep |
-// [3P, ...) one int per component: rows its pass gathered;  P = nm + 1 rounded up to 8 doubles.
-struct MixAux {
-    double *shift, *out, *logw;
-    int *used;
-    size_t P;
-};
-static int mix_aux(ppca_ctx *ctx, int32_t nm, MixAux &a) {
+// [3P, ...) one int per component: rows its pass gathered;  P = nm + 1 rounded up to 8 doubles.  (MixAux: ppca_handles.hpp)
+int ppca_host::mix_aux(ppca_ctx *ctx, int32_t nm, MixAux &a) {
     a.P = ((size_t)nm + 1 + 7) & ~(size_t)7;
     if (int rc = ensure(ctx->mixaux, ctx->mixaux_cap, sizeof(double) * 3 * a.P + sizeof(int) * (size_t)nm)) return rc;
     a.shift = static_cast<double *>(ctx->mixaux->p);
@@ -1742,7 +1740,7 @@ static int mix_llk_sweeps_multi(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *con
 }
 // normalised log-weights (PPCAMix::new mix.rs:66-70) into aux.logw, through the context's pinned staging buffer: an asynchronous
 // copy (every entry point that uses the staging ends with a synchronisation, so it is free at the next call)
-static int mix_upload_logw(ppca_ctx *ctx, const double *log_weights, int nm, const MixAux &aux) {
+int ppca_host::mix_upload_logw(ppca_ctx *ctx, const double *log_weights, int nm, const MixAux &aux) {
     if (int rc = ensure_hstage(ctx, sizeof(double) * (size_t)nm)) return rc;
     double *lw = static_cast<double *>(ctx->hstage);
     double mx = log_weights[0];

@@ -23,7 +23,8 @@ score, PPCAModel.loo_llks and the scale pass with output for comparison, and the
 extrapolated covariance diagonal and both downloads).  `--sparse DENSITY` / `--sparse-rows M [--k2 K2]` run ONLY the legs of
 SparseDataset (see sparse_legs); with `--sparse-heldout` beside either, ONLY the legs of held-out scoring on that
 data (see sparse_heldout_legs); with `--sparse-topn N_TOP` beside either, ONLY the legs of PPCAModel.recommend on that
-data (see sparse_topn_legs)."""
+data (see sparse_topn_legs); with `--mix NM` beside either, ONLY the legs of PPCAMix on that data (see
+sparse_mix_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -294,6 +295,69 @@ def sparse_topn_legs(reps=5):
               f"to N: {comp / 1e3:.1f} s = {comp / m:.0f} x")
 
 
+def sparse_mix_legs(nm, reps=5):
+    """PPCAMix on a SparseDataset (`--mix NM [--reps R]` beside `--sparse DENSITY` or `--sparse-rows M`), in one process,
+    alternating, every repetition timed on its own, NM components of state size K: (a) the fused row pass (the component-major ell
+    buffer, downloaded: NM x N doubles) against NM calls of PPCAModel.llks (the single-model row pass; N doubles downloaded each, plus
+    its scalar sums); (b) one PPCAMix.iterate against NM x PPCAModel.iterate; (c) PPCAMix.predict at 1 M query entries against NM x
+    PPCAModel.predict."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    sp = P.SparseDataset(indptr, cols.int().cpu().numpy(), vals.cpu().numpy(), d, ctx=ctx)
+    del cols, vals
+    sp._sh
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    mix = P.PPCAMix.init(nm, k, sp, seed=3).iterate(sp)
+    models = mix.models
+    devs, arr = mix._handles(ctx)
+    ell = np.empty((nm, n))
+    rng = np.random.default_rng(5)
+    nq = 1 << 20
+    q_indptr = np.searchsorted(np.sort(rng.integers(0, n, nq)), np.arange(n + 1), side="left").astype(np.int64)
+    q_cols = rng.integers(0, d, nq).astype(np.int32)
+
+    def fused():
+        _lib.check(_lib.lib().ppca_mix_sparse_component_llks(ctx.handle, sp._sh, arr, nm, _lib.ptr(ell)))
+
+    def series(fn, r, warm=2):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    fused()
+    same = all(np.array_equal(ell[c], m.llks(sp)) for c, m in enumerate(models))
+    print(f"  the fused pass's ell against PPCAModel.llks, component by component: {'bit-identical' if same else 'DIFFERENT'}", flush=True)
+    legs = [(f"(a) fused row pass, {nm} components", fused),
+            (f"(a) {nm} x PPCAModel.llks", lambda: [m.llks(sp) for m in models]),
+            ("(b) PPCAMix.iterate", lambda: mix.iterate(sp)),
+            (f"(b) {nm} x PPCAModel.iterate", lambda: [m.iterate(sp) for m in models]),
+            (f"(c) PPCAMix.predict, {nq} entries", lambda: mix.predict(sp, (q_indptr, q_cols))),
+            (f"(c) {nm} x PPCAModel.predict", lambda: [m.predict(sp, (q_indptr, q_cols)) for m in models])]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn, reps))
+    med = [report(name, np.concatenate(got[name])) for name, _ in legs]
+    spread = [float(np.ptp(np.concatenate(got[name])) / np.median(np.concatenate(got[name]))) for name, _ in legs]
+    for i, what in ((0, "fused / separate row passes"), (2, "mixture iterate / nm single iterates"), (4, "mixture predict / nm single predicts")):
+        print(f"  {what}: {med[i] / med[i + 1]:.3f}  (run-to-run spread of the two legs: {spread[i]:.1%}, {spread[i + 1]:.1%})", flush=True)
+
+
+if "--mix" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
+    sparse_mix_legs(int(sys.argv[sys.argv.index("--mix") + 1]))
+    sys.exit(0)
 if "--sparse-topn" in sys.argv:
     sparse_topn_legs()
     sys.exit(0)
