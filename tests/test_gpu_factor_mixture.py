@@ -64,7 +64,7 @@ def _sweep_reference(x, e, a, b):
 
 
 @pytest.mark.parametrize("sliced", [False, True], ids=["plain", "slice"])
-@pytest.mark.parametrize("nc", [1, 3, 9])
+@pytest.mark.parametrize("nc", [1, 2, 3, 4, 5, 8, 9, 16])  # (KB = 1, 2, 4, 8: a partial and a full block of each, two full trips)
 @pytest.mark.parametrize("d", [256, 200, 1024, 7])
 def test_multi_component_sweep_against_numpy(P, d, nc, sliced):
     """Every sum within 1e-12 of numpy's, relative to the sum of the absolute values of its terms (the bound and measure of

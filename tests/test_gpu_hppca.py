@@ -15,6 +15,7 @@ import pytest
 
 import hppca_restatement as R
 import mask_patterns as MP
+import state_size_cases as S
 
 pytestmark = pytest.mark.gpu
 
@@ -79,8 +80,28 @@ SHAPES = [(1, 1, 1), (3, 5, 2), (65, 17, 3), (257, 64, 10), (130, 65, 16), (600,
 
 @pytest.mark.parametrize("n,d,k", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
 def test_against_restatement(P, n, d, k):
-    x, p, w, (s, c, mu) = _case(n, d, k)
-    e = _want(n, d, k)
+    _check_against_restatement(P, _case(n, d, k), _want(n, d, k))
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_want(k):
+    x, p, w, (s, c, mu) = S.hetero_case(k)
+    return R.estep(x, p, w, s, c, mu)
+
+
+@pytest.mark.parametrize("k", S.KS)
+def test_state_size_sweep(P, k):
+    """Every instantiation of the sweep and the statistics kernel at (130, 97, k): two full 64-row workgroup steps and one of 2 rows,
+    eight 16-row steps of the statistics kernel and 2 rows; three column chunks of 32 and one column (k = 11, 12: one of 64 and 33
+    columns), one full 64-column tile of the statistics kernel and a ragged one.  Rows 0 .. k + 2 hold exactly 0 .. k + 2 entries."""
+    e = _sweep_want(k)
+    assert np.array_equal(e["m"][:k + 3], np.arange(k + 3))
+    _check_against_restatement(P, S.hetero_case(k), e)
+
+
+def _check_against_restatement(P, case, e):
+    x, p, w, (s, c, mu) = case
+    (n, d), k = x.shape, c.shape[1]
     ds, prec = P.Dataset(x, w), P.Dataset(p)
     model = P.HPPCAModel(s, c, mu)
     got = _all(model, ds, prec)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import mask_patterns as MP
+import state_size_cases as S
 import tppca_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -66,9 +67,12 @@ SHAPES = [(1, 1, 1), (3, 5, 2), (65, 17, 3), (257, 64, 10), (600, 256, 10), (300
 
 @pytest.mark.parametrize("n,d,k", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
 def test_estep_against_restatement(P, n, d, k):
-    nu = 4.0
-    x, w, (s, c, mu) = _case(n, d, k)
-    e = _want(n, d, k, nu)
+    _check_estep(P, _case(n, d, k), _want(n, d, k, 4.0), 4.0)
+
+
+def _check_estep(P, case, e, nu):
+    x, w, (s, c, mu) = case
+    (n, d), k = x.shape, c.shape[1]
     ds = P.Dataset(x, w)
     model = P.TPPCAModel(s, c, mu, nu)
     got = model._estep(ds, scaled=True, col_sums=True, u=True, maha=True, llks=True, scalars=True)
@@ -126,6 +130,32 @@ def test_estep_against_restatement(P, n, d, k):
             assert np.array_equal(up, u[sl]) and np.array_equal(dp, delta[sl]) and np.array_equal(lp, ell[sl])
             at += len(part)
         assert at == n
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_want(d, k, nu):
+    x, w, (s, c, mu) = S.robust_case(d, k)
+    return R.estep(x, w, s, c, mu, nu)
+
+
+@pytest.mark.parametrize("d", S.ROBUST_DS)
+@pytest.mark.parametrize("k", S.KS)
+def test_state_size_sweep(P, k, d):
+    """Every instantiation of the sweep: the four row blocks KB = 4, 8, 12, 16 (with every k that pads a thread's rows of C) x the three
+    column layouts (d <= 64, d <= 256, beyond) x the three modes that the E-step check's calls reach, at n = 70 (a ragged last step in
+    every layout); then one ECM step (d = 300: the EM pass on the scaled rows runs through the lane solver).  Rows 0 .. k + 2 hold
+    exactly 0 .. k + 2 entries."""
+    nu = 4.0
+    case, e = S.robust_case(d, k), _sweep_want(d, k, nu)
+    assert np.array_equal(e["m"][:k + 3], np.arange(k + 3))
+    _check_estep(P, case, e, nu)
+    x, w, (s, c, mu) = case
+    model = P.TPPCAModel(s, c, mu, nu)
+    new, llk = model.iterate_with_llk(P.Dataset(x, w))
+    errs = _model_errors(new, R.mstep(s, c, mu, e))
+    errs["llk"] = abs(llk - e["scalars"][1]) / e["scalars_abs"][1]
+    print("   iterate 70x%dx%d" % (d, k), " ".join("%s %.1e" % kv for kv in errs.items()), "(bound %g)" % TOL)
+    assert max(errs.values()) <= TOL, errs
 
 
 @pytest.mark.parametrize("nu", [0.7, 200.0])

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import sparse_cases as SC
+import state_size_cases as S
 
 pytestmark = pytest.mark.gpu
 
@@ -137,14 +138,18 @@ def _show(label, errs):
 # ------------------------------------------------------------------ against the oracle
 @pytest.mark.parametrize("n,d,k", SHAPES, ids=IDS)
 def test_against_oracle(P, oracle, n, d, k):
+    _check_against_oracle(P, oracle, n, d, k)
+
+
+def _check_against_oracle(P, oracle, n, d, k, **tiling):
     x, w, (s, c, mu) = _case(n, d, k)
     e = _want(oracle, n, d, k)
-    sp = P.SparseDataset.from_dense(x, w)
+    sp = P.SparseDataset.from_dense(x, w, **tiling)
     model = P.PPCAModel(s, c, mu)
     inf = model.infer(sp)
     errs = dict(llks=_rel(model.llks(sp), e["llks"]), llk=abs(model.llk(sp) - e["llk"]) / max(e["scale"][-6], 1.0),
                 z=_rel(inf.states(), e["z"]), Sigma=_rel(np.array(inf.covariances()), e["cov"]))
-    _show("rows %dx%dx%d" % (n, d, k), errs)
+    _show("rows %dx%dx%d %s" % (n, d, k, tiling or ""), errs)
     assert max(errs.values()) <= TOL, errs
     empty = ~np.isfinite(x).any(axis=1)
     assert np.all(model.llks(sp)[empty] == 0) and not inf.states()[empty].any()
@@ -155,7 +160,7 @@ def test_against_oracle(P, oracle, n, d, k):
     _show("   stats", serr)
     assert max(serr.values()) <= TOL, serr
     a, b = _layout(d, k)["totals"]
-    assert np.array_equal(_stats_raw(P, model, P.SparseDataset.from_dense(x))[a:b], np.isfinite(x).sum(axis=0))  # un-weighted: exact
+    assert np.array_equal(_stats_raw(P, model, P.SparseDataset.from_dense(x, **tiling))[a:b], np.isfinite(x).sum(axis=0))  # un-weighted: exact
 
     new, llk = model.iterate_with_llk(sp)
     merr = _model_errors(new, oracle.iterate(x, s, c, mu, w))
@@ -180,6 +185,10 @@ def test_against_oracle(P, oracle, n, d, k):
 
 @pytest.mark.parametrize("n,d,k", SHAPES, ids=IDS)
 def test_predict(P, oracle, n, d, k):
+    _check_predict(P, oracle, n, d, k)
+
+
+def _check_predict(P, oracle, n, d, k):
     x, w, (s, c, mu) = _case(n, d, k)
     e = _want(oracle, n, d, k)
     sp = P.SparseDataset.from_dense(x, w)
@@ -205,8 +214,12 @@ def test_predict(P, oracle, n, d, k):
 # ------------------------------------------------------------------ against the library's dense path
 @pytest.mark.parametrize("n,d,k", SHAPES[:-1] + [(64, 9, 0), (257, 300, 0)], ids=IDS[:-1] + ["64x9x0", "257x300x0"])
 def test_against_dense_path(P, oracle, n, d, k):
+    _check_against_dense_path(P, oracle, n, d, k)
+
+
+def _check_against_dense_path(P, oracle, n, d, k, **tiling):
     x, w, (s, c, mu) = _case(n, d, k)
-    sp = P.SparseDataset.from_dense(x, w)
+    sp = P.SparseDataset.from_dense(x, w, **tiling)
     ds = sp.to_dense()
     assert np.array_equal(np.isfinite(ds.numpy()), np.isfinite(x)) and np.array_equal(ds.weights(), w)
     model = P.PPCAModel(s, c, mu)
@@ -223,9 +236,36 @@ def test_against_dense_path(P, oracle, n, d, k):
     errs.update(_stats_errors(_stats_raw(P, model, sp), _dense_stats_raw(model, ds), scale, d, kk))
     new_s, new_d = model.iterate(sp), model.iterate(ds)
     errs.update({"it_" + key: v for key, v in _model_errors(new_s, (new_d.isotropic_noise, new_d.transform, new_d.mean)).items()})
-    _show("dense path %dx%dx%d" % (n, d, k), errs)
+    _show("dense path %dx%dx%d %s" % (n, d, k, tiling or ""), errs)
     assert max(errs.values()) <= TOL, errs
     assert new_s.state_size == k
+
+
+# ------------------------------------------------------------------ every state size
+SWEEP_N, SWEEP_D = S.SPARSE
+SWEEP_TILING = dict(block_rows=64, segment=8)  # three row blocks; columns of up to 148 entries cut into runs of 8
+
+
+@pytest.mark.parametrize("k", range(17))
+def test_state_size_sweep(P, oracle, k):
+    """Every instantiation of the row and the column kernel (k = 0 is the model without a transform) on rows in all three length bins
+    (tests/test_state_sizes_host.py), at the default tiling and at one with three row blocks and every long column cut into runs."""
+    check = _check_against_oracle if k else _check_against_dense_path  # (the oracle has no k = 0)
+    check(P, oracle, SWEEP_N, SWEEP_D, k)
+    check(P, oracle, SWEEP_N, SWEEP_D, k, **SWEEP_TILING)
+
+
+@pytest.mark.parametrize("k", range(17))
+def test_predict_state_size_sweep(P, oracle, k):
+    if k:
+        return _check_predict(P, oracle, SWEEP_N, SWEEP_D, k)
+    x, w, (s, c, mu) = _case(SWEEP_N, SWEEP_D, 0)  # no transform: the column's mean and sigma^2 at every position
+    rows, cols = np.nonzero(~np.isfinite(x) & (np.random.default_rng(11).random(x.shape) < 40.0 / SWEEP_D))
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=SWEEP_N))])
+    mean, var = P.PPCAModel(s, c, mu).predict(P.SparseDataset.from_dense(x, w), (indptr, cols))
+    errs = dict(mean=_rel(mean, mu[cols]), var=_rel(var, np.full(cols.size, s * s)))
+    _show("predict disjoint %dx%dx0 (%d entries)" % (SWEEP_N, SWEEP_D, rows.size), errs)
+    assert rows.size > 1000 and max(errs.values()) <= TOL, errs
 
 
 # ------------------------------------------------------------------ seams

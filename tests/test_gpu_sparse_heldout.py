@@ -15,6 +15,7 @@ import pytest
 
 import heldout_restatement as H
 import sparse_cases as SC
+import state_size_cases as S
 from test_gpu_heldout import _counts_match, _errors, _rel_rows, _rel_sums
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +82,17 @@ def _show(label, errs, bound):
 # ------------------------------------------------------------------ 1. against the restatement
 @pytest.mark.parametrize("n,d,k", SHAPES, ids=IDS)
 def test_score_matches_the_restatement(P, oracle, n, d, k):
+    _check_score(P, oracle, n, d, k)
+
+
+@pytest.mark.parametrize("k", range(17))
+def test_score_state_size_sweep(P, oracle, k):
+    """Every instantiation of the held-out row and column kernels, on the shape whose train rows fall in all three length bins at every
+    k (tests/test_state_sizes_host.py)."""
+    _check_score(P, oracle, *S.SPARSE, k)
+
+
+def _check_score(P, oracle, n, d, k):
     x, w, (s, c, mu), train, held, counts = _case(n, d, k)
     res = _want(oracle, n, d, k)
     tsp, hsp, m = P.SparseDataset.from_dense(train, w), P.SparseDataset.from_dense(held), P.PPCAModel(s, c, mu)

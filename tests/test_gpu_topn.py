@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import sparse_cases as SC
+import state_size_cases as S
 import topn_cases as TC
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +78,14 @@ def test_exact_against_predict(P, n, d, k):
     x, w, (s, c, mu) = _case(n, d, k)
     sp = P.SparseDataset.from_dense(x, w)
     _check_exact(P.PPCAModel(s, c, mu), sp, x, (1, 10, 64), "%dx%dx%d" % (n, d, k))
+
+
+@pytest.mark.parametrize("k", range(17))
+def test_exact_state_size_sweep(P, k):
+    """Every instantiation of the top-n kernel against predict, which tests/test_gpu_sparse.py holds to the oracle on the same case."""
+    x, w, (s, c, mu) = _case(*S.SPARSE, k)
+    sp = P.SparseDataset.from_dense(x, w)
+    _check_exact(P.PPCAModel(s, c, mu), sp, x, (10,), "%dx%dx%d" % (S.SPARSE + (k,)))
 
 
 # ------------------------------------------------------------------ 2. against the oracle
