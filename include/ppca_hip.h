@@ -586,6 +586,22 @@ int ppca_mix_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *m
                             const ppca_prior *prior, ppca_model *const *models_out, double *log_weights_out, double *llk_in);
 int ppca_mix_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models, const double *log_weights, int32_t n_models,
                             const int64_t *query_row_ptr, const int32_t *query_col, double *mean_host, double *var_host);
+/* ppca_topn_sparse for the mixture: the n_top best columns of every row under n_models components (as above: sp's
+ * output size, any state sizes <= 16, state size 0 as one zero column, any number of them).  The score of column j for row i is
+ * fma(kappa, sqrt(var), mean) with ppca_mix_sparse_predict's (mean, var) of position (i, j), bit for bit: with r_c = exp(log posterior
+ * of component c given the row's entries) and (m_c, v_c) ppca_sparse_predict's pair under component c, mean = r_0 m_0, then
+ * fma(r_c, m_c, mean) in index order; var likewise from the v_c; then var + s with s = fma(r_c, (m_c - mean)^2, s) from 0 in index
+ * order.  kappa = 0 ranks by the mean and forms or reads no covariance.  Candidates, exclude_observed, the order (score descending,
+ * equal scores by ascending column; NaN and -inf are not ranked), the outputs and their padding with -1 / NaN are ppca_topn_sparse's.
+ * Row weights play no part; an empty row ranks under the prior weights with z = 0, Sigma = I per component; a one-component mixture
+ * gives ppca_topn_sparse's columns and score bits.  The scratch is one block's states (and, with kappa != 0, covariances) of ALL
+ * components in the layout of the largest state size, and one weight per (row, component); no n x d buffer, no float atomics,
+ * bit-identical under any grid limit and block_rows.
+ * Preconditions, all checked before any device work: those of the four calls above, then 1 <= n_top <= 64, kappa finite, non-null
+ * outputs, candidates strictly increasing in [0, d) (else PPCA_ERR_INVALID).  (Named with the family first, like ppca_topn_sparse.) */
+int ppca_mix_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models, const double *log_weights, int32_t n_models,
+                         int32_t n_top, double kappa, int32_t exclude_observed, const int32_t *candidates, int64_t n_candidates,
+                         int32_t *cols_host, double *scores_host);
 /* The hold-out split of ppca_dataset_holdout_range on the pattern of row-compressed data, on host buffers (no GPU needed; DESIGN.md
  * 4.21).  row_ptr (n + 1, from 0, monotone) and col (>= 0) as above.  Entry e of row i, column j = col[e], global row
  * g = row_offset + i draws the word of the dense split, u = (row_word(row_key(seed, 8, g), j) >> 11) 2^-53, and

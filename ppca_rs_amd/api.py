@@ -517,7 +517,7 @@ class SparseDataset:
         # every pass written for the dense layout reaches its dataset through _h
         raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
                         "predict / recommend / heldout_score and PPCATrainer are, and PPCAMix.llk / llks / infer_cluster / iterate* / "
-                        "predict and PPCAMixTrainer")
+                        "predict / recommend and PPCAMixTrainer")
 
     @property
     def _sh(self):
@@ -904,6 +904,30 @@ class _DevModel:
             pass
 
 
+def _recommend_args(sparse, n, kappa, candidates):
+    """The argument checks PPCAModel.recommend and PPCAMix.recommend share, in their documented order -> (n, kappa, candidates int32 or
+    None); nothing here touches the library or a device."""
+    if not isinstance(sparse, SparseDataset):
+        raise TypeError("recommend takes a SparseDataset (from a Dataset or an array: SparseDataset.from_dense)")
+    n = int(n)
+    if not 1 <= n <= 64:
+        raise ValueError("n must lie in [1, 64]")
+    kappa = float(kappa)
+    if not math.isfinite(kappa):
+        raise ValueError("kappa must be finite")
+    cand = None
+    if candidates is not None:
+        cand = np.asarray(candidates)
+        if cand.ndim != 1 or (cand.size and not np.issubdtype(cand.dtype, np.integer)):
+            raise ValueError("candidates must be a 1-D integer array")
+        if cand.size and (cand.min() < 0 or cand.max() >= sparse._d):
+            raise ValueError(f"a candidate column lies outside [0, {sparse._d})")
+        if np.any(np.diff(cand) <= 0):
+            raise ValueError("candidates must be strictly increasing (sorted, no duplicates)")
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+    return n, kappa, cand
+
+
 class PPCAModel:
     """Immutable PPCA model (ppca_model.rs:18-48; src/python_bindings.rs:367-533).
 
@@ -1105,24 +1129,7 @@ class PPCAModel:
         (N, n), scores float64 (N, n)); a row with fewer than n candidates is padded at the end with -1 and NaN.  1 <= n <= 64.  Row
         weights play no part, an empty row ranks with z = 0, Sigma = I, and no N x d array is formed.  Rows are independent: a shard
         calls this on its own rows."""
-        if not isinstance(sparse, SparseDataset):
-            raise TypeError("recommend takes a SparseDataset (from a Dataset or an array: SparseDataset.from_dense)")
-        n = int(n)
-        if not 1 <= n <= 64:
-            raise ValueError("n must lie in [1, 64]")
-        kappa = float(kappa)
-        if not math.isfinite(kappa):
-            raise ValueError("kappa must be finite")
-        cand = None
-        if candidates is not None:
-            cand = np.asarray(candidates)
-            if cand.ndim != 1 or (cand.size and not np.issubdtype(cand.dtype, np.integer)):
-                raise ValueError("candidates must be a 1-D integer array")
-            if cand.size and (cand.min() < 0 or cand.max() >= sparse._d):
-                raise ValueError(f"a candidate column lies outside [0, {sparse._d})")
-            if np.any(np.diff(cand) <= 0):
-                raise ValueError("candidates must be strictly increasing (sorted, no duplicates)")
-            cand = np.ascontiguousarray(cand, dtype=np.int32)
+        n, kappa, cand = _recommend_args(sparse, n, kappa, candidates)
         if self.output_size != sparse._d:
             raise ValueError(f"dataset has {sparse._d} columns but the model has output size {self.output_size}")
         if self.state_size > 16:  # (the library's own answer, given here so that it comes before the first touch of a device)
@@ -2453,6 +2460,29 @@ class PPCAMix:
         devs, arr = self._handles(ctx)
         check(lib().ppca_mix_sparse_predict(ctx.handle, sparse._sh, arr, ptr(self._lw), len(devs), ptr(ip), ptr(ix), ptr(mean), ptr(var)))
         return mean, var
+
+    def recommend(self, sparse: "SparseDataset", n: int, *, kappa: float = 0.0, exclude_observed: bool = True, candidates=None):
+        """PPCAModel.recommend for the mixture, in one device pass: for every row of row-compressed data the n columns
+        the mixture ranks highest.  The score of column j for row i is mean_ij + kappa sqrt(var_ij) with exactly this mixture's
+        `predict`'s two values (the posterior-weighted mean; the weighted variances plus the spread of the components' means), so
+        kappa = 0 ranks by the mixture's predictive mean and forms no covariance.  Arguments, checks, order (score descending, equal
+        scores by ascending column) and padding (-1 / NaN) are PPCAModel.recommend's; returns (columns int32 (N, n), scores float64
+        (N, n)).  Row weights play no part, an empty row ranks under the prior weights, a one-component mixture gives its model's
+        `recommend` bit for bit, and no N x d array is formed."""
+        n, kappa, cand = _recommend_args(sparse, n, kappa, candidates)
+        if self.output_size != sparse._d:
+            raise ValueError(f"dataset has {sparse._d} columns but the mixture has output size {self.output_size}")
+        if max(self.state_sizes) > 16:  # (the library's own answer, given here so that it comes before the first touch of a device)
+            raise _lib.PPCAError(-3, f"state size {max(self.state_sizes)} is not supported on sparse data: the kernels cover k <= 16")
+        cols, scores = np.empty((len(sparse), n), dtype=np.int32), np.empty((len(sparse), n))
+        if len(sparse) == 0:
+            return cols, scores
+        ctx = sparse._ctx
+        devs, arr = self._handles(ctx)
+        cbuf = cand if cand is None or cand.size else np.zeros(1, dtype=np.int32)  # (an empty list is not NULL = every column)
+        check(lib().ppca_mix_topn_sparse(ctx.handle, sparse._sh, arr, ptr(self._lw), len(devs), n, kappa, 1 if exclude_observed else 0,
+                                         ptr(cbuf), 0 if cand is None else cand.size, ptr(cols), ptr(scores)))
+        return cols, scores
 
     def _iterate(self, dataset: Dataset, prior: Optional[Prior], want_llk: bool):
         if len(dataset) == 0:

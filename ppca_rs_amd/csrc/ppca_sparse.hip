@@ -55,6 +55,13 @@
 //     bit; sparse_row_kernel itself is left as it was.  The step is ppca_host::mix_em_step's sequence with sp_accumulate under each
 //     component's weight vector.
 // sparse_mix_predict_kernel, sparse_mix_spread_kernel  the mixture predictive, component by component in index order per query entry.
+//
+// The mixture's top-n ranking (ppca_mix_topn_sparse).  The posteriors once; per block sparse_mix_resp_kernel
+// (r = exp(log posterior)), sparse_row_kernel<k_c> per component into one scratch in the layout of the largest state size
+// (sparse_pad_kernel for a smaller component), then
+// sparse_mix_topn_kernel<K, VAR, R>  sparse_topn_kernel's work items, lists and windows with a loop over the components per 64 columns:
+//     the score is fma(kappa, sqrt(var), mean) with sparse_mix_predict_kernel / sparse_mix_spread_kernel's (mean, var), operation for
+//     operation; sparse_topn_merge_kernel when the columns were split.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -909,6 +916,187 @@ __global__ __launch_bounds__(256) void sparse_topn_merge_kernel(const double *__
     }
 }
 
+// ---- the mixture's top-n ranking
+struct SpMixComp {    // a component as sparse_mix_topn_kernel<K, ..> reads it
+    const double *C;  // d x K: the component's own C, or its copy with the rows zero-padded from k_c to K
+    const double *mu;
+    const double *model;  // sigma^2 at [1]
+};
+
+// dst (rows x kout, or rows x kout x kout with `square`) = src (rows x kin, or rows x kin x kin) with zeros behind: a component of
+// a smaller state size in the layout of the largest (a trailing zero term leaves an fma chain that started at +0 as it was)
+__global__ __launch_bounds__(256) void sparse_pad_kernel(const double *__restrict__ src, int64_t rows, int kin, int kout, int square,
+                                                         double *__restrict__ dst) {
+    const int64_t per = square ? (int64_t)kout * kout : kout, pin = square ? (int64_t)kin * kin : kin, len = rows * per;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+        const int64_t row = i / per;
+        const int e = (int)(i - row * per), t = square ? e / kout : 0, u = square ? e % kout : e;
+        dst[i] = (t < kin && u < kin) ? src[row * pin + (square ? t * kin + u : u)] : 0.0;
+    }
+}
+
+// r[i] = exp(logpost[i]): the factor of sparse_mix_predict_kernel / sparse_mix_spread_kernel, once per (row, component)
+__global__ __launch_bounds__(256) void sparse_mix_resp_kernel(const double *__restrict__ logpost, int64_t len, double *__restrict__ r) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) r[i] = exp(logpost[i]);
+}
+
+// The mixture's combination, in the operations of sparse_mix_predict_kernel and sparse_mix_spread_kernel.  There the steps are
+// separated by stores and loads; here they meet in one kernel, where the compiler would contract across them (r0 v0 + s into one
+// fused operation at one component, for one).  So: no contraction in these three, and the multiply-adds of those kernels as fma.
+__device__ __forceinline__ void mix_top_add(bool first, double r, double m, double v, bool with_var, double &mean, double &var) {
+#pragma clang fp contract(off)
+    mean = first ? r * m : fma(r, m, mean);
+    if (with_var) var = first ? r * v : fma(r, v, var);
+}
+__device__ __forceinline__ double mix_top_spread(double r, double m, double mean, double s) {
+#pragma clang fp contract(off)
+    const double dv = m - mean;
+    return fma(r, dv * dv, s);
+}
+__device__ __forceinline__ double mix_top_score(double kappa, double var, double s, double mean) {
+#pragma clang fp contract(off)
+    const double total = var + s;
+    return fma(kappa, sqrt(total), mean);
+}
+
+// sparse_topn_kernel for the mixture: the same work items, tile walk, lists and windows; per 64 candidate positions the wave loops
+// over the components.  Lane l holds c_j and mean_j of ONE component at a time (the next component's, or the next tile's first, is
+// loaded while this one is used); z, Sigma (scratch of all components: component c's rows at c * cap) and r of a row are
+// wave-uniform operands.  (m_c, v_c) are predict_entry's, multiply-add for multiply-add, at the largest state size K: a smaller
+// component is zero-padded (sparse_pad_kernel).  mean[R] and var[R] add the components in index order.  With VAR the spread needs
+// every m_c again once the mean is final: a second loop over the components recomputes it (K multiply-adds beside the K^2 + 2 K of
+// the first: no m_c is kept, so nm is not bounded by registers or LDS).
+// floor = -inf, the threshold of an empty list, is an argument, not a literal: from K = 13 on the compiler holds the R = 16 thresholds
+// in scalar registers that it fills with one 64-bit move each, and the move's 32-bit literal field keeps the low half of the
+// constant -- 0, so columns with a score below 0.0 never reached a list that was not yet full.
+template <int K, bool VAR, int R>
+__global__ __launch_bounds__(256) void sparse_mix_topn_kernel(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
+                                                              const int32_t *__restrict__ cand, const SpMixComp *__restrict__ comps,
+                                                              const double *__restrict__ resp, const double *__restrict__ states,
+                                                              const double *__restrict__ covs, double *__restrict__ ps,
+                                                              int32_t *__restrict__ pc, SpTopDims g, int nm, int64_t cap, double floor) {
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = g.n_top;
+    const int64_t ntiles = (g.rows + R - 1) / R, nitems = ntiles * g.nchunks;
+    const int nsteps = VAR ? 2 * nm : nm;
+    for (int64_t item = (int64_t)blockIdx.x * 4 + wid; item < nitems; item += (int64_t)gridDim.x * 4) {  // (uniform over the wave)
+        const int ch = (int)(item / ntiles);
+        const int64_t r0 = (item % ntiles) * R;
+        const int nr = (int)(g.rows - r0 < R ? g.rows - r0 : R);
+        double ls[R], thr[R];
+        int lc[R], rc[R], win[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            ls[r] = -INFINITY;
+            thr[r] = floor;
+            lc[r] = -1;
+            rc[r] = INT_MAX;
+            win[r] = 0;
+        }
+        const int64_t p0 = (int64_t)ch * g.chunk, p1 = p0 + g.chunk < g.nc ? p0 + g.chunk : g.nc;
+        if (g.exclude && p0 < p1) {
+            const int jstart = cand ? cand[p0] : (int)p0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= nr) continue;  // (uniform)
+                const int64_t row = g.row0 + r0 + r, e0 = row_ptr[row];
+                const int m = (int)(row_ptr[row + 1] - e0);
+                win[r] = (m > 64 && p0 > 0) ? top_window_start(col, e0, m, jstart) : 0;
+                rc[r] = top_window(col, e0, m, win[r], lane);
+            }
+        }
+        auto column = [&](int64_t base, bool &valid, int &j) {
+            const int64_t idx = base + lane;
+            valid = idx < p1;
+            j = valid ? (cand ? cand[idx] : (int)idx) : 0;
+        };
+        auto load = [&](int j, int comp, double *c, double &muj) {
+            const double *cj = comps[comp].C + (int64_t)j * K;
+#pragma unroll
+            for (int t = 0; t < K; ++t) c[t] = cj[t];
+            muj = comps[comp].mu[j];
+        };
+        bool valid = false, nvalid = false;
+        int j = 0, nj = 0;
+        double c[K], ncv[K], muj = 0.0, nmuj = 0.0;
+        if (p0 < p1) {
+            column(p0, valid, j);
+            load(j, 0, c, muj);
+        }
+        for (int64_t base = p0; base < p1; base += 64) {
+            const bool more = base + 64 < p1;
+            if (more) column(base + 64, nvalid, nj);
+            double mean[R], var[R], spread[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) mean[r] = var[r] = spread[r] = 0.0;
+#pragma unroll 1
+            for (int step = 0; step < nsteps; ++step) {  // (uniform) the components, then -- VAR -- the components again
+                const bool again = step >= nm;
+                const int comp = again ? step - nm : step;
+                if (step + 1 < nsteps)
+                    load(j, step + 1 >= nm ? step + 1 - nm : step + 1, ncv, nmuj);
+                else if (more)
+                    load(nj, 0, ncv, nmuj);
+                const double s2 = comps[comp].model[1];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (r >= nr) continue;  // (uniform)
+                    const int64_t at = (int64_t)comp * cap + r0 + r;
+                    const double *z = states + at * K;
+                    const double w = resp[(r0 + r) * nm + comp];
+                    double dot = 0.0;
+#pragma unroll
+                    for (int t = 0; t < K; ++t) dot = fma(c[t], z[t], dot);
+                    const double m = muj + dot;
+                    if (VAR && again) {
+                        spread[r] = mix_top_spread(w, m, mean[r], spread[r]);
+                        continue;
+                    }
+                    double v = 0.0;
+                    if (VAR) {
+                        const double *S = covs + at * (K * K);
+                        double q = 0.0;
+#pragma unroll
+                        for (int t = 0; t < K; ++t) {
+                            double sc = 0.0;
+#pragma unroll
+                            for (int u = 0; u < K; ++u) sc = fma(S[t * K + u], c[u], sc);
+                            q = fma(c[t], sc, q);
+                        }
+                        v = q + s2;
+                    }
+                    mix_top_add(comp == 0, w, m, v, VAR, mean[r], var[r]);
+                }
+                muj = nmuj;
+#pragma unroll
+                for (int t = 0; t < K; ++t) c[t] = ncv[t];
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= nr) continue;  // (uniform)
+                const double score = VAR ? mix_top_score(g.kappa, var[r], spread[r], mean[r]) : mean[r];
+                const bool beat = valid && score > thr[r];
+                if (__ballot(beat)) {
+                    const int64_t row = g.row0 + r0 + r, e0 = row_ptr[row];
+                    top_offer(ls[r], lc[r], thr[r], beat, score, j, g.exclude != 0, rc[r], win[r], col, e0, (int)(row_ptr[row + 1] - e0), lane, n);
+                }
+            }
+            valid = nvalid;
+            j = nj;
+        }
+        if (lane < n) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= nr) continue;
+                const int64_t at = ((r0 + r) * g.nchunks + ch) * n + lane;
+                ps[at] = (g.final && lc[r] < 0) ? (double)NAN : ls[r];
+                pc[at] = lc[r];
+            }
+        }
+    }
+}
+
 
 #define SP_DISPATCH(k, F, ...)                  \
     switch (k) {                                \
@@ -997,6 +1185,35 @@ hipError_t topn_t(const SpTopPtrs &p, const SpTopDims &g, bool var, int n_cu, hi
     return hipGetLastError();
 }
 hipError_t launch_topn(int k, const SpTopPtrs &p, const SpTopDims &g, bool var, int n_cu, hipStream_t s) { SP_DISPATCH(k, topn_t, p, g, var, n_cu, s); }
+struct SpMixTopPtrs {
+    const int64_t *row_ptr;
+    const int32_t *col, *cand;
+    const SpMixComp *comps;
+    const double *resp, *states, *covs;
+    double *ps;
+    int32_t *pc;
+    int nm;
+    int64_t cap;  // rows of a component's slice of states / covs
+};
+template <int K>
+hipError_t mix_topn_t(const SpMixTopPtrs &p, const SpTopDims &g, bool var, int n_cu, hipStream_t s) {
+    const int64_t items = sp_top_tiles(g.rows, var) * g.nchunks;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((items + 3) / 4, (int64_t)std::max(n_cu, 1) * 8));
+    if (var)
+        hipLaunchKernelGGL((sparse_mix_topn_kernel<K, true, SP_TOP_RV>), dim3((unsigned)grid), dim3(256), 0, s, p.row_ptr, p.col, p.cand,
+                           p.comps, p.resp, p.states, p.covs, p.ps, p.pc, g, p.nm, p.cap, -(double)INFINITY);
+    else
+        hipLaunchKernelGGL((sparse_mix_topn_kernel<K, false, SP_TOP_R>), dim3((unsigned)grid), dim3(256), 0, s, p.row_ptr, p.col, p.cand,
+                           p.comps, p.resp, p.states, p.covs, p.ps, p.pc, g, p.nm, p.cap, -(double)INFINITY);
+    return hipGetLastError();
+}
+hipError_t launch_mix_topn(int k, const SpMixTopPtrs &p, const SpTopDims &g, bool var, int n_cu, hipStream_t s) {
+    SP_DISPATCH(k, mix_topn_t, p, g, var, n_cu, s);
+}
+// one of the two element-wise helpers of the mixture's top-n, over len outputs
+int sp_elementwise_grid(int64_t len, int n_cu) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((len + 255) / 256, (int64_t)std::max(n_cu, 1) * 16));
+}
 
 // ------------------------------------------------------------------ host: validation and the inverted index
 int sp_validate(int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *col, const double *val) {
@@ -1691,11 +1908,12 @@ extern "C" int ppca_mix_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, ppca_mode
     return PPCA_OK;
 }
 
-// ------------------------------------------------------------------ top-n ranking
-extern "C" int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, int32_t n_top, double kappa, int32_t exclude_observed,
-                                const int32_t *candidates, int64_t n_candidates, int32_t *cols_host, double *scores_host) {
-    if (int rc = sp_check(ctx, sp, model)) return rc;
-    const SpCore &c = *sp->core;
+// ------------------------------------------------------------------ top-n ranking (DESIGN.md sections 4.22 and 4.24)
+namespace {
+
+// the arguments that ppca_topn_sparse and ppca_mix_topn_sparse share, in the order their checks are documented
+int sp_top_check(const SpCore &c, int32_t n_top, double kappa, const int32_t *candidates, int64_t n_candidates, const int32_t *cols_host,
+                 const double *scores_host) {
     if (n_top < 1 || n_top > SP_TOP_MAX) return fail(PPCA_ERR_INVALID, "n_top = %d is outside [1, %d]", n_top, SP_TOP_MAX);
     if (!std::isfinite(kappa)) return fail(PPCA_ERR_INVALID, "kappa must be finite");
     if (!cols_host || !scores_host) return fail(PPCA_ERR_INVALID, "null output");
@@ -1705,34 +1923,86 @@ extern "C" int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model
             if (candidates[i] < 0 || candidates[i] >= c.d) return fail(PPCA_ERR_INVALID, "candidate column %d is outside [0, %d)", candidates[i], c.d);
             if (i > 0 && candidates[i] <= candidates[i - 1]) return fail(PPCA_ERR_INVALID, "candidate columns are not strictly increasing at %lld", (long long)i);
         }
-    USE_CTX(ctx);
-    const int k = model->k, nc = candidates ? (int)n_candidates : c.d;
-    const bool var = kappa != 0.0;
-    // the column split: chunks so that (row tiles) x (chunks) fills the device, none under SP_TOP_MINCHUNK positions.  The order of the
-    // list is total, so the result does not depend on this choice.
-    auto chunks_of = [&](int64_t rows, int *chunk) {
-        const int64_t target = (int64_t)std::max(ctx->n_cu, 1) * 32;
-        int64_t nch = std::max<int64_t>(1, std::min<int64_t>(target / sp_top_tiles(rows, var), nc / SP_TOP_MINCHUNK));
-        const int64_t per = std::max<int64_t>(64, ((nc + nch - 1) / nch + 63) / 64 * 64);
-        *chunk = (int)per;
-        return (int)std::max<int64_t>(1, (nc + per - 1) / per);
-    };
+    return PPCA_OK;
+}
+
+// the column split: chunks so that (row tiles) x (chunks) fills the device, none under SP_TOP_MINCHUNK positions.  The order of the
+// list is total, so the result does not depend on this choice.
+int sp_top_chunks(int n_cu, int64_t rows, bool var, int nc, int *chunk) {
+    const int64_t target = (int64_t)std::max(n_cu, 1) * 32;
+    int64_t nch = std::max<int64_t>(1, std::min<int64_t>(target / sp_top_tiles(rows, var), nc / SP_TOP_MINCHUNK));
+    const int64_t per = std::max<int64_t>(64, ((nc + nch - 1) / nch + 63) / 64 * 64);
+    *chunk = (int)per;
+    return (int)std::max<int64_t>(1, (nc + per - 1) / per);
+}
+
+// the result and scratch of a top-n call: one block's lists and, where a block's columns are split, its chunk lists
+struct SpTopOut {
+    BufRef os, oc, ps, pc;
+};
+int sp_top_out(const ppca_ctx *ctx, const SpCore &c, int n_top, bool var, int nc, SpTopOut *o) {
     int64_t part_len = 0;
     for (const SpBlock &b : c.blocks) {
         int chunk;
-        const int nch = chunks_of(b.rows, &chunk);
+        const int nch = sp_top_chunks(ctx->n_cu, b.rows, var, nc, &chunk);
         if (nch > 1) part_len = std::max(part_len, b.rows * nch * n_top);
     }
-    BufRef st, cv, cd, os, oc, ps, pc;
+    if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * n_top, &o->os)) return rc;
+    if (int rc = dev_alloc(sizeof(int32_t) * (size_t)c.max_rows * n_top, &o->oc)) return rc;
+    if (part_len > 0) {
+        if (int rc = dev_alloc(sizeof(double) * (size_t)part_len, &o->ps)) return rc;
+        if (int rc = dev_alloc(sizeof(int32_t) * (size_t)part_len, &o->pc)) return rc;
+    }
+    return PPCA_OK;
+}
+SpTopDims sp_top_dims(const ppca_ctx *ctx, const SpCore &c, const SpBlock &b, int n_top, double kappa, int exclude_observed, int nc) {
+    SpTopDims g{};
+    g.row0 = b.row0;
+    g.rows = b.rows;
+    g.d = c.d;
+    g.nc = nc;
+    g.nchunks = sp_top_chunks(ctx->n_cu, b.rows, kappa != 0.0, nc, &g.chunk);
+    g.n_top = n_top;
+    g.exclude = exclude_observed ? 1 : 0;
+    g.final = g.nchunks == 1;
+    g.kappa = kappa;
+    return g;
+}
+// behind a block's ranking kernel: the merge of its chunk lists where the columns were split, then the block's rows of the result
+int sp_top_finish(ppca_ctx *ctx, const SpBlock &b, const SpTopDims &g, const SpTopOut &o, int32_t *cols_host, double *scores_host) {
+    const int n_top = g.n_top;
+    if (!g.final) {
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((b.rows + 3) / 4, (int64_t)std::max(ctx->n_cu, 1) * 8));
+        hipLaunchKernelGGL(sparse_topn_merge_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, static_cast<const double *>(o.ps->p),
+                           static_cast<const int32_t *>(o.pc->p), b.rows, g.nchunks, n_top, static_cast<double *>(o.os->p),
+                           static_cast<int32_t *>(o.oc->p));
+        if (hipGetLastError() != hipSuccess) return fail(PPCA_ERR_HIP, "top-n merge launch failed");
+    }
+    if (hipMemcpyAsync(scores_host + b.row0 * n_top, o.os->p, sizeof(double) * (size_t)b.rows * n_top, hipMemcpyDeviceToHost, ctx->stream) !=
+            hipSuccess ||
+        hipMemcpyAsync(cols_host + b.row0 * n_top, o.oc->p, sizeof(int32_t) * (size_t)b.rows * n_top, hipMemcpyDeviceToHost, ctx->stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)  // (the next block overwrites the scratch)
+        return fail(PPCA_ERR_HIP, "top-n failed: %s", hipGetErrorString(hipGetLastError()));
+    return PPCA_OK;
+}
+
+}  // namespace
+
+extern "C" int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, int32_t n_top, double kappa, int32_t exclude_observed,
+                                const int32_t *candidates, int64_t n_candidates, int32_t *cols_host, double *scores_host) {
+    if (int rc = sp_check(ctx, sp, model)) return rc;
+    const SpCore &c = *sp->core;
+    if (int rc = sp_top_check(c, n_top, kappa, candidates, n_candidates, cols_host, scores_host)) return rc;
+    USE_CTX(ctx);
+    const int k = model->k, nc = candidates ? (int)n_candidates : c.d;
+    const bool var = kappa != 0.0;
+    BufRef st, cv, cd;
+    SpTopOut o;
     if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * k, &st)) return rc;
     if (var)
         if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * k * k, &cv)) return rc;
-    if (int rc = dev_alloc(sizeof(double) * (size_t)c.max_rows * n_top, &os)) return rc;
-    if (int rc = dev_alloc(sizeof(int32_t) * (size_t)c.max_rows * n_top, &oc)) return rc;
-    if (part_len > 0) {
-        if (int rc = dev_alloc(sizeof(double) * (size_t)part_len, &ps)) return rc;
-        if (int rc = dev_alloc(sizeof(int32_t) * (size_t)part_len, &pc)) return rc;
-    }
+    if (int rc = sp_top_out(ctx, c, n_top, var, nc, &o)) return rc;
     int rc = PPCA_OK;
     if (candidates) rc = sp_upload(ctx, candidates, sizeof(int32_t) * (size_t)n_candidates, &cd);
     for (size_t bi = 0; bi < c.blocks.size() && !rc; ++bi) {
@@ -1740,16 +2010,7 @@ extern "C" int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model
         rc = sp_rows_of_block(ctx, sp, b, model, nullptr, static_cast<double *>(st->p), var ? static_cast<double *>(cv->p) : nullptr, nullptr,
                               nullptr);
         if (rc) break;
-        SpTopDims g{};
-        g.row0 = b.row0;
-        g.rows = b.rows;
-        g.d = c.d;
-        g.nc = nc;
-        g.nchunks = chunks_of(b.rows, &g.chunk);
-        g.n_top = n_top;
-        g.exclude = exclude_observed ? 1 : 0;
-        g.final = g.nchunks == 1;
-        g.kappa = kappa;
+        const SpTopDims g = sp_top_dims(ctx, c, b, n_top, kappa, exclude_observed, nc);
         SpTopPtrs p{};
         p.row_ptr = static_cast<const int64_t *>(c.row_ptr->p);
         p.col = static_cast<const int32_t *>(c.col->p);
@@ -1757,32 +2018,124 @@ extern "C" int ppca_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model
         p.model = model->p();
         p.states = static_cast<const double *>(st->p);
         p.covs = var ? static_cast<const double *>(cv->p) : nullptr;
-        p.ps = static_cast<double *>(g.final ? os->p : ps->p);
-        p.pc = static_cast<int32_t *>(g.final ? oc->p : pc->p);
+        p.ps = static_cast<double *>(g.final ? o.os->p : o.ps->p);
+        p.pc = static_cast<int32_t *>(g.final ? o.oc->p : o.pc->p);
         if (launch_topn(k, p, g, var, ctx->n_cu, ctx->stream) != hipSuccess) {
             rc = fail(PPCA_ERR_HIP, "top-n launch failed");
             break;
         }
-        if (!g.final) {
-            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((b.rows + 3) / 4, (int64_t)std::max(ctx->n_cu, 1) * 8));
-            hipLaunchKernelGGL(sparse_topn_merge_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, static_cast<const double *>(ps->p),
-                               static_cast<const int32_t *>(pc->p), b.rows, g.nchunks, (int)n_top, static_cast<double *>(os->p),
-                               static_cast<int32_t *>(oc->p));
-            if (hipGetLastError() != hipSuccess) {
-                rc = fail(PPCA_ERR_HIP, "top-n merge launch failed");
-                break;
-            }
-        }
-        if (hipMemcpyAsync(scores_host + b.row0 * n_top, os->p, sizeof(double) * (size_t)b.rows * n_top, hipMemcpyDeviceToHost, ctx->stream) !=
-                hipSuccess ||
-            hipMemcpyAsync(cols_host + b.row0 * n_top, oc->p, sizeof(int32_t) * (size_t)b.rows * n_top, hipMemcpyDeviceToHost, ctx->stream) !=
-                hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)  // (the next block overwrites the scratch)
-            rc = fail(PPCA_ERR_HIP, "top-n failed: %s", hipGetErrorString(hipGetLastError()));
+        rc = sp_top_finish(ctx, b, g, o, cols_host, scores_host);
     }
     const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the upload reads the caller's buffer)
     if (rc) return rc;
     if (e != hipSuccess) return fail(PPCA_ERR_HIP, "top-n failed: %s", hipGetErrorString(e));
+    return PPCA_OK;
+}
+
+// The mixture's: the posteriors once, then per block r = exp(log posterior), every component's row pass into
+// ONE scratch (component c's rows at c * max_rows, in the layout of the largest state size K), sparse_mix_topn_kernel<K, ..>, and the
+// merge and download of ppca_topn_sparse.
+extern "C" int ppca_mix_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *models, const double *log_weights, int32_t n_models,
+                                    int32_t n_top, double kappa, int32_t exclude_observed, const int32_t *candidates, int64_t n_candidates,
+                                    int32_t *cols_host, double *scores_host) {
+    if (int rc = sp_mix_check(ctx, sp, models, log_weights, n_models)) return rc;
+    const SpCore &c = *sp->core;
+    if (int rc = sp_top_check(c, n_top, kappa, candidates, n_candidates, cols_host, scores_host)) return rc;
+    USE_CTX(ctx);
+    const int nm = n_models, nc = candidates ? (int)n_candidates : c.d;
+    const bool var = kappa != 0.0;
+    int K = 1, ksmall = 0;  // the largest state size, and the largest below it (0: the components agree)
+    for (int e = 0; e < nm; ++e) K = std::max(K, models[e]->k);
+    for (int e = 0; e < nm; ++e)
+        if (models[e]->k < K) ksmall = std::max(ksmall, models[e]->k);
+    const size_t cap = (size_t)c.max_rows;
+    // every device block of the call, before its first launch
+    SpMixDev m;
+    if (int rc = sp_mix_blocks(ctx, c.n, nm, true, &m)) return rc;
+    BufRef st, cv, tst, tcv, resp, cd, table;
+    std::vector<BufRef> padded((size_t)nm);
+    SpTopOut o;
+    if (int rc = dev_alloc(sizeof(double) * cap * nm * K, &st)) return rc;
+    if (var)
+        if (int rc = dev_alloc(sizeof(double) * cap * nm * K * K, &cv)) return rc;
+    if (ksmall > 0) {  // a smaller component's row pass writes its own layout here; sparse_pad_kernel moves it
+        if (int rc = dev_alloc(sizeof(double) * cap * ksmall, &tst)) return rc;
+        if (var)
+            if (int rc = dev_alloc(sizeof(double) * cap * ksmall * ksmall, &tcv)) return rc;
+    }
+    if (int rc = dev_alloc(sizeof(double) * cap * nm, &resp)) return rc;
+    if (int rc = dev_alloc(sizeof(SpMixComp) * (size_t)nm, &table)) return rc;
+    for (int e = 0; e < nm; ++e)
+        if (models[e]->k < K)
+            if (int rc = dev_alloc(sizeof(double) * (size_t)c.d * K, &padded[e])) return rc;
+    if (int rc = sp_top_out(ctx, c, n_top, var, nc, &o)) return rc;
+    std::vector<SpMixComp> comps((size_t)nm);  // (read by the upload: alive until the synchronisation below)
+    int rc = PPCA_OK;
+    for (int e = 0; e < nm && !rc; ++e) {
+        const int ke = models[e]->k;
+        const double *mp = models[e]->p();
+        comps[e].C = mp + MODEL_HDR;
+        comps[e].mu = mp + MODEL_HDR + (int64_t)c.d * ke;
+        comps[e].model = mp;
+        if (ke < K) {
+            double *pd = static_cast<double *>(padded[e]->p);
+            hipLaunchKernelGGL(sparse_pad_kernel, dim3((unsigned)sp_elementwise_grid((int64_t)c.d * K, ctx->n_cu)), dim3(256), 0, ctx->stream,
+                               comps[e].C, (int64_t)c.d, ke, K, 0, pd);
+            if (hipGetLastError() != hipSuccess) rc = fail(PPCA_ERR_HIP, "mixture top-n launch failed");
+            comps[e].C = pd;
+        }
+    }
+    SpMixComp *table_dev = static_cast<SpMixComp *>(table->p);
+    if (!rc && hipMemcpyAsync(table_dev, comps.data(), sizeof(SpMixComp) * (size_t)nm, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = fail(PPCA_ERR_HIP, "upload failed");
+    if (!rc && candidates) rc = sp_upload(ctx, candidates, sizeof(int32_t) * (size_t)n_candidates, &cd);
+    if (!rc) rc = sp_mix_posteriors(ctx, sp, models, log_weights, nm, m);
+    double *stp = static_cast<double *>(st->p), *cvp = var ? static_cast<double *>(cv->p) : nullptr, *rp = static_cast<double *>(resp->p);
+    for (size_t bi = 0; bi < c.blocks.size() && !rc; ++bi) {
+        const SpBlock &b = c.blocks[bi];
+        hipLaunchKernelGGL(sparse_mix_resp_kernel, dim3((unsigned)sp_elementwise_grid(b.rows * nm, ctx->n_cu)), dim3(256), 0, ctx->stream,
+                           m.logpost + b.row0 * nm, b.rows * nm, rp);
+        if (hipGetLastError() != hipSuccess) rc = fail(PPCA_ERR_HIP, "mixture top-n launch failed");
+        for (int e = 0; e < nm && !rc; ++e) {
+            const int ke = models[e]->k;
+            double *zs = stp + cap * e * K, *ss = var ? cvp + cap * e * K * K : nullptr;
+            if (ke == K) {
+                rc = sp_rows_of_block(ctx, sp, b, models[e], nullptr, zs, ss, nullptr, nullptr);
+                continue;
+            }
+            double *tz = static_cast<double *>(tst->p), *ts = var ? static_cast<double *>(tcv->p) : nullptr;
+            rc = sp_rows_of_block(ctx, sp, b, models[e], nullptr, tz, ts, nullptr, nullptr);
+            if (rc) break;
+            hipLaunchKernelGGL(sparse_pad_kernel, dim3((unsigned)sp_elementwise_grid(b.rows * K, ctx->n_cu)), dim3(256), 0, ctx->stream, tz, b.rows,
+                               ke, K, 0, zs);
+            if (var)
+                hipLaunchKernelGGL(sparse_pad_kernel, dim3((unsigned)sp_elementwise_grid(b.rows * K * K, ctx->n_cu)), dim3(256), 0, ctx->stream, ts,
+                                   b.rows, ke, K, 1, ss);
+            if (hipGetLastError() != hipSuccess) rc = fail(PPCA_ERR_HIP, "mixture top-n launch failed");
+        }
+        if (rc) break;
+        const SpTopDims g = sp_top_dims(ctx, c, b, n_top, kappa, exclude_observed, nc);
+        SpMixTopPtrs p{};
+        p.row_ptr = static_cast<const int64_t *>(c.row_ptr->p);
+        p.col = static_cast<const int32_t *>(c.col->p);
+        p.cand = candidates ? static_cast<const int32_t *>(cd->p) : nullptr;
+        p.comps = table_dev;
+        p.resp = rp;
+        p.states = stp;
+        p.covs = cvp;
+        p.ps = static_cast<double *>(g.final ? o.os->p : o.ps->p);
+        p.pc = static_cast<int32_t *>(g.final ? o.oc->p : o.pc->p);
+        p.nm = nm;
+        p.cap = (int64_t)cap;
+        if (launch_mix_topn(K, p, g, var, ctx->n_cu, ctx->stream) != hipSuccess) {
+            rc = fail(PPCA_ERR_HIP, "mixture top-n launch failed");
+            break;
+        }
+        rc = sp_top_finish(ctx, b, g, o, cols_host, scores_host);
+    }
+    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's buffer and `comps`)
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(PPCA_ERR_HIP, "mixture top-n failed: %s", hipGetErrorString(e));
     return PPCA_OK;
 }
 

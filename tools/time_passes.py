@@ -24,7 +24,8 @@ extrapolated covariance diagonal and both downloads).  `--sparse DENSITY` / `--s
 SparseDataset (see sparse_legs); with `--sparse-heldout` beside either, ONLY the legs of held-out scoring on that
 data (see sparse_heldout_legs); with `--sparse-topn N_TOP` beside either, ONLY the legs of PPCAModel.recommend on that
 data (see sparse_topn_legs); with `--mix NM` beside either, ONLY the legs of PPCAMix on that data (see
-sparse_mix_legs)."""
+sparse_mix_legs); with `--sparse-topn N_TOP` and `--mix NM` together, ONLY the legs of PPCAMix.recommend (see
+sparse_mix_topn_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -355,6 +356,78 @@ def sparse_mix_legs(nm, reps=5):
         print(f"  {what}: {med[i] / med[i + 1]:.3f}  (run-to-run spread of the two legs: {spread[i]:.1%}, {spread[i + 1]:.1%})", flush=True)
 
 
+def sparse_mix_topn_legs(nm, reps=5):
+    """PPCAMix.recommend on a SparseDataset (`--sparse-topn N_TOP --mix NM [--kappa KAPPA] [--slice ROWS] [--reps R]` beside
+    `--sparse DENSITY` or `--sparse-rows M`), in one process, alternating, every repetition timed on its own, NM components of state
+    size K: (a) PPCAMix.recommend at N_TOP (with KAPPA when given); (b) NM x PPCAModel.recommend, the same multiply-adds with NM lists
+    and NM downloads; (c) the floor: NM N d k multiply-adds (NM N d (k^2 + 2 k) with kappa) at 78.6 TFLOP/s plus the mixture's ell
+    pass (PPCAMix.llks); (d) what the call replaces -- PPCAMix.predict at all positions of a slice of ROWS rows (default: 2^24
+    positions) and np.argpartition, scaled to N."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    sp = P.SparseDataset(indptr, cols.int().cpu().numpy(), vals.cpu().numpy(), d, ctx=ctx)
+    del cols, vals
+    sp._sh
+    n_top = int(sys.argv[sys.argv.index("--sparse-topn") + 1])
+    kap = float(sys.argv[sys.argv.index("--kappa") + 1]) if "--kappa" in sys.argv else 0.0
+    rows = int(sys.argv[sys.argv.index("--slice") + 1]) if "--slice" in sys.argv else max(1, min(n, (1 << 24) // d))
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    mix = P.PPCAMix.init(nm, k, sp, seed=3).iterate(sp)
+    models = mix.models
+    q_indptr = np.zeros(n + 1, dtype=np.int64)
+    q_indptr[1:rows + 1] = d
+    q_indptr = np.cumsum(q_indptr)
+    q_cols = np.tile(np.arange(d, dtype=np.int32), rows)
+
+    def composition():
+        mean, var = mix.predict(sp, (q_indptr, q_cols))
+        score = (mean + kap * np.sqrt(var) if kap else mean).reshape(rows, d)
+        score[np.repeat(np.arange(rows), np.diff(indptr[:rows + 1])), sp._indices[:indptr[rows]]] = -np.inf
+        return np.argpartition(score, d - min(n_top, d), axis=1)[:, d - min(n_top, d):]
+
+    def series(fn, r, warm):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:60s} median {med:9.3f} ms  min {ts.min():9.3f}  max {ts.max():9.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    got_cols, _ = mix.recommend(sp, n_top, kappa=kap)
+    want = np.sort(composition(), axis=1)
+    same = float(np.mean(np.sort(got_cols[:rows], axis=1) == want)) if n_top <= d else float("nan")
+    print(f"  recommend against the composition on the first {rows} rows: {same:.6f} of the columns agree (ties and last bits apart)", flush=True)
+    tag = f"n = {n_top}" + (f", kappa = {kap:g}" if kap else "")
+    legs = [(f"(a) PPCAMix.recommend {tag}, {nm} components", lambda: mix.recommend(sp, n_top, kappa=kap), reps, 2),
+            (f"(b) {nm} x PPCAModel.recommend {tag}", lambda: [m.recommend(sp, n_top, kappa=kap) for m in models], reps, 2),
+            ("(c) PPCAMix.llks (the mixture's ell pass)", lambda: mix.llks(sp), reps, 2),
+            (f"(d) PPCAMix.predict at all positions of {rows} rows + argpartition", composition, reps, 1)]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn, r, warm in legs:
+            got.setdefault(name, []).append(series(fn, r, warm))
+    med = [report(name, np.concatenate(got[name])) for name, _, _, _ in legs]
+    spread = [float(np.ptp(np.concatenate(got[name])) / np.median(np.concatenate(got[name]))) for name, _, _, _ in legs]
+    fl = 2.0 * nm * n * d * (k * k + 2 * k if kap else k) / 78.6e12 * 1e3
+    comp = med[3] * n / rows
+    print(f"  (a) / (b): {med[0] / med[1]:.3f} (below 1: the fused call is faster; run-to-run spread of the two legs: {spread[0]:.1%}, {spread[1]:.1%})")
+    print(f"  (c) floor {fl:.3f} ms + ell pass {med[2]:.3f} ms = {fl + med[2]:.3f} ms, achieved fraction {(fl + med[2]) / med[0]:.3f} (of the ranking "
+          f"alone: {fl / max(med[0] - med[2], 1e-9):.3f})")
+    print(f"  (d) the composition scaled to N: {comp / 1e3:.1f} s;  (d) / (a): {comp / med[0]:.0f} x (spread of (d): {spread[3]:.1%})")
+
+
+if "--mix" in sys.argv and "--sparse-topn" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
+    sparse_mix_topn_legs(int(sys.argv[sys.argv.index("--mix") + 1]))
+    sys.exit(0)
 if "--mix" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
     sparse_mix_legs(int(sys.argv[sys.argv.index("--mix") + 1]))
     sys.exit(0)
