@@ -624,6 +624,32 @@ int ppca_heldout_split_csr_host(int64_t n, const int64_t *row_ptr, const int32_t
  * segment) of `held` the column sums are bit-identical under any grid limit. */
 int ppca_heldout_score_sparse(ppca_ctx *ctx, ppca_sparse *train, ppca_sparse *held, const ppca_model *model, double *totals_host,
                               double *col_sums_host, double *per_row);
+/* Factor analysis (per-column noise, section "factor analysis" above) on row-compressed data.
+ * ppca_scale_columns_sparse: ppca_dataset_scale_columns on the entries of sp, on the device, with per-column host vectors a, b, l (d
+ * each; b, l nullable = 0; every element finite, else PPCA_ERR_INVALID before any device work):
+ *   out     (nullable) a values view of sp: a ppca_sparse that shares sp's pattern, row lists, inverted index and work items (nothing
+ *           is re-indexed) and carries sp's weights, with buffers of its own for the values val_e a_col(e) -- one fp64 multiply -- in CSR
+ *           order and in index order (16 bytes per entry; the two copies of an entry hold the same bits).  Every entry point that takes
+ *           a ppca_sparse takes a view, ppca_sparse_to_host returns the view's own values, ppca_sparse_free releases its two buffers to
+ *           the context's block cache.  With out == NULL no per-entry buffer is allocated.
+ *   col_sums_host (nullable, 3 d): tot_j = sum w_i | sum_j = sum w_i (x_ij a_j - b_j) | sq_j = sum w_i (x_ij a_j - b_j)^2 over the
+ *           entries of column j, w = sp's weights; zeros for a column without an entry
+ *   row_sums_host (nullable, n, host memory): sum of l_j over the row's entries; 0 for an empty row
+ * At least one output is given.  The row sums and the values depend on the row's entry list alone: bit-identical under any grid limit,
+ * block_rows, weights or position.  The column sums are added in a fixed order (chunks of 16 entries by a butterfly, chunks in order,
+ * runs in run order, blocks in order; no float atomics): bit-identical under any grid limit for a given (block_rows, segment).  An
+ * empty dataset gives zeros and a view without entries.  Synchronises once.
+ * ppca_fa_sparse_em_step: ppca_fa_em_step on row-compressed data -- whiten and take sq in one scale pass (a = 1 / s, b = mean / s), the
+ * row and column passes of ppca_sparse_em_accumulate on the view under PPCAModel(1, C / s, mean / s), the statistics to the host and
+ * ppca_fa_finalize_host unchanged; the view is released before returning.  llk_in (nullable): the pass's by-product minus
+ * sum_j tot_j ln s_j.  One synchronisation for the results (the upload of the whitened model waits once before it).  Preconditions,
+ * checked before any launch: sp's d equals d (else PPCA_ERR_INVALID); k <= 16 (else PPCA_ERR_UNSUPPORTED); n = 0: PPCA_ERR_EMPTY; noise
+ * positive and finite. */
+int ppca_scale_columns_sparse(ppca_ctx *ctx, ppca_sparse *sp, const double *a_host, const double *b_host, const double *l_host,
+                              ppca_sparse **out, double *col_sums_host, double *row_sums_host);
+int ppca_fa_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, int32_t d, int32_t k, const double *noise, const double *transform,
+                           const double *mean, const double *min_noise, double *noise_out, double *transform_out, double *mean_out,
+                           double *llk_in);
 
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every

@@ -433,7 +433,8 @@ class SparseDataset:
     The entries go to the device, with the inverted index the statistics pass reads, on first use.
     `holdout` / `holdout_range` / `kfold` split the entries on the host exactly as Dataset's split the same matrix, and
     PPCAModel.heldout_score takes the two parts.  PPCAMix takes one too: llk / llks / infer_cluster / iterate* /
-    predict and PPCAMixTrainer."""
+    predict and PPCAMixTrainer.  So does FAModel, one noise level per column: llk / llks / infer / iterate* / predict /
+    heldout_score and FATrainer."""
 
     def __init__(self, indptr, indices, values, n_columns: int, weights=None, *, ctx=None, block_rows: Optional[int] = None,
                  segment: Optional[int] = None):
@@ -474,7 +475,7 @@ class SparseDataset:
                 raise ValueError(f"{name} must be positive")
         for a in (ip, ix, v):
             a.setflags(write=False)
-        self._indptr, self._indices, self._values, self._d, self._w = ip, ix, v, d, w
+        self._indptr, self._indices, self._vals, self._d, self._w = ip, ix, v, d, w
         self._block_rows, self._segment = int(block_rows or 0), int(segment or 0)
         self._ctx_arg = ctx
         self._handle = None
@@ -517,7 +518,22 @@ class SparseDataset:
         # every pass written for the dense layout reaches its dataset through _h
         raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
                         "predict / recommend / heldout_score and PPCATrainer are, and PPCAMix.llk / llks / infer_cluster / iterate* / "
-                        "predict / recommend and PPCAMixTrainer")
+                        "predict / recommend and PPCAMixTrainer, and FAModel.llk / llks / infer / iterate* / predict / heldout_score and "
+                        "FATrainer")
+
+    @property
+    def _values(self) -> np.ndarray:
+        """The values on the host.  A values view (`_scale_columns`) is made on the device and fetches them on first use only."""
+        if self._vals is None:
+            v = np.empty(self._indices.size)
+            check(lib().ppca_sparse_to_host(self._handle, None, None, ptr(v), None))
+            v.setflags(write=False)
+            self._vals = v
+        return self._vals
+
+    @_values.setter
+    def _values(self, v):
+        self._vals = v
 
     @property
     def _sh(self):
@@ -545,7 +561,7 @@ class SparseDataset:
 
     @property
     def nnz(self) -> int:
-        return int(self._values.size)
+        return int(self._indices.size)
 
     def csr(self):
         """(indptr int64, indices int32, values float64): copies."""
@@ -573,6 +589,44 @@ class SparseDataset:
         if len(self) == 0:
             return []
         return np.flatnonzero(np.bincount(self._indices, minlength=self._d) == 0).tolist()
+
+    def _scale_columns(self, a, b=None, l=None, *, out: bool = True, col_sums: bool = False, row_sums: bool = False):
+        """ppca_scale_columns_sparse, with Dataset._scale_columns's return triple: (the entries times a[column] as a SparseDataset or
+        None, (tot, sum, sq) of x * a - b per column or None, the row sums of l over the row's entries or None), from one pass on the
+        device.  The returned dataset is a values view: it shares this one's pattern, inverted index and weights on
+        the device and only its values are new; they come to the host if csr() / to_dense() asks for them, not before."""
+        d = self._d
+        a, b, l = f64(a, (d,)), (f64(b, (d,)) if b is not None else None), (f64(l, (d,)) if l is not None else None)
+        for name, v in (("a", a), ("b", b), ("l", l)):
+            if v is not None and not np.isfinite(v).all():
+                raise ValueError(f"every entry of {name} must be finite")
+        if not (out or col_sums or row_sums):
+            raise ValueError("no output requested")
+        h = C.c_void_p()
+        sums = np.empty((3, d)) if col_sums else None
+        rows = np.empty(len(self)) if row_sums else None
+        check(lib().ppca_scale_columns_sparse(self._ctx.handle, self._sh, ptr(a), ptr(b), ptr(l), C.byref(h) if out else None,
+                                              ptr(sums), ptr(rows)))
+        view = None
+        if out:
+            view = SparseDataset.__new__(SparseDataset)
+            view.__dict__.update(self.__dict__)
+            view.__dict__.pop("holdout_counts", None)
+            view._vals, view._handle = None, h
+        return view, sums, rows
+
+    def column_stats(self):
+        """(totals, means, variances) of every column over its entries, weighted: Dataset.column_stats on row-compressed data.  Two
+        sums-only passes on the device, the second centred on the means of the first."""
+        d = self._d
+        one = np.ones(d)
+        _, s1, _ = self._scale_columns(one, out=False, col_sums=True)
+        tot = s1[0]
+        safe = np.where(tot > 0.0, tot, 1.0)
+        mean = np.where(tot > 0.0, s1[1] / safe, 0.0)
+        _, s2, _ = self._scale_columns(one, mean, out=False, col_sums=True)
+        var = np.where(tot > 0.0, s2[2] / safe - (s2[1] / safe) ** 2, 0.0)
+        return tot, mean, np.maximum(var, 0.0)
 
     # -- hold-out splits (DESIGN.md 4.21) ---------------------------------------
     def _select(self, keep: np.ndarray) -> "SparseDataset":
@@ -1143,10 +1197,14 @@ class PPCAModel:
                                      0 if cand is None else cand.size, ptr(cols), ptr(scores)))
         return cols, scores
 
-    def _recon(self, dataset: Dataset, mode: int, fn) -> Dataset:
+    @staticmethod
+    def _recon_check(dataset: Dataset) -> None:
         if isinstance(dataset, SparseDataset):
             raise TypeError("smooth / extrapolate would write an N x d output, which is what a SparseDataset exists to avoid: use "
                             "predict(sparse, query) at the positions that are wanted")
+
+    def _recon(self, dataset: Dataset, mode: int, fn) -> Dataset:
+        self._recon_check(dataset)
         h = C.c_void_p()
         check(fn(dataset._ctx.handle, dataset._h, self._device(dataset._ctx).h, mode, C.byref(h)))
         return Dataset._wrap(h, dataset._ctx)
@@ -1504,7 +1562,8 @@ def heldout_score(model, train: Dataset, held: Dataset, precisions=None, held_pr
     """The held-out score of a model of ANY family on one split, so that families are compared on identical held entries:
     model.heldout_score(train, held) for PPCAModel, PPCAMix, FAModel and FAMix; TPPCAModel.score_heldout(train, held) (the t
     predictive); HPPCAModel.score_heldout(train, held, precisions, held_precisions) (an entry at its own noise level).  `precisions`
-    are required for an HPPCAModel and refused for every other family.  Two SparseDatasets are scored by a PPCAModel only."""
+    are required for an HPPCAModel and refused for every other family.  Two SparseDatasets are scored by a PPCAModel only (an FAModel
+    scores them through its own method, FAModel.heldout_score: taking it here, and in cross_validate, is the follow-up of DESIGN.md 7)."""
     if (isinstance(train, SparseDataset) or isinstance(held, SparseDataset)) and not isinstance(model, PPCAModel):
         raise TypeError(f"{type(model).__name__} does not score a SparseDataset: on row-compressed data only PPCAModel.heldout_score exists "
                         "(DESIGN.md section 7)")
@@ -1711,6 +1770,8 @@ class FAModel:
             raise ValueError("method must be 'random' or 'pca'")
         m = PPCAModel.init(state_size, dataset, seed=seed)  # (the checks of state_size and of an empty dataset, for both methods)
         if method == "pca":
+            if isinstance(dataset, SparseDataset):
+                raise ValueError("method='pca' is not available on a SparseDataset: the d x d moments are not built from row-compressed data")
             return FAModel.from_moments(state_size, dataset.pairwise_moments())
         return FAModel(np.ones(m.output_size), m._c, m._mean)
 
@@ -1753,11 +1814,13 @@ class FAModel:
     def _whiten(self, dataset: Dataset, **kw):
         if dataset._d != self.output_size:
             raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {self.output_size}")
+        if isinstance(dataset, SparseDataset) and self.state_size > 16:  # (the library's own answer, before the first touch of a device)
+            raise _lib.PPCAError(-3, f"state size {self.state_size} is not supported on sparse data: the kernels cover k <= 16")
         return dataset._scale_columns(1.0 / self._noise, **kw)
 
     def llks(self, dataset: Dataset) -> np.ndarray:
         """Per-sample log-likelihood: the whitened model's on the whitened rows minus the sum of ln noise[j] over the row's
-        observed entries."""
+        observed entries.  A SparseDataset is whitened on the device as a values view, here and in every pass below."""
         y, _, jac = self._whiten(dataset, l=np.log(self._noise), row_sums=True)
         return self.whitened().llks(y) - jac
 
@@ -1768,7 +1831,19 @@ class FAModel:
 
     def heldout_score(self, train: Dataset, held: Dataset) -> "HeldOutScore":
         """PPCAModel.heldout_score for per-column noise: both parts whitened with the same scales, scored by the whitened model and
-        mapped back to the units of the data."""
+        mapped back to the units of the data.  Two SparseDatasets (the parts of SparseDataset.holdout) are whitened on the device as
+        values views and scored from their entry lists; the one-of-each and block_rows checks are PPCAModel's.  (The
+        package-level heldout_score(model, sparse, sparse) and cross_validate still take a PPCAModel only: DESIGN.md section 7.)"""
+        sparse = isinstance(train, SparseDataset), isinstance(held, SparseDataset)
+        if sparse[0] != sparse[1]:
+            raise TypeError("heldout_score takes two Datasets or two SparseDatasets, not one of each")
+        if sparse[0]:  # (PPCAModel.heldout_score's checks, before the first touch of a device)
+            if len(train) == len(held) and train._d == held._d and train._block_rows != held._block_rows:
+                raise ValueError(f"the train part is tiled with block_rows={train._block_rows or None} and the held part with "
+                                 f"block_rows={held._block_rows or None}: the score walks both block by block, so build them with one "
+                                 "block_rows tiling")
+            if len(train) != len(held) or train._d != held._d:
+                raise ValueError("the train part and the held part differ in shape")
         score = self.whitened().heldout_score(self._whiten(train)[0], self._whiten(held)[0])
         return _heldout_unwhiten(score, held, self._noise)
 
@@ -1777,18 +1852,30 @@ class FAModel:
         inf = self.whitened().infer(self._whiten(dataset)[0])
         return InferredFA(inf._states, inf._covs)
 
+    def predict(self, sparse: "SparseDataset", query):
+        """PPCAModel.predict for per-column noise: (mean, variance) of a new reading at the query positions of row-compressed data, in
+        the units of the data -- the whitened model's predict on the whitened view, the mean times noise[j] and the variance times
+        noise[j]^2."""
+        if not isinstance(sparse, SparseDataset):
+            raise TypeError("predict takes a SparseDataset (on a Dataset: smooth / extrapolate / heldout_score)")
+        _, ix = _query_pattern(sparse, query)
+        mean, var = self.whitened().predict(self._whiten(sparse)[0], query)
+        s = self._noise[ix]
+        return mean * s, var * (s * s)
+
     def smooth(self, dataset: Dataset) -> Dataset:
         """C z + mean for every dimension."""
+        PPCAModel._recon_check(dataset)
         sm = self.whitened().smooth(self._whiten(dataset)[0])  # (the whitened copy is released here)
         return sm._scale_columns(self._noise)[0]
 
     def extrapolate(self, dataset: Dataset) -> Dataset:
         """Observed values kept bit for bit, masked ones replaced by C z + mean."""
+        PPCAModel._recon_check(dataset)
         sm = self.whitened().smooth(self._whiten(dataset)[0])
         return dataset._fill_masked(sm, self._noise)
 
     def _iterate(self, dataset: Dataset, min_noise, want_llk: bool):
-        ctx = dataset._ctx
         if len(dataset) == 0:
             raise ValueError("dataset is empty")
         d, k = self.output_size, self.state_size
@@ -1799,8 +1886,14 @@ class FAModel:
             floor = np.ascontiguousarray(np.broadcast_to(np.asarray(min_noise, dtype=np.float64), (d,)))
         n_out, c_out, m_out = np.empty(d), np.empty((d, k)), np.empty(d)
         llk = C.c_double(0.0)
-        check(lib().ppca_fa_em_step(ctx.handle, dataset._h, d, k, ptr(self._noise), ptr(self._c), ptr(self._mean), ptr(floor),
-                                    ptr(n_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
+        if isinstance(dataset, SparseDataset):
+            if k > 16:  # (the library's own answer, given here so that it comes before the first touch of a device)
+                raise _lib.PPCAError(-3, f"state size {k} is not supported on sparse data: the kernels cover k <= 16")
+            fn, h = lib().ppca_fa_sparse_em_step, dataset._sh
+        else:
+            fn, h = lib().ppca_fa_em_step, dataset._h
+        check(fn(dataset._ctx.handle, h, d, k, ptr(self._noise), ptr(self._c), ptr(self._mean), ptr(floor),
+                 ptr(n_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
         return FAModel(n_out, c_out, m_out, ctx=self._ctx), (llk.value if want_llk else None)
 
     def iterate(self, dataset: Dataset, min_noise=None) -> "FAModel":
@@ -1853,11 +1946,12 @@ class FATrainer:
     def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
                           init: str = "random", prior: Optional[Prior] = None, folds: int = 1):
         """PPCATrainer.select_state_size with FAModel fits: [(state_size, HeldOutScore, FAModel)].  FAModel has no MAP step:
-        `prior` must be None."""
+        `prior` must be None.  On a SparseDataset the split is SparseDataset.holdout / kfold and the score FAModel.heldout_score on
+        the two parts (the package-level heldout_score does not take an FAModel with row-compressed data)."""
         if prior is not None:
             raise ValueError("FATrainer takes no prior")
         return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: FATrainer(tr).train(
-            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init), folds)
+            state_size=k, n_iters=n_iters, quiet=True, seed=seed, init=init), folds, score=lambda m, t, h: m.heldout_score(t, h))
 
 
 # --------------------------------------------------------------------------- Student-t PPCA (robust to outlying rows)
@@ -2915,6 +3009,7 @@ class FAMix:
     def _whiten(self, dataset: Dataset, **kw):
         if dataset._d != self.output_size:
             raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {self.output_size}")
+        _dense_only(dataset)  # (the mixture of factor analysers on row-compressed data is not built: DESIGN.md section 7)
         return dataset._scale_columns(1.0 / self._noise, **kw)
 
     def llks(self, dataset: Dataset) -> np.ndarray:

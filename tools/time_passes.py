@@ -25,7 +25,7 @@ SparseDataset (see sparse_legs); with `--sparse-heldout` beside 
 data (see sparse_heldout_legs); with `--sparse-topn N_TOP` beside either, ONLY the legs of PPCAModel.recommend on that
 data (see sparse_topn_legs); with `--mix NM` beside either, ONLY the legs of PPCAMix on that data (see
 sparse_mix_legs); with `--sparse-topn N_TOP` and `--mix NM` together, ONLY the legs of PPCAMix.recommend (see
-sparse_mix_topn_legs)."""
+sparse_mix_topn_legs); with `--fa` beside either, ONLY the legs of FAModel on that data (see sparse_fa_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -425,6 +425,70 @@ def sparse_mix_topn_legs(nm, reps=5):
     print(f"  (d) the composition scaled to N: {comp / 1e3:.1f} s;  (d) / (a): {comp / med[0]:.0f} x (spread of (d): {spread[3]:.1%})")
 
 
+def sparse_fa_legs(reps=5):
+    """FAModel on a SparseDataset (`--fa [--reps R]` beside `--sparse DENSITY` or `--sparse-rows M`), in one process,
+    alternating, every repetition timed on its own: (a) ppca_scale_columns_sparse with the view and the column sums, (b) its sums-only
+    form, (c) PPCAModel.iterate(sp), (d) FAModel.iterate(sp), and (e) what there was before the scale pass: a new SparseDataset from
+    the rescaled host values (validation, index build, upload) plus PPCAModel.iterate on it -- one repetition per round, it takes
+    seconds.  Reported: (d) / (c), (a) / (c), and the bytes per second of (a) at 36 B per entry (both orientations: 8 B read, 8 B
+    written; the 4 B column index of the CSR copy; the a[col] gather stays in cache; the data carries no weights, so the row index of
+    the inverted copy is not read) and of (b) at 8 B per entry."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    ix, v = cols.int().cpu().numpy(), vals.cpu().numpy()
+    del cols, vals
+    sp = P.SparseDataset(indptr, ix, v, d, ctx=ctx)
+    sp._sh
+    print(f"  host: the index, row lists and work items {sp.index_build_seconds():.2f} s", flush=True)
+    model = P.PPCAModel.init(k, sp, seed=3).iterate(sp)
+    rng = np.random.default_rng(5)
+    fa = P.FAModel(model.isotropic_noise * rng.uniform(0.5, 2.0, d), model.transform, model.mean)
+    a, b = 1.0 / fa.noise, fa.mean / fa.noise
+
+    def scale():
+        sp._scale_columns(a, b, col_sums=True)
+
+    def sums():
+        sp._scale_columns(a, b, out=False, col_sums=True)
+
+    def rebuild():
+        model.iterate(P.SparseDataset(indptr, ix, v * a[ix], d, ctx=ctx))
+
+    def series(fn, r, warm):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:72s} median {med:10.3f} ms  min {ts.min():10.3f}  max {ts.max():10.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    legs = [("(a) scale pass: view + column sums", scale, reps, 2), ("(b) scale pass: column sums only", sums, reps, 2),
+            ("(c) PPCAModel.iterate(sp)", lambda: model.iterate(sp), reps, 2), ("(d) FAModel.iterate(sp)", lambda: fa.iterate(sp), reps, 2),
+            ("(e) new SparseDataset from rescaled host values + PPCAModel.iterate", rebuild, 1, 0)]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn, r, warm in legs:
+            got.setdefault(name, []).append(series(fn, r, warm))
+    med = [report(name, np.concatenate(got[name])) for name, _, _, _ in legs]
+    spread = [float((np.concatenate(got[name]).max() - np.concatenate(got[name]).min()) / m_) for (name, _, _, _), m_ in zip(legs, med)]
+    print(f"  (d) / (c): {med[3] / med[2]:.3f};  (a) / (c): {med[0] / med[2]:.3f};  (e) / (d): {med[4] / med[3]:.1f} x  "
+          f"(run-to-run spread of (c), (d): {spread[2]:.1%}, {spread[3]:.1%})")
+    print(f"  (a) {36.0 * nnz / med[0] / 1e6:.0f} GB/s at 36 B per entry;  (b) {8.0 * nnz / med[1] / 1e6:.0f} GB/s at 8 B per entry")
+
+
+if "--fa" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
+    sparse_fa_legs()
+    sys.exit(0)
 if "--mix" in sys.argv and "--sparse-topn" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
     sparse_mix_topn_legs(int(sys.argv[sys.argv.index("--mix") + 1]))
     sys.exit(0)
