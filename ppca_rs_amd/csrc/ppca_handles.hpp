@@ -153,7 +153,7 @@ int em_finalize_with_table(ppca_ctx *ctx, const ppca_model *model_in, const doub
 // PPCAMix::iterate_with_prior over the context's rows (comm nullable: one row shard of several), ppca_capi.hip
 int mix_em_step(ppca_ctx *ctx, ppca_comm *comm, ppca_dataset *ds, ppca_model *const *models_in, const double *log_weights_in,
                 int32_t nm, const ppca_prior *prior, ppca_model *const *models_out, double *log_weights_out, double *llk_in);
-// What the mixture step on row-compressed data (ppca_sparse.hip) shares with mix_em_step, ppca_capi.hip: the check of a prior, the plain
+// What the mixture step on row-compressed data (ppca_sparse_mix.hip) shares with mix_em_step, ppca_capi.hip: the check of a prior, the plain
 // finalisation (no slice table: the next iteration walks K models), the step's small device vectors in ctx->mixaux -- [0, P) maxima ->
 // shifts | [P, 2P) new log-weights, llk | [2P, 3P) the normalised log-weights of the llk sweep | [3P, ...) one int per component --
 // and the upload of the normalised log-weights (PPCAMix::new mix.rs:66-70) into logw through the pinned staging buffer.

@@ -294,7 +294,7 @@ PPCA_HD constexpr bool pair_first_of_owner(int K, int p, int nw) {
 
 // Per-sample log-likelihood from the solve's by-products (ppca_model.rs:124-139):
 //   -1/2 [ (|x~|^2 - b^T M^-1 b)/s2 + ln det M + 2 ln(sigma)(m - k) + ln(2 pi) m ],  0 if m == 0
-// (sp_mix_row_ell in ppca_sparse.hip writes this expression out operation by operation, to give sparse_row_kernel's bits: change both)
+// (sp_mix_row_ell in ppca_sparse_mix.hip writes this expression out operation by operation, to give sparse_row_kernel's bits: change both)
 PPCA_HD double sample_llk(double xx, double quad, double logdet, double s2, double ln_sigma, int m, int k) {
     if (m == 0) return 0.0;
     return -0.5 * ((xx - quad) / s2 + logdet + 2.0 * ln_sigma * (double)(m - k) + LN_2PI * (double)m);

@@ -13,7 +13,7 @@ namespace ppca {
 // ------------------------------------------------------------------ the generator
 // Every stream of the library: draws are keyed by (seed, stream, global row, index), and two streams never meet as long as every id
 // is given out here.  smix64, row_key, row_word and u01_floor are host code too: the host-side split of row-compressed data
-// (ppca_sparse.hip, ppca_heldout_split_csr_host) draws the words of holdout_kernel.
+// (ppca_sparse_heldout.hip, ppca_heldout_split_csr_host) draws the words of holdout_kernel.
 enum RngStream : uint64_t {
     STREAM_SYNTH_LATENT = 1,  // synthetic data: z
     STREAM_SYNTH_NOISE = 2,   //   the noise of x

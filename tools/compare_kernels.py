@@ -2,7 +2,9 @@
 
     python tools/compare_kernels.py --build TREE OUT     device code of TREE's ppca_rs_amd/csrc/*.hip -> OUT/<name>.elf (gfx950,
                                                          the flags of ppca_rs_amd/build.py; needs no GPU)
-    python tools/compare_kernels.py OLD NEW              compares two such directories
+    python tools/compare_kernels.py OLD NEW              compares two such directories, file by file
+    python tools/compare_kernels.py --pooled [--namespace OLD=NEW] [--rename OLDSYM=NEWSYM]... OLD NEW
+                                                         follows kernels that moved to another file or namespace (below)
 
 Per kernel symbol: the bytes of its function in .text with the disassembly's own addresses left out (a function that moved is
 still the same function), and .vgpr_count / .sgpr_count / .group_segment_fixed_size / .private_segment_fixed_size of its metadata
@@ -14,6 +16,14 @@ One kind of operand depends on where the function lies and is compared as equal:
 pair that follows an s_getpc_b64 on the same register pair -- the distance from the code to a constant table in another section
 (lean_log's coefficients, for one).  Deleting a kernel from a file moves the others and changes nothing else in them.  The line
 of a file says how many such literals were masked on either side.  The zero padding between a function and the next is left out too.
+
+--pooled: the kernels of all .elf files of a side are one pool, and a kernel's partner is the one of the same mangled name wherever
+it lies.  --namespace 12_GLOBAL__N_1=7ppca_sp rewrites that component of OLD's names textually (a file's anonymous namespace that
+became the named namespace ppca_sp; length-prefixed as in the mangled name, so no demangler is needed; a kernel whose unchanged name
+exists in NEW keeps it, as in a file that was not touched); --rename gives a partner by hand, to a kernel that became an instantiation
+of a template for one.  A kernel's own name shows in its disassembly, in the
+`<symbol+0x...>` comment behind each branch: that comment is dropped before the comparison, as is the s_nop / s_code_end padding
+behind the last instruction.  The exit status is as above; a kernel of NEW without a partner counts as one that appeared.
 """
 import os
 import re
@@ -114,9 +124,69 @@ def main(old, new):
     return 1 if bad else 0
 
 
+def pool(d):
+    """{kernel symbol: (normalised code, metadata, file)} over the .elf files of d"""
+    out = {}
+    for f in sorted(os.listdir(d)):
+        if f.endswith(".elf"):
+            for k, (code, meta) in kernels(os.path.join(d, f))[0].items():
+                lines = [re.sub(r"\s*<[^<>\s]+>$", "", ln) for ln in code.split("\n")]
+                while lines and re.match(r"\s*(s_nop|s_code_end)\b", lines[-1]):
+                    lines.pop()
+                if k in out:
+                    sys.exit("%s: %s is also a kernel of %s: the pool cannot tell them apart" % (f, k, out[k][2]))
+                out[k] = ("\n".join(lines), meta, f)
+    return out
+
+
+def main_pooled(old, new, namespaces, renames):
+    a, b = pool(old), pool(new)
+    partner = {}  # OLD symbol -> the name it should have in NEW
+    for k in a:
+        name = k
+        for frm, to in namespaces:
+            name = name.replace(frm, to)
+        partner[k] = renames.get(k, k if k in b else name)  # (a file that did not change keeps its anonymous namespace)
+    bad = 0
+    for f in sorted(set(v[2] for v in a.values())):
+        mine = sorted(k for k in a if a[k][2] == f)
+        found = [k for k in mine if partner[k] in b]
+        diff = [k for k in found if a[k][:2] != b[partner[k]][:2]]
+        where = {}
+        for k in found:
+            where[b[partner[k]][2]] = where.get(b[partner[k]][2], 0) + 1
+        print("%-22s old %3d  matched %3d  identical %3d  differ %d  gone %d   now in: %s"
+              % (f, len(mine), len(found), len(found) - len(diff), len(diff), len(mine) - len(found),
+                 ", ".join("%s %d" % kv for kv in sorted(where.items()))))
+        for k in diff:
+            print("   DIFFERS  %s -> %s (%s)  %s meta %s -> %s" % (k, partner[k], b[partner[k]][2], "code" if a[k][0] != b[partner[k]][0] else "",
+                                                               a[k][1], b[partner[k]][1]))
+        for k in mine:
+            if k not in found:
+                print("   gone     %s" % k)
+        bad += len(diff)
+    came = sorted(set(b) - set(partner.values()))
+    for k in came:
+        print("   NEW      %s (%s)" % (k, b[k][2]))
+    print("total: old %d  new %d  matched %d  differ %d  without a partner in OLD %d" % (len(a), len(b), len(set(partner.values()) & set(b)), bad, len(came)))
+    return 1 if bad or came else 0
+
+
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--build":
         build(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) >= 4 and sys.argv[1] == "--pooled":
+        args, namespaces, renames = sys.argv[2:], [], {}
+        while len(args) > 2 and args[0] in ("--namespace", "--rename"):
+            frm, to = args[1].split("=", 1)
+            if args[0] == "--namespace":
+                namespaces.append((frm, to))
+            else:
+                renames[frm] = to
+            args = args[2:]
+        if len(args) != 2:
+            sys.exit(__doc__)
+        sys.exit(main_pooled(args[0], args[1], namespaces, renames))
     elif len(sys.argv) == 3:
         sys.exit(main(sys.argv[1], sys.argv[2]))
     else:
