@@ -1,6 +1,6 @@
 // ppca_capi.hip -- host side of the C-ABI declared in include/ppca_hip.h.
-// Owns device memory behind opaque handles, sequences the kernels of
-// ppca_kernels.hip on the context stream and never computes the hot path on the
+// Owns device memory behind opaque handles, sequences the kernels of the
+// other units (ppca_internal.hpp) on the context stream and never computes the hot path on the
 // CPU: without a HIP device every compute entry point fails with PPCA_ERR_HIP.
 #include <hip/hip_runtime.h>
 
@@ -1813,7 +1813,7 @@ extern "C" int ppca_mix_llk(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *
 // One component of the mixture M-step on this context's rows, ENQUEUED only (no host synchronisation): sample weights
 // exp(u_i - *shift_dev) (mix.rs:320-323), their sum (:324-325) into *sum_dev, and the component's weighted statistics
 // into stats_dev.  Every statistic is linear in the weights, so rows whose weight is below 2^-200 of the component's
-// largest (SEL_MIN_WEIGHT, ppca_kernels.hip: their terms sit >= 147 binary orders below the fp64 resolution of the sums
+// largest (SEL_MIN_WEIGHT, ppca_mix.hip: their terms sit >= 147 binary orders below the fp64 resolution of the sums
 // they would join) are dropped from the pass on the fused path: select_* kernels build the ascending row list and its
 // length ON THE DEVICE, the pass gathers those rows and reads the count from device memory (PassArgs::n_dev) -- at
 // d = 256 a sample keeps weight in about one component, so the K component passes together cost about as much as one.
@@ -1978,7 +1978,7 @@ static int mix_em_step_multi(ppca_ctx *ctx, ppca_comm *comm, ppca_dataset *ds, p
         HIP_TRY(launch_pass_em(k, grid, a, ctx->stream));
     }
     // 4. reductions + verdicts in one launch, then the (normally idle) second stages
-    HIP_TRY(launch_reduce_wguard_multi(k, r, grid, ctx->stream));
+    HIP_TRY(launch_reduce_wguard_multi(k, r, ctx->stream));
     ctx->guard_words.clear();
     for (int c = 0; c < nm; ++c) ctx->guard_words.push_back(r.g[c].qflag);
     for (int c = 0; c < nm; ++c)

@@ -1,4 +1,4 @@
-// ppca_device.hpp -- device-side helpers shared by the fused-pass kernels (ppca_kernels.hip, ppca_llk.hip):
+// ppca_device.hpp -- device-side helpers shared by the fused-pass kernels (ppca_pass.hip, ppca_kernels.hip, ppca_em9.hip, ppca_llk.hip):
 // the LDS layout constants of a 32-sample tile, wave reductions on the DPP path, lane-targeted writes, compile-time
 // loops, the fp64 MFMA wrapper and the constants of the int8-sliced Gram table; and the host's dispatch over the state size
 // (PPCA_DISPATCH_K).  Not installed.

@@ -2,7 +2,7 @@
 // (128).  BASELINE config 4: d = 1024, k = 64.  (The EM pass of 11 <= k <= 16, d <= 256 is handed on to ppca_em16.hip; every output
 // pass of those shapes runs here.)
 //
-// Same mathematics as pass_kernel (ppca_kernels.hip) and the same reference items
+// Same mathematics as pass_kernel (ppca_pass.hip) and the same reference items
 // (ppca/src/ppca_model.rs:195-208 infer_one, :281-358 M-step sweeps, :142-149 llk), but
 // the k x k per-sample state no longer fits registers and the d x k(k+1)/2 statistics no
 // longer fit one workgroup, so the pass is cut into stages over chunks of samples (gen_chunk: ~1.5 GB of per-sample
@@ -2256,7 +2256,7 @@ static hipError_t run_em16(const double *X, int64_t ldx, const double *w, int64_
     int *qflag = reinterpret_cast<int *>(qscale + 160);
     int *anyflag = qflag + 16;
     signed char *qtab = reinterpret_cast<signed char *>(qscale + 192);
-    GTRY(launch_qprep16(k, model, d, qscale, qtab, qflag, s));
+    GTRY(launch_qprep(k, model, d, qscale, qtab, qflag, s));
     hipLaunchKernelGGL(flag_any_kernel, dim3(1), dim3(1), 0, s, qflag, ntp, anyflag);
     {
         const int64_t tot = (int64_t)d * kp;
@@ -2568,7 +2568,7 @@ hipError_t generic_gram_guard(int d, int k, const double *model, void *ws, hipSt
     if (em16_enabled() && em16_covers(d, k)) {  // the EM pass of these shapes: the guard of its own slice table (ppca_em16.hip)
         double *qscale = W.e16_q;
         int *qflag = reinterpret_cast<int *>(qscale + 160);
-        GTRY(launch_qprep16(k, model, d, qscale, reinterpret_cast<signed char *>(qscale + 192), qflag, s));
+        GTRY(launch_qprep(k, model, d, qscale, reinterpret_cast<signed char *>(qscale + 192), qflag, s));
         hipLaunchKernelGGL(flag_any_kernel, dim3(1), dim3(1), 0, s, qflag, (int)((kp + 15) / 16), qflag + 16);
         *flag_dev = qflag + 16;
         return hipGetLastError();

@@ -1,6 +1,6 @@
-// ppca_internal.hpp -- declarations shared by the kernels (ppca_kernels.hip) and
-// the C-ABI host layer (ppca_capi.hip).  Not installed; the public surface is
-// include/ppca_hip.h.
+// ppca_internal.hpp -- declarations shared by the kernel units (ppca_*.hip: every launcher that
+// crosses files is a host function declared here) and the C-ABI host layer (ppca_capi.hip).
+// Not installed; the public surface is include/ppca_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -156,6 +156,9 @@ void fused_qtab_layout(void *base, PassArgs &a);  // points the three at a buffe
 // Runs only the slice-table / guard kernel of a model (what every fused pass launches first).  *forced = 0 / 1 when
 // the environment pins the engine (int8 without guard / fp64), -1 when qflag decides.
 hipError_t launch_gram_guard(int k, const PassArgs &a, hipStream_t s, int *forced);
+// qprep_kernel itself, 1 <= k <= 16: the slice table, dequantisation multipliers and guard flags of `model` and, for k <= FUSED_MAX_K
+// (where qscale must be the base of a fused_qtab_view block), the operand-ordered copy of C behind the table
+hipError_t launch_qprep(int k, const double *model, int d, double *qscale, signed char *qtab, int *qflag, hipStream_t s);
 int fused_gram_tiles(int k);  // number of qflag entries the guard writes for state size k
 // Launchers.  Return hipSuccess or the launch error.
 hipError_t launch_pass_em(int k, int grid, const PassArgs &a, hipStream_t s);
@@ -176,7 +179,7 @@ struct Em16Launch {
     int d;
     const double *model;
     double *part;          // [grid][stats_len]
-    signed char *qtab;     // int8 Gram slice table of the model, em16_qtab_bytes(k) (launch_qprep16)
+    signed char *qtab;     // int8 Gram slice table of the model, em16_qtab_bytes(k) (launch_qprep)
     double *qscale;        // 16 x tiles dequantisation multipliers
     int *qflag;            // [tiles] guard flags; any set -> the Gram rows are read from Gext
     const double *Gext;    // [n][k'] packed Gram rows of the fp64 engine (read only when the guard tripped)
@@ -190,7 +193,6 @@ hipError_t em16_debug_counters(unsigned long long *out4, int reset, hipStream_t 
 bool em16_covers(int d, int k);
 int em16_ncol(int k);
 size_t em16_qtab_bytes(int k);
-hipError_t launch_qprep16(int k, const double *model, int d, double *qscale, signed char *qtab, int *qflag, hipStream_t s);
 hipError_t launch_em16(int k, int grid, const Em16Launch &a, hipStream_t s);
 // The log-likelihood sweep alone (ppca_llk.hip): per-sample llks (nullable) and the per-workgroup scalars; honours
 // a.qflag like the int8 instantiation of pass_kernel.
@@ -208,7 +210,7 @@ hipError_t launch_pass_post_fp64(int k, int grid, const PassArgs &a, hipStream_t
 int fused_gram_mode();  // 0: int8 behind the guard (default); 1: fp64 pinned (PPCA_GRAM_FP64=1); 2: int8 without guard (tuning builds)
 hipError_t launch_qprep_multi(int k, const MixTabArgs &a, hipStream_t s);
 hipError_t launch_finalize_qprep_multi(int k, const MixFinalArgs &a, hipStream_t s);
-hipError_t launch_reduce_wguard_multi(int k, const MixReduceArgs &a, int grid_parts, hipStream_t s);
+hipError_t launch_reduce_wguard_multi(int k, const MixReduceArgs &a, hipStream_t s);
 hipError_t launch_reduce_partials(const double *part, int grid_parts, int64_t len, double *out, hipStream_t s, int accumulate = 0,
                                   const int *run_if = nullptr);  // run_if: device flag; the kernel returns at once when it is 0
 // A guarded EM pass of the fused path after launch_pass_em, in two launches (round 5; rounds 3-4: reduction, wguard_kernel,
@@ -226,6 +228,8 @@ hipError_t launch_reduce_partials(const double *part, int grid_parts, int64_t le
 hipError_t launch_reduce_wguard(int k, const double *part, int64_t len, double *stats, const GuardArgs &g, hipStream_t s, bool *applies_out);
 hipError_t launch_em_fallback(int k, int grid, PassArgs a, const GuardArgs &g, const double *part, double *part2, int64_t len, double *stats,
                               hipStream_t s);
+// its second half alone (what launch_em_fallback ends with: the pass is ppca_pass.hip's, the reduction ppca_kernels.hip's)
+hipError_t launch_reduce_fallback(const double *part, const double *part2, const GuardArgs &g, int64_t len, double *stats, hipStream_t s);
 // finalize_kernel + the slice table / guard flags / operand-ordered C of the NEW model in one launch (the plain EM step: the next pass of
 // that model then runs with PassArgs::skip_qprep)
 hipError_t launch_finalize_qprep(int k, int d, const double *stats, const double *model_in, double *model_out, double tau, int has_ig,

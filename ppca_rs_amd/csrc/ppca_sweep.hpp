@@ -1,5 +1,5 @@
 // ppca_sweep.hpp -- what the streaming sweeps (ppca_scale.hip, ppca_heldout.hip, ppca_kmeans.hip) and the row-wise passes
-// (ppca_sample.hip, ppca_loo.hip, ppca_heldout.hip, the synthetic data of ppca_kernels.hip) share, each defined here and nowhere else:
+// (ppca_sample.hip, ppca_loo.hip, ppca_heldout.hip, the synthetic data of ppca_util.hip) share, each defined here and nowhere else:
 // the counter-based generator and every stream id of the library, the 16-byte column-pair access and the launchers' choice of it, a
 // workgroup's cut of a sweep, and the constants of the per-entry predictives.  DESIGN.md section 4.18.  Not installed.
 #pragma once

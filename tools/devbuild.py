@@ -1,6 +1,6 @@
 """Kernel-tuning build: the named .hip files recompiled with the given -D flags (source list and hipcc line: ppca_rs_amd.build)
 and linked with the current objects of all the other sources into ppca_rs_amd/libppca_hip_<name>.so (select it with PPCA_HIP_LIB).
-    python tools/devbuild.py --name=dev ppca_kernels.hip ppca_em9.hip ppca_llk.hip -DPPCA_DEV_K10   (the fused kernels for k = 10 only)
+    python tools/devbuild.py --name=dev ppca_kernels.hip ppca_pass.hip ppca_em9.hip ppca_llk.hip -DPPCA_DEV_K10   (the fused kernels for k = 10 only)
     python tools/devbuild.py --name=dev16 ppca_em16.hip -DPPCA_E16_ONLY=16
     python tools/devbuild.py --name=pipe0 ppca_generic.hip -DI8_PIPE=0
 `--timing` adds -DPPCA_PHASE_TIMING and recompiles ppca_capi.hip too (it prints the phase table); `--asm` also leaves each
