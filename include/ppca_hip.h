@@ -650,6 +650,31 @@ int ppca_scale_columns_sparse(ppca_ctx *ctx, ppca_sparse *sp, const double *a_ho
 int ppca_fa_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, int32_t d, int32_t k, const double *noise, const double *transform,
                            const double *mean, const double *min_noise, double *noise_out, double *transform_out, double *mean_out,
                            double *llk_in);
+/* Student-t PPCA (section "Student-t PPCA" above) on row-compressed data: state sizes 1 .. 16 and ANY output size
+ * (the limit of 1024 above is the dense sweep's register budget, not the model's).
+ * ppca_t_sparse_estep: ppca_t_estep on the entries of sp.  Per block the row pass of ppca_sparse_infer / ppca_sparse_llk writes z and the
+ * Gaussian log-density of every row to scratch, one row kernel forms delta, u, ell from them, and one kernel over the inverted index
+ * takes the column sums.  Every output is nullable; at least one must be given (all host memory).
+ *   scaled_out     a values view of sp (ppca_scale_columns_sparse): fl(fl(sqrt(u_i)) fl(x_ij - mean_j)) in CSR order and in index order
+ *                  (16 bytes per entry; the two copies of an entry hold the same bits), on sp's pattern, index and weights; without it
+ *                  no per-entry buffer is allocated
+ *   col_sums_host, u_host, maha_host, llks_host, scalars_host   ppca_t_estep's, with m_ij = 1 on the entries of sp; the third scalar
+ *                  sums over every row, an empty one (u = 1: g[0] - 1) included
+ * u, delta, ell and the view depend on the row's entry list alone: bit-identical under any grid limit, block_rows, segment, weights or
+ * position.  Sums and scalars are added in a fixed order (entries of a work item in ascending row, runs in run order, blocks in order;
+ * 1024 rows per workgroup in a fixed tree; no float atomics): bit-identical under any grid limit for a given (block_rows, segment); a
+ * column without an entry gives zeros.  An empty dataset gives zeros and a view without entries.  Synchronises once.
+ * ppca_t_sparse_em_step: ppca_t_em_step on row-compressed data -- (sigma, C, mean), (sigma, C, 0) and the tables uploaded without a
+ * wait, the E-step with the view and the sums, the row and column passes of ppca_sparse_em_accumulate on the view under (sigma, C, 0),
+ * statistics and sums to the host and ppca_t_finalize_host unchanged; the view is released before returning.  llk_in, q_out as
+ * ppca_t_em_step.  One synchronisation of its own.
+ * Preconditions, checked before any device work: sp's d equals the model's, dof positive and finite, an output given (else
+ * PPCA_ERR_INVALID); 1 <= k <= 16 (else PPCA_ERR_UNSUPPORTED); the step on n = 0: PPCA_ERR_EMPTY. */
+int ppca_t_sparse_estep(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, double dof, ppca_sparse **scaled_out,
+                        double *col_sums_host, double *u_host, double *maha_host, double *llks_host, double *scalars_host);
+int ppca_t_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, int32_t d, int32_t k, double sigma, const double *transform,
+                          const double *mean, double dof, double *sigma_out, double *transform_out, double *mean_out, double *llk_in,
+                          double *q_out);
 
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every

@@ -197,6 +197,8 @@ SIGNATURES = {
     "ppca_heldout_score_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppca_scale_columns_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_void_p]),
     "ppca_fa_sparse_em_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p]),
+    "ppca_t_sparse_estep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, c_void_pp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_t_sparse_em_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_double, c_double_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p]),
     "ppca_mix_em_step": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.POINTER(Prior), c_void_pp, C.c_void_p, c_double_p]),
     "ppca_mix_last_rows_used": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "ppca_mix_llk": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, c_double_p, C.c_void_p, C.c_void_p]),

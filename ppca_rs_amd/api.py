@@ -434,7 +434,8 @@ class SparseDataset:
     `holdout` / `holdout_range` / `kfold` split the entries on the host exactly as Dataset's split the same matrix, and
     PPCAModel.heldout_score takes the two parts.  PPCAMix takes one too: llk / llks / infer_cluster / iterate* /
     predict and PPCAMixTrainer.  So does FAModel, one noise level per column: llk / llks / infer / iterate* / predict /
-    heldout_score and FATrainer."""
+    heldout_score and FATrainer.  So does TPPCAModel, the robust model: llk / llks / row_weights / mahalanobis / infer /
+    predict / iterate* and TPPCATrainer.train."""
 
     def __init__(self, indptr, indices, values, n_columns: int, weights=None, *, ctx=None, block_rows: Optional[int] = None,
                  segment: Optional[int] = None):
@@ -519,7 +520,7 @@ class SparseDataset:
         raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
                         "predict / recommend / heldout_score and PPCATrainer are, and PPCAMix.llk / llks / infer_cluster / iterate* / "
                         "predict / recommend and PPCAMixTrainer, and FAModel.llk / llks / infer / iterate* / predict / heldout_score and "
-                        "FATrainer")
+                        "FATrainer, and TPPCAModel.llk / llks / row_weights / mahalanobis / infer / predict / iterate* and TPPCATrainer.train")
 
     @property
     def _values(self) -> np.ndarray:
@@ -1988,12 +1989,19 @@ class TPPCAModel:
     Given u a row is a Gaussian row scaled by 1 / sqrt(u): an iteration is one streaming sweep (distances, weights, log-densities, the
     scaled rows, a few column sums) and the EM pass of PPCAModel on the scaled rows.  The step is an ECM step (transform, then mean,
     then noise, each given the ones before it), not the reference's EM step; as dof -> infinity it becomes that ECM step of the
-    Gaussian model.  LIMITS: state sizes 1 .. 16, output sizes 1 .. 1024.
+    Gaussian model.  LIMITS: state sizes 1 .. 16; output sizes 1 .. 1024 on a `Dataset` (the streaming sweep's register budget), any
+    output size on a `SparseDataset`.
+
+    On a `SparseDataset`: llk / llks / row_weights / mahalanobis / infer / predict / iterate* and TPPCATrainer.train
+    run on the entries alone, and the scaled rows are a values view of the dataset.  `row_compressed=True` (keyword-only) declares a
+    model meant for such data and lifts the constructor's limit on the output size; `init` on a SparseDataset sets it, and every
+    model derived from a flagged one carries it.  Not there: score_heldout and TPPCATrainer.select_state_size (TypeError).
     """
 
     MAX_STATE_SIZE, MAX_OUTPUT_SIZE = 16, 1024
 
-    def __init__(self, isotropic_noise: float, transform, mean, dof: float, *, ctx=None, _estimated_dof: bool = False):
+    def __init__(self, isotropic_noise: float, transform, mean, dof: float, *, ctx=None, _estimated_dof: bool = False,
+                 row_compressed: bool = False):
         base = PPCAModel(isotropic_noise, transform, mean, ctx=ctx)  # (the checks of transform and mean are PPCAModel's)
         dof = float(dof)
         if not (np.isfinite(dof) and dof > 0.0):
@@ -2001,10 +2009,11 @@ class TPPCAModel:
         if not (np.isfinite(base._sigma) and base._sigma > 0.0):
             raise ValueError("isotropic_noise must be a positive finite number")
         d, k = base.output_size, base.state_size
-        if k < 1 or k > self.MAX_STATE_SIZE or d < 1 or d > self.MAX_OUTPUT_SIZE:
+        if k < 1 or k > self.MAX_STATE_SIZE or d < 1 or (d > self.MAX_OUTPUT_SIZE and not row_compressed):
             raise ValueError(f"the Student-t sweep covers state sizes 1 .. {self.MAX_STATE_SIZE} and output sizes 1 .. "
                              f"{self.MAX_OUTPUT_SIZE} (got k={k}, d={d})")
         self._base, self._dof, self._ctx, self._estimated = base, dof, ctx, bool(_estimated_dof)
+        self._row_compressed = bool(row_compressed)
 
     # -- getters ----------------------------------------------------------------
     @property
@@ -2022,6 +2031,11 @@ class TPPCAModel:
     @property
     def dof(self) -> float:
         return self._dof
+
+    @property
+    def row_compressed(self) -> bool:
+        """Whether the model was declared for row-compressed data (no limit on the output size)."""
+        return self._row_compressed
 
     @property
     def output_size(self) -> int:
@@ -2043,15 +2057,17 @@ class TPPCAModel:
     # -- construction -------------------------------------------------------------
     @staticmethod
     def init(state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random", dof: float = 4.0) -> "TPPCAModel":
-        """The start of PPCAModel.init (same seed, same draw; method="pca": its spectral start) with `dof` degrees of freedom."""
+        """The start of PPCAModel.init (same seed, same draw; method="pca": its spectral start) with `dof` degrees of freedom.  On a
+        SparseDataset the model is flagged row_compressed (and method="pca" raises PPCAModel.init's ValueError)."""
         if state_size < 1:
             raise ValueError("state_size must be >= 1")
-        return TPPCAModel.from_ppca(PPCAModel.init(state_size, dataset, seed=seed, method=method), dof)
+        return TPPCAModel.from_ppca(PPCAModel.init(state_size, dataset, seed=seed, method=method), dof,
+                                    row_compressed=isinstance(dataset, SparseDataset))
 
     @staticmethod
-    def from_ppca(model: PPCAModel, dof: float) -> "TPPCAModel":
+    def from_ppca(model: PPCAModel, dof: float, row_compressed: bool = False) -> "TPPCAModel":
         """The t model with the Gaussian model's sigma, C and mean."""
-        return TPPCAModel(model._sigma, model._c, model._mean, dof, ctx=model._ctx)
+        return TPPCAModel(model._sigma, model._c, model._mean, dof, ctx=model._ctx, row_compressed=row_compressed)
 
     def gaussian(self) -> PPCAModel:
         """PPCAModel with the same sigma, C and mean (the limit dof -> infinity)."""
@@ -2060,7 +2076,8 @@ class TPPCAModel:
     def to_canonical(self) -> "TPPCAModel":
         """The rotation of PPCAModel.to_canonical on C; sigma, mean and dof are untouched."""
         b = self._base.to_canonical()
-        return TPPCAModel(b._sigma, b._c, b._mean, self._dof, ctx=self._ctx, _estimated_dof=self._estimated)
+        return TPPCAModel(b._sigma, b._c, b._mean, self._dof, ctx=self._ctx, _estimated_dof=self._estimated,
+                          row_compressed=self._row_compressed)
 
     def sample(self, dataset_size: int, mask_prob: float, seed: Optional[int] = None, *, ctx=None) -> Dataset:
         """Host-side numpy (like posterior_sampler(), not a GPU path): Gaussian rows C x + noise, divided by sqrt(u) with
@@ -2078,7 +2095,9 @@ class TPPCAModel:
     # -- passes ---------------------------------------------------------------------
     def _estep(self, dataset: Dataset, *, scaled: bool = False, col_sums: bool = False, u: bool = False, maha: bool = False,
                llks: bool = False, scalars: bool = False):
-        """ppca_t_estep: (scaled rows as a Dataset, column sums V | A | T | sq, u, delta, llks, scalars), None where not asked for."""
+        """ppca_t_estep: (scaled rows as a Dataset, column sums V | A | T | sq, u, delta, llks, scalars), None where not asked for.
+        On a SparseDataset ppca_t_sparse_estep: the scaled rows are a values view of it, a SparseDataset whose values
+        come to the host if csr() / to_dense() asks for them, not before (as SparseDataset._scale_columns's)."""
         if dataset._d != self.output_size:
             raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {self.output_size}")
         ctx, n, d, k = dataset._ctx, len(dataset), self.output_size, self.state_size
@@ -2086,6 +2105,16 @@ class TPPCAModel:
         cs = np.empty((k + 3) * d) if col_sums else None
         uu, mm, ll = (np.empty(n) if f else None for f in (u, maha, llks))
         sc = np.empty(4) if scalars else None
+        if isinstance(dataset, SparseDataset):
+            check(lib().ppca_t_sparse_estep(ctx.handle, dataset._sh, self._base._device(ctx).h, self._dof, C.byref(h) if scaled else None,
+                                            ptr(cs), ptr(uu), ptr(mm), ptr(ll), ptr(sc)))
+            view = None
+            if scaled:
+                view = SparseDataset.__new__(SparseDataset)
+                view.__dict__.update(dataset.__dict__)
+                view.__dict__.pop("holdout_counts", None)
+                view._vals, view._handle = None, h
+            return view, cs, uu, mm, ll, sc
         check(lib().ppca_t_estep(ctx.handle, dataset._h, self._base._device(ctx).h, self._dof, C.byref(h) if scaled else None, ptr(cs),
                                  ptr(uu), ptr(mm), ptr(ll), ptr(sc)))
         return (Dataset._wrap(h, ctx) if scaled else None), cs, uu, mm, ll, sc
@@ -2105,8 +2134,10 @@ class TPPCAModel:
 
     def mahalanobis(self, dataset: Dataset):
         """(delta, m): the rows' squared Mahalanobis distances (x - mean)_O^T (C_O C_O^T + sigma^2 I)^-1 (x - mean)_O and their
-        numbers of observed entries (a second streaming pass counts them)."""
+        numbers of observed entries (a second streaming pass counts them; on a SparseDataset they are the rows' lengths)."""
         delta = self._estep(dataset, maha=True)[3]
+        if isinstance(dataset, SparseDataset):
+            return delta, np.diff(dataset._indptr).astype(np.int64)
         m = dataset._scale_columns(np.ones(self.output_size), l=np.ones(self.output_size), out=False, row_sums=True)[2]
         return delta, np.rint(m).astype(np.int64)
 
@@ -2114,6 +2145,12 @@ class TPPCAModel:
         """The posterior of gaussian(): the posterior mean of the state does not depend on dof; covariances() are the u = 1
         covariances (given the row's scale u they are these divided by u)."""
         return self._base.infer(dataset)
+
+    def predict(self, sparse: "SparseDataset", query):
+        """gaussian().predict: (mean, var) of a new reading at the query positions of row-compressed data.  As with `infer`, the mean
+        mean_j + c_j . z does not depend on dof, and the variance is the u = 1 variance (given the row's scale u it is this divided
+        by u)."""
+        return self._base.predict(sparse, query)
 
     def smooth(self, dataset: Dataset) -> Dataset:
         """C z + mean for every dimension (gaussian().smooth)."""
@@ -2128,6 +2165,7 @@ class TPPCAModel:
         dof + m degrees of freedom around mean_j + c_j . z, of scale (sigma^2 + c_j^T Sigma c_j) (dof + delta) / (dof + m) -- an
         outlying row (large delta) widens its own predictive.  z2 takes the variance scale (dof + m) / (dof + m - 2); where
         dof + m <= 2 there is none and the entry adds 0 to it.  One pass on the GPU; nothing of size N x d is allocated."""
+        _t_no_sparse_score("TPPCAModel.score_heldout", train, held)
         if train._d != self.output_size:
             raise ValueError(f"dataset has {train._d} dimensions but the model has output size {self.output_size}")
         ctx = train._ctx
@@ -2135,24 +2173,27 @@ class TPPCAModel:
                                                                                      self._base._device(ctx).h, self._dof, t, c, r))
 
     def _iterate(self, dataset: Dataset, estimate_dof: bool, want_llk: bool):
-        ctx = dataset._ctx
         if len(dataset) == 0:
             raise ValueError("dataset is empty")
         d, k = self.output_size, self.state_size
         if dataset._d != d:
             raise ValueError(f"dataset has {dataset._d} dimensions but the model has output size {d}")
+        ctx = dataset._ctx
         s_out, c_out, m_out = C.c_double(0.0), np.empty((d, k)), np.empty(d)
         llk, q = C.c_double(0.0), C.c_double(0.0)
-        check(lib().ppca_t_em_step(ctx.handle, dataset._h, d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean), self._dof,
-                                   C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None,
-                                   C.byref(q) if estimate_dof else None))
+        sparse = isinstance(dataset, SparseDataset)
+        fn, h = (lib().ppca_t_sparse_em_step, dataset._sh) if sparse else (lib().ppca_t_em_step, dataset._h)
+        check(fn(ctx.handle, h, d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean), self._dof,
+                 C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None, C.byref(q) if estimate_dof else None))
         dof = _t_dof_root(q.value) if estimate_dof else self._dof
-        new = TPPCAModel(s_out.value, c_out, m_out, dof, ctx=self._ctx, _estimated_dof=self._estimated or estimate_dof)
+        new = TPPCAModel(s_out.value, c_out, m_out, dof, ctx=self._ctx, _estimated_dof=self._estimated or estimate_dof,
+                         row_compressed=self._row_compressed or sparse)
         return new, (llk.value if want_llk else None)
 
     def iterate(self, dataset: Dataset, estimate_dof: bool = False) -> "TPPCAModel":
         """One ECM iteration (transform, then mean, then noise, each given the ones before it; with estimate_dof then dof, the root
-        of ln(nu / 2) - psi(nu / 2) + 1 + q = 0 on [0.5, 1e4]): the t log-likelihood cannot decrease."""
+        of ln(nu / 2) - psi(nu / 2) + 1 + q = 0 on [0.5, 1e4]): the t log-likelihood cannot decrease.  `dataset` may be a
+        SparseDataset (ppca_t_sparse_em_step)."""
         return self._iterate(dataset, estimate_dof, False)[0]
 
     def iterate_with_llk(self, dataset: Dataset, estimate_dof: bool = False):
@@ -2162,13 +2203,17 @@ class TPPCAModel:
     # -- serialisation (own npz container) ----------------------------------------------
     def dump(self) -> bytes:
         return _npz_dump("ppca_rs_amd.TPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean,
-                         dof=self._dof, estimated_dof=self._estimated)
+                         dof=self._dof, estimated_dof=self._estimated,
+                         # (an unflagged model dumps the container it always dumped: absent reads as off)
+                         **({"row_compressed": True} if self._row_compressed else {}))
 
     @staticmethod
     def load(data: bytes) -> "TPPCAModel":
         return _npz_load(data, "ppca_rs_amd.TPPCAModel", "a TPPCAModel",
                          lambda z: TPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"], float(z["dof"]),
-                                              _estimated_dof=bool(z["estimated_dof"])))
+                                              _estimated_dof=bool(z["estimated_dof"]),
+                                              # (a dump from before the flag existed has no such entry: off)
+                                              row_compressed=bool(z["row_compressed"]) if "row_compressed" in z.files else False))
 
     def __getstate__(self):
         return self.dump()
@@ -2180,9 +2225,18 @@ class TPPCAModel:
         return (self.isotropic_noise, self.transform, self.mean, self.dof)
 
 
+def _t_no_sparse_score(what: str, *datasets) -> None:
+    """The t predictive is not built on row-compressed data: raised before anything touches a device."""
+    if any(isinstance(ds, SparseDataset) for ds in datasets):
+        raise TypeError(f"{what} is not available on a SparseDataset: held-out scoring under the t model is not built on row-compressed "
+                        "data (DESIGN.md section 7); PPCAModel.heldout_score scores the two parts of SparseDataset.holdout under "
+                        "gaussian()")
+
+
 @dataclass
 class TPPCATrainer:
-    """EM driver of TPPCAModel: the loop and metrics of FATrainer."""
+    """EM driver of TPPCAModel: the loop and metrics of FATrainer.  `dataset` may be a SparseDataset (train; init="pca" raises
+    PPCAModel.init's ValueError)."""
 
     dataset: Dataset
 
@@ -2201,7 +2255,8 @@ class TPPCATrainer:
     def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
                           init: str = "random", dof: float = 4.0, estimate_dof: bool = False, folds: int = 1):
         """PPCATrainer.select_state_size with TPPCAModel fits at `dof` degrees of freedom (estimated from there with estimate_dof),
-        scored by the t predictive: [(state_size, HeldOutScore, TPPCAModel)]."""
+        scored by the t predictive: [(state_size, HeldOutScore, TPPCAModel)].  Not on a SparseDataset (TypeError)."""
+        _t_no_sparse_score("TPPCATrainer.select_state_size", self.dataset)
         return _select_state_size(self.dataset, state_sizes, fraction, seed, lambda tr, k: TPPCATrainer(tr).train(
             state_size=k, dof=dof, estimate_dof=estimate_dof, n_iters=n_iters, quiet=True, seed=seed, init=init), folds)
 

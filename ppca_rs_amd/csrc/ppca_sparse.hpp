@@ -1,6 +1,6 @@
-// ppca_sparse.hpp -- what the translation units of the row-compressed data path share (SparseDataset, DESIGN.md sections 4.20 - 4.26):
-// ppca_sparse.hip (container, EM passes, llk / infer / predict), ppca_sparse_mix.hip, ppca_sparse_topn.hip, ppca_sparse_heldout.hip
-// and ppca_sparse_fa.hip.  Internal: not installed.
+// ppca_sparse.hpp -- what the translation units of the row-compressed data path share (SparseDataset, DESIGN.md sections 4.20 - 4.28):
+// ppca_sparse.hip (container, EM passes, llk / infer / predict), ppca_sparse_mix.hip, ppca_sparse_topn.hip, ppca_sparse_heldout.hip,
+// ppca_sparse_fa.hip and ppca_sparse_robust.hip.  Internal: not installed.
 //
 // Storage.  CSR on the device: row_ptr (int64, n + 1), col (int32, nnz, strictly increasing within a row), val (fp64, nnz).  Rows are
 // cut into blocks of block_rows (fixed at construction: the records of a block stay under 1 GiB at k = 16).  Per block the host builds

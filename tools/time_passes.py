@@ -25,7 +25,8 @@ SparseDataset (see sparse_legs); with `--sparse-heldout` beside 
 data (see sparse_heldout_legs); with `--sparse-topn N_TOP` beside either, ONLY the legs of PPCAModel.recommend on that
 data (see sparse_topn_legs); with `--mix NM` beside either, ONLY the legs of PPCAMix on that data (see
 sparse_mix_legs); with `--sparse-topn N_TOP` and `--mix NM` together, ONLY the legs of PPCAMix.recommend (see
-sparse_mix_topn_legs); with `--fa` beside either, ONLY the legs of FAModel on that data (see sparse_fa_legs)."""
+sparse_mix_topn_legs); with `--fa` beside either, ONLY the legs of FAModel on that data (see sparse_fa_legs); with
+`--robust` beside either, ONLY the legs of TPPCAModel on that data (see sparse_t_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -486,6 +487,56 @@ def sparse_fa_legs(reps=5):
     print(f"  (a) {36.0 * nnz / med[0] / 1e6:.0f} GB/s at 36 B per entry;  (b) {8.0 * nnz / med[1] / 1e6:.0f} GB/s at 8 B per entry")
 
 
+def sparse_t_legs(reps=5):
+    """TPPCAModel on a SparseDataset (`--robust [--reps R]` beside `--sparse DENSITY` or `--sparse-rows M`), in one
+    process, alternating, every repetition timed on its own behind a synchronise: (1) PPCAModel.llks(sp), (2) TPPCAModel.llks(sp),
+    (3) the E-step with the view and the column sums, (4) PPCAModel.iterate(sp), (5) TPPCAModel.iterate(sp).  The yardstick is the
+    Gaussian model's own passes in the same process: reported are (2) / (1), (3) / (4) and (5) / (4)."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    ix, v = cols.int().cpu().numpy(), vals.cpu().numpy()
+    del cols, vals
+    sp = P.SparseDataset(indptr, ix, v, d, ctx=ctx)
+    sp._sh
+    print(f"  host: the index, row lists and work items {sp.index_build_seconds():.2f} s", flush=True)
+    model = P.PPCAModel.init(k, sp, seed=3).iterate(sp)
+    t = P.TPPCAModel.from_ppca(model, 4.0, row_compressed=True)
+
+    def series(fn, r, warm):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:72s} median {med:10.3f} ms  min {ts.min():10.3f}  max {ts.max():10.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    legs = [("(1) PPCAModel.llks(sp)", lambda: model.llks(sp)), ("(2) TPPCAModel.llks(sp)", lambda: t.llks(sp)),
+            ("(3) t E-step: view + column sums", lambda: t._estep(sp, scaled=True, col_sums=True, scalars=True)),
+            ("(4) PPCAModel.iterate(sp)", lambda: model.iterate(sp)), ("(5) TPPCAModel.iterate(sp)", lambda: t.iterate(sp))]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn, reps, 2))
+    med = [report(name, np.concatenate(got[name])) for name, _ in legs]
+    spread = [float((np.concatenate(got[name]).max() - np.concatenate(got[name]).min()) / m_) for (name, _), m_ in zip(legs, med)]
+    print(f"  (2) / (1): {med[1] / med[0]:.3f};  (3) / (4): {med[2] / med[3]:.3f};  (5) / (4): {med[4] / med[3]:.3f}  "
+          f"(run-to-run spread of (4), (5): {spread[3]:.1%}, {spread[4]:.1%});  (1) + (3) + (4) = {med[0] + med[2] + med[3]:.3f} ms "
+          f"against (5) = {med[4]:.3f} ms")
+
+
+if "--robust" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
+    sparse_t_legs()
+    sys.exit(0)
 if "--fa" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
     sparse_fa_legs()
     sys.exit(0)
