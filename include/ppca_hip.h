@@ -798,6 +798,14 @@ int ppca_mix_loo_predictive(ppca_ctx *ctx, ppca_dataset *ds, ppca_model *const *
  * pipelines, the periodic flush of the integer accumulators) under the oracle.  n_workgroups <= 0 restores the device's
  * CU count.  Results do not depend on the grid beyond the order of the partial sums. */
 int ppca_ctx_set_grid_limit(ppca_ctx *ctx, int32_t n_workgroups);
+/* Test hook: afterwards the context behaves as a newly created one, except that every device byte it owns or caches holds `byte`
+ * (its low eight bits).  Takes the context's lock, waits for its stream, returns every scratch buffer the context keeps across calls
+ * to its block cache and forgets what it remembered about them (slice tables, guard words, the place of the last log-likelihood, the
+ * rows of the last mixture step, the split pipeline's trace), fills every cached block on the stream and waits again.  blocks_out /
+ * bytes_out (nullable): how many blocks and bytes were filled.  Blocks that a live dataset, model or row-compressed handle owns are
+ * not in the cache and are never touched; pinned host buffers stay as they are.  For tests of "no pass depends on what its recycled
+ * memory held" (tests/test_gpu_recycled_memory.py); the library itself never calls it. */
+int ppca_ctx_dirty_scratch(ppca_ctx *ctx, int32_t byte, int64_t *blocks_out, int64_t *bytes_out);
 /* (ABI 6) Test / measurement hook of the EM pass's int8 form of the mask-side statistics (k <= 10): a 32-sample tile with at most
  * max_rows rows that do not fit the fixed-point form -- outlier samples, heavy sample weights -- sends those rows round it (exact
  * fp64 additions into the accumulators, what the reference's f64 sums do with such a row, ppca_model.rs:297-306) instead of raising

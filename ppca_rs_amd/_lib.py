@@ -220,6 +220,7 @@ SIGNATURES = {
     "ppca_mix_em_step_sharded": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.POINTER(Prior), c_void_pp, C.c_void_p, c_double_p]),
     "ppca_em_step_group": (C.c_int, [c_void_pp, C.c_int32, c_void_pp, c_void_pp, C.POINTER(Prior), c_void_pp, c_double_p]),
     "ppca_ctx_set_grid_limit": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ppca_ctx_dirty_scratch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ppca_ctx_set_heavy_rows": (C.c_int, [C.c_void_p, C.c_int32]),
     "ppca_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "ppca_generic_last_trace": (C.c_int, [C.c_void_p, C.POINTER(GenericTrace)]),
@@ -319,6 +320,13 @@ class Context:
     def set_grid_limit(self, n_workgroups: int = 0) -> None:
         """Test hook (ppca_ctx_set_grid_limit): cap the workgroups of every persistent-grid launch; 0 restores."""
         check(lib().ppca_ctx_set_grid_limit(self.handle, int(n_workgroups)))
+
+    def dirty_scratch(self, byte: int):
+        """Test hook (ppca_ctx_dirty_scratch): the context as a new one, except that every device byte it owns or caches holds `byte`;
+        -> (blocks, bytes) filled."""
+        blocks, nbytes = C.c_int64(0), C.c_int64(0)
+        check(lib().ppca_ctx_dirty_scratch(self.handle, int(byte), C.byref(blocks), C.byref(nbytes)))
+        return int(blocks.value), int(nbytes.value)
 
     def set_heavy_rows(self, max_rows: int = 8) -> None:
         """Test hook (ppca_ctx_set_heavy_rows): rows of a tile that may go round the fixed-point form of the EM pass's mask-side

@@ -2395,6 +2395,52 @@ extern "C" int ppca_ctx_set_grid_limit(ppca_ctx *ctx, int32_t n_workgroups) {
     return PPCA_OK;
 }
 
+// Test hook: the context as a newly created one, except that every device byte it owns or caches holds `byte`.  The grow-only scratch
+// goes back to the block cache (a block nobody else holds: datasets, models and row-compressed handles keep their own references and
+// their blocks never enter the cache while they live), what the host remembers about it is forgotten, and every cached block is filled
+// on the context's stream.  Pinned host buffers stay.
+extern "C" int ppca_ctx_dirty_scratch(ppca_ctx *ctx, int32_t byte, int64_t *blocks_out, int64_t *bytes_out) {
+    if (!ctx) return fail(PPCA_ERR_INVALID, "null context");
+    USE_CTX(ctx);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    size_t work_cap = 0;
+    BufRef *refs[] = {&ctx->part, &ctx->stats, &ctx->scal, &ctx->work, &ctx->qtab, &ctx->errb, &ctx->gws, &ctx->mixpack,
+                      &ctx->mixaux, &ctx->mixq, &ctx->mixred, &ctx->canon[0], &ctx->canon[1]};
+    size_t *caps[] = {&ctx->part_cap, &ctx->stats_cap, &ctx->scal_cap, &work_cap, &ctx->qtab_cap, &ctx->errb_cap, &ctx->gws_cap,
+                      &ctx->mixpack_cap, &ctx->mixaux_cap, &ctx->mixq_cap, &ctx->mixred_cap, &ctx->canon_cap[0], &ctx->canon_cap[1]};
+    for (size_t i = 0; i < sizeof(refs) / sizeof(refs[0]); ++i) {
+        refs[i]->reset();
+        *caps[i] = 0;
+    }
+    for (int i = 0; i < 7; ++i) {
+        ctx->mix[i].reset();
+        ctx->mix_cap[i] = 0;
+    }
+    ctx->qtab_base = ctx->qtab_model = nullptr;
+    ctx->qtab_stamp = 0;
+    ctx->mixq_base = nullptr;
+    ctx->mixq_stride = 0;
+    ctx->mixq_slots.clear();
+    ctx->guard_words.clear();
+    ctx->stats_llk_at = -1;
+    ctx->mix_rows_used.clear();
+    ctx->gen_trace = ppca_generic_trace{};
+    int64_t blocks = 0, bytes = 0;
+    if (ctx->pool) {
+        std::lock_guard<std::mutex> lk(ctx->pool->mu);
+        for (auto &b : ctx->pool->blocks) {
+            HIP_TRY(hipMemsetAsync(b.second, byte & 0xff, b.first, ctx->stream));
+            ++blocks;
+            bytes += (int64_t)b.first;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ensure(ctx->work, work_cap, 2048 * sizeof(double))) return PPCA_ERR_HIP;  // (every context holds it: ppca_ctx_create)
+    if (blocks_out) *blocks_out = blocks;
+    if (bytes_out) *bytes_out = bytes;
+    return PPCA_OK;
+}
+
 extern "C" int ppca_ctx_set_heavy_rows(ppca_ctx *ctx, int32_t max_rows) {
     if (!ctx) return fail(PPCA_ERR_INVALID, "null context");
     USE_CTX(ctx);
