@@ -675,6 +675,39 @@ int ppca_t_sparse_estep(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model,
 int ppca_t_sparse_em_step(ppca_ctx *ctx, ppca_sparse *sp, int32_t d, int32_t k, double sigma, const double *transform,
                           const double *mean, double dof, double *sigma_out, double *transform_out, double *mean_out, double *llk_in,
                           double *q_out);
+/* PPCA with a known precision per entry (section "PPCA with a known precision per entry" above) on row-compressed data (DESIGN.md
+ * 4.30): state sizes 1 .. 16 and ANY output size (the limit of 1024 above is the dense sweep's).  An entry is observed iff it is
+ * stored, and every stored entry has a precision that is finite and > 0 -- unlike the dense rule there is NO masking precision here
+ * (p = 0 or NaN): an entry that should not count is not stored.  Per row and per column the quantities are those of ppca_h_estep with
+ * O the row's stored entries; an empty row has ell = 0, z = 0, Sigma = I.
+ * ppca_h_sparse_precisions: the precisions of sp's entries as a values view of sp (ppca_scale_columns_sparse's: it shares sp's
+ * pattern, row lists, inverted index, work items and weights; 16 bytes per entry of its own).  prec_host: nnz doubles in the order of
+ * sp's values (CSR), each finite and > 0, else PPCA_ERR_INVALID before any device work.  The CSR-order copy is uploaded; the
+ * index-order copy is filled on the device (per index entry, a bisection of its row's column list).  Synchronises once.  Release
+ * with ppca_sparse_free.
+ * The three passes take (sp, prec) with prec a view made from sp or from a dataset that shares sp's pattern on the device
+ * (ppca_sparse_with_weights); anything else is PPCA_ERR_INVALID: no pattern is compared on the device.
+ * ppca_h_sparse_estep: ppca_h_estep's outputs and nullability (llks n, states n x k, covs n x k x k: host or device destinations;
+ * stats_host: ppca_h_stats_len(d, k) doubles in ppca_h_estep's layout and order; scalars_host: 4 doubles, sum w | sum w ell | rows
+ * with an entry | 0).  ell, z and Sigma of a row depend on its entry list alone: bit-identical under any grid limit, block_rows,
+ * segment, weights or position.  The statistics are added in a fixed order (entries of a work item in ascending row, runs in run
+ * order, blocks in order; no float atomics): bit-identical under any grid limit for a given (block_rows, segment).  They live in
+ * scratch of the pass's own: ppca_em_last_llk keeps reporting the last plain step.
+ * ppca_h_sparse_em_step: ppca_h_em_step on row-compressed data -- model upload, E-step, one wait for the results, then the M-step of
+ * ppca_h_finalize_host (the same code, without that entry's limit on d).  llk_in (nullable): sum_i w_i ell_i of the INPUT model.
+ * ppca_h_sparse_predict: ppca_sparse_predict under the posterior of the known-precision model: mean = mean_j + c_j . z and
+ * var = c_j^T Sigma c_j + sigma^2, the predictive of a reading at UNIT precision (one at precision q has var + sigma^2 (1 / q - 1)); a
+ * row without an entry gives the prior predictive (mean_j, |c_j|^2 + sigma^2).
+ * Preconditions of the three, checked before any device work: sp's d equals the model's, prec a view of sp (else PPCA_ERR_INVALID);
+ * 1 <= k <= 16 (else PPCA_ERR_UNSUPPORTED); n = 0: PPCA_ERR_EMPTY.  (The model or the host arrays lead the parameter lists, as in
+ * ppca_model_download and the *_finalize_host family.) */
+int ppca_h_sparse_precisions(const double *prec_host, ppca_ctx *ctx, ppca_sparse *sp, ppca_sparse **view_out);
+int ppca_h_sparse_estep(const ppca_model *model, ppca_ctx *ctx, ppca_sparse *sp, ppca_sparse *prec, double *llks, double *states,
+                        double *covs, double *stats_host, double *scalars_host);
+int ppca_h_sparse_em_step(int32_t d, int32_t k, double sigma, const double *transform, const double *mean, ppca_ctx *ctx, ppca_sparse *sp,
+                          ppca_sparse *prec, double *sigma_out, double *transform_out, double *mean_out, double *llk_in);
+int ppca_h_sparse_predict(const ppca_model *model, ppca_ctx *ctx, ppca_sparse *sp, ppca_sparse *prec, const int64_t *query_row_ptr,
+                          const int32_t *query_col, double *mean_host, double *var_host);
 
 /* ------------------------------------------- sample-sharded EM across GPUs */
 /* The dataset shards by contiguous row blocks (the rule of Dataset.chunks, src/python_bindings.rs:110-118); every

@@ -435,7 +435,9 @@ class SparseDataset:
     PPCAModel.heldout_score takes the two parts.  PPCAMix takes one too: llk / llks / infer_cluster / iterate* /
     predict and PPCAMixTrainer.  So does FAModel, one noise level per column: llk / llks / infer / iterate* / predict /
     heldout_score and FATrainer.  So does TPPCAModel, the robust model: llk / llks / row_weights / mahalanobis / infer /
-    predict / iterate* and TPPCATrainer.train."""
+    predict / iterate* and TPPCATrainer.train.  So does HPPCAModel, with a known precision per stored entry: llk / llks /
+    infer / predict / iterate* and HPPCATrainer.train take (sparse, precisions); `with_values` lets the precisions
+    travel as a SparseDataset of the same pattern."""
 
     def __init__(self, indptr, indices, values, n_columns: int, weights=None, *, ctx=None, block_rows: Optional[int] = None,
                  segment: Optional[int] = None):
@@ -520,7 +522,8 @@ class SparseDataset:
         raise TypeError("this operation is not available on a SparseDataset (DESIGN.md section 7); PPCAModel.llk / llks / infer / iterate* / "
                         "predict / recommend / heldout_score and PPCATrainer are, and PPCAMix.llk / llks / infer_cluster / iterate* / "
                         "predict / recommend and PPCAMixTrainer, and FAModel.llk / llks / infer / iterate* / predict / heldout_score and "
-                        "FATrainer, and TPPCAModel.llk / llks / row_weights / mahalanobis / infer / predict / iterate* and TPPCATrainer.train")
+                        "FATrainer, and TPPCAModel.llk / llks / row_weights / mahalanobis / infer / predict / iterate* and TPPCATrainer.train, "
+                        "and HPPCAModel.llk / llks / infer / predict / iterate* and HPPCATrainer.train with (sparse, precisions)")
 
     @property
     def _values(self) -> np.ndarray:
@@ -583,6 +586,24 @@ class SparseDataset:
             h = C.c_void_p()
             check(lib().ppca_sparse_with_weights(self._handle, ptr(w), C.byref(h)))
             out._handle = h
+        return out
+
+    def with_values(self, values) -> "SparseDataset":
+        """Same pattern, weights, tiling and ctx, new values (nnz, finite, aligned with csr()[2]).  Host work: no device is touched and
+        the new dataset uploads on first use.  This is how per-entry quantities travel with the data -- the precisions of HPPCAModel:
+        `sp.with_values(p).holdout(f, seed)` splits p exactly as `sp.holdout(f, seed)` splits sp, because the split is keyed by
+        (seed, row, column)."""
+        v = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
+        if v.ndim != 1 or v.shape[0] != self.nnz:
+            raise ValueError(f"values must be 1-D of length nnz = {self.nnz}; got shape {v.shape}")
+        if not np.isfinite(v).all():
+            raise ValueError("values must be finite (an entry that is missing is simply not stored)")
+        out = SparseDataset.__new__(SparseDataset)
+        out.__dict__.update(self.__dict__)
+        out.__dict__.pop("holdout_counts", None)
+        v = v.copy()
+        v.setflags(write=False)
+        out._vals, out._handle = v, None
         return out
 
     def empty_dimensions(self) -> List[int]:
@@ -2271,20 +2292,31 @@ class HPPCAModel:
     Every pass takes (dataset, precisions): `precisions` is a Dataset, or an array, of the dataset's shape.  An entry is observed iff
     its value is finite and its precision is finite and > 0; a precision of NaN or 0 masks the entry whatever its value; a negative or
     +inf precision raises PPCAError (PPCA_ERR_INVALID).  An iteration is an ECM step (transform, then mean, then noise, each given the
-    ones before it, all from one E-step), not the reference's EM step.  LIMITS: state sizes 1 .. 16, output sizes 1 .. 1024.
+    ones before it, all from one E-step), not the reference's EM step.  LIMITS: state sizes 1 .. 16; output sizes 1 .. 1024 on a
+    `Dataset` (the dense sweep's register budget), any output size on a `SparseDataset`.
+
+    On a `SparseDataset`: llk / llks / infer / predict / iterate* and HPPCATrainer.train take (sparse, precisions),
+    `precisions` a 1-D array of length nnz aligned with `sparse.csr()[2]`, or a SparseDataset of the identical pattern
+    (`sparse.with_values(p)`, or a part of its split).  THE RULE DIFFERS FROM THE DENSE ONE: an entry is observed iff it is stored,
+    and every stored entry needs a precision that is finite and > 0 -- there is no masking precision on this data (0, NaN, a negative
+    or an infinite one raise ValueError before a device is touched); an entry that should not count is not stored.
+    `row_compressed=True` (keyword-only) declares a model meant for such data and lifts the constructor's limit on the output size;
+    `init` on a SparseDataset sets it, and every model derived from a flagged one carries it.  Not there: smooth / extrapolate (use
+    predict), score_heldout and HPPCATrainer.select_state_size (TypeError).
     """
 
     MAX_STATE_SIZE, MAX_OUTPUT_SIZE = 16, 1024
 
-    def __init__(self, isotropic_noise: float, transform, mean, *, ctx=None):
+    def __init__(self, isotropic_noise: float, transform, mean, *, ctx=None, row_compressed: bool = False):
         base = PPCAModel(isotropic_noise, transform, mean, ctx=ctx)  # (the checks of transform and mean are PPCAModel's)
         if not (np.isfinite(base._sigma) and base._sigma > 0.0):
             raise ValueError("isotropic_noise must be a positive finite number")
         d, k = base.output_size, base.state_size
-        if k < 1 or k > self.MAX_STATE_SIZE or d < 1 or d > self.MAX_OUTPUT_SIZE:
+        if k < 1 or k > self.MAX_STATE_SIZE or d < 1 or (d > self.MAX_OUTPUT_SIZE and not row_compressed):
             raise ValueError(f"the per-entry-precision sweep covers state sizes 1 .. {self.MAX_STATE_SIZE} and output sizes 1 .. "
                              f"{self.MAX_OUTPUT_SIZE} (got k={k}, d={d})")
         self._base, self._ctx = base, ctx
+        self._row_compressed = bool(row_compressed)
 
     # -- getters ----------------------------------------------------------------
     @property
@@ -2311,6 +2343,11 @@ class HPPCAModel:
     def n_parameters(self) -> int:
         return self._base.n_parameters
 
+    @property
+    def row_compressed(self) -> bool:
+        """Whether the model was declared for row-compressed data (no limit on the output size)."""
+        return self._row_compressed
+
     def __repr__(self) -> str:
         return f"HPPCAModel(isotropic_noise={self._base._sigma}, transform=array({self._base._c}), mean=array({self._base._mean}))"
 
@@ -2318,14 +2355,16 @@ class HPPCAModel:
     @staticmethod
     def init(state_size: int, dataset: Dataset, seed: Optional[int] = None, method: str = "random") -> "HPPCAModel":
         """The start of PPCAModel.init (same seed, same draw; method="pca": its spectral start through PPCAModel.from_moments, which
-        ignores the precisions)."""
+        ignores the precisions).  On a SparseDataset the model is flagged row_compressed (and method="pca" raises PPCAModel.init's
+        ValueError)."""
         if state_size < 1:
             raise ValueError("state_size must be >= 1")
-        return HPPCAModel.from_ppca(PPCAModel.init(state_size, dataset, seed=seed, method=method))
+        return HPPCAModel.from_ppca(PPCAModel.init(state_size, dataset, seed=seed, method=method),
+                                    row_compressed=isinstance(dataset, SparseDataset))
 
     @staticmethod
-    def from_ppca(model: PPCAModel) -> "HPPCAModel":
-        return HPPCAModel(model._sigma, model._c, model._mean, ctx=model._ctx)
+    def from_ppca(model: PPCAModel, row_compressed: bool = False) -> "HPPCAModel":
+        return HPPCAModel(model._sigma, model._c, model._mean, ctx=model._ctx, row_compressed=row_compressed)
 
     def gaussian(self) -> PPCAModel:
         """PPCAModel with the same sigma, C and mean (every precision 1)."""
@@ -2334,7 +2373,7 @@ class HPPCAModel:
     def to_canonical(self) -> "HPPCAModel":
         """The rotation of PPCAModel.to_canonical on C; sigma and mean are untouched."""
         b = self._base.to_canonical()
-        return HPPCAModel(b._sigma, b._c, b._mean, ctx=self._ctx)
+        return HPPCAModel(b._sigma, b._c, b._mean, ctx=self._ctx, row_compressed=self._row_compressed)
 
     def sample(self, precisions, seed: Optional[int] = None, *, ctx=None) -> Dataset:
         """Host-side numpy (like TPPCAModel.sample): one row per row of `precisions` (an array or a Dataset, N x output_size),
@@ -2367,18 +2406,53 @@ class HPPCAModel:
             precisions = Dataset(p, ctx=dataset._ctx)
         return precisions
 
+    def _sparse_pair(self, sparse: "SparseDataset", precisions) -> "_SparsePrecisions":
+        """`precisions` as a device view of `sparse` (ppca_h_sparse_precisions): a 1-D array of length nnz aligned
+        with sparse.csr()[2], a SparseDataset of the identical pattern, or a view built before (HPPCATrainer builds it once).  Every
+        check comes before a device is touched."""
+        if sparse._d != self.output_size:
+            raise ValueError(f"dataset has {sparse._d} dimensions but the model has output size {self.output_size}")
+        if len(sparse) == 0:
+            raise ValueError("dataset is empty")
+        if isinstance(precisions, _SparsePrecisions):
+            if not precisions._matches(sparse):
+                raise ValueError("the precisions were prepared for a dataset of another pattern")
+            return precisions
+        return _SparsePrecisions(sparse, precisions)
+
     def _estep(self, dataset: Dataset, precisions, *, llks: bool = False, states: bool = False, covs: bool = False, stats: bool = False,
                scalars: bool = False):
-        """ppca_h_estep: (llks, states, covs, statistics, scalars), None where not asked for."""
-        prec = self._pair(dataset, precisions)
+        """ppca_h_estep: (llks, states, covs, statistics, scalars), None where not asked for.  On a SparseDataset
+        ppca_h_sparse_estep."""
+        sparse = isinstance(dataset, SparseDataset)
+        prec = self._sparse_pair(dataset, precisions) if sparse else self._pair(dataset, precisions)
         ctx, n, d, k = dataset._ctx, len(dataset), self.output_size, self.state_size
         ll = np.empty(n) if llks else None
         st = np.empty((n, k)) if states else None
         cv = np.empty((n, k, k)) if covs else None
         ss = np.empty(int(lib().ppca_h_stats_len(d, k))) if stats else None
         sc = np.empty(4) if scalars else None
-        check(lib().ppca_h_estep(ctx.handle, dataset._h, prec._h, self._base._device(ctx).h, ptr(ll), ptr(st), ptr(cv), ptr(ss), ptr(sc)))
+        if sparse:
+            check(lib().ppca_h_sparse_estep(self._base._device(ctx).h, ctx.handle, dataset._sh, prec._handle, ptr(ll), ptr(st), ptr(cv),
+                                            ptr(ss), ptr(sc)))
+        else:
+            check(lib().ppca_h_estep(ctx.handle, dataset._h, prec._h, self._base._device(ctx).h, ptr(ll), ptr(st), ptr(cv), ptr(ss), ptr(sc)))
         return ll, st, cv, ss, sc
+
+    def predict(self, sparse: "SparseDataset", precisions, query):
+        """PPCAModel.predict under this model's posterior: (mean, var) at the query positions (a SparseDataset of the same rows, or an
+        (indptr, indices) pair), given the row's stored entries at their precisions.  mean = mean_j + c_j . z;
+        var = c_j^T Sigma c_j + sigma^2 is the predictive variance of a reading at UNIT precision -- one taken at precision q has
+        var + sigma^2 (1 / q - 1).  A row without an entry gives the prior predictive (mean_j, |c_j|^2 + sigma^2)."""
+        if not isinstance(sparse, SparseDataset):
+            raise TypeError("predict takes a SparseDataset; on a Dataset use smooth / extrapolate")
+        prec = self._sparse_pair(sparse, precisions)
+        ip, ix = _query_pattern(sparse, query)
+        ctx = sparse._ctx
+        mean, var = np.empty(ix.size), np.empty(ix.size)
+        check(lib().ppca_h_sparse_predict(self._base._device(ctx).h, ctx.handle, sparse._sh, prec._handle, ptr(ip), ptr(ix), ptr(mean),
+                                          ptr(var)))
+        return mean, var
 
     def llks(self, dataset: Dataset, precisions) -> np.ndarray:
         """Per-sample log-density of the observed entries (0 for a row without any)."""
@@ -2394,6 +2468,9 @@ class HPPCAModel:
         return InferredFA(st, cv)
 
     def _recon(self, dataset: Dataset, precisions, mode: int) -> Dataset:
+        if isinstance(dataset, SparseDataset):
+            raise TypeError("smooth / extrapolate are not available on a SparseDataset (their output is N x d): "
+                            "HPPCAModel.predict(sparse, precisions, query) gives the reconstruction at the positions asked for")
         prec = self._pair(dataset, precisions)
         ctx = dataset._ctx
         h = C.c_void_p()
@@ -2412,7 +2489,8 @@ class HPPCAModel:
         """PPCAModel.heldout_score under known precisions (module function `heldout_score` calls it for this family): the posterior of a row from its entries in `train` under `precisions`,
         then every entry of `held` that is observed under `held_precisions` (default: `precisions` -- after a split of the values the
         precisions of both parts are the same array) scored at its own noise level, v = sigma^2 / q + c_j^T Sigma c_j.  A negative or
-        +inf precision raises PPCAError.  One pass on the GPU; nothing of size N x d is allocated."""
+        +inf precision raises PPCAError.  One pass on the GPU; nothing of size N x d is allocated.  Not on SparseDatasets (TypeError)."""
+        _h_no_sparse_score("HPPCAModel.score_heldout", train, held)
         if len(train) != len(held) or train._d != held._d:
             raise ValueError("the train part and the held part differ in shape")
         prec = self._pair(train, precisions)
@@ -2424,15 +2502,22 @@ class HPPCAModel:
     def _iterate(self, dataset: Dataset, precisions, want_llk: bool):
         if len(dataset) == 0:
             raise ValueError("dataset is empty")
-        prec = self._pair(dataset, precisions)
+        sparse = isinstance(dataset, SparseDataset)
+        prec = self._sparse_pair(dataset, precisions) if sparse else self._pair(dataset, precisions)
         ctx, d, k = dataset._ctx, self.output_size, self.state_size
         s_out, c_out, m_out, llk = C.c_double(0.0), np.empty((d, k)), np.empty(d), C.c_double(0.0)
-        check(lib().ppca_h_em_step(ctx.handle, dataset._h, prec._h, d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean),
-                                   C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
-        return HPPCAModel(s_out.value, c_out, m_out, ctx=self._ctx), (llk.value if want_llk else None)
+        if sparse:
+            check(lib().ppca_h_sparse_em_step(d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean), ctx.handle, dataset._sh,
+                                              prec._handle, C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
+        else:
+            check(lib().ppca_h_em_step(ctx.handle, dataset._h, prec._h, d, k, self._base._sigma, ptr(self._base._c), ptr(self._base._mean),
+                                       C.byref(s_out), ptr(c_out), ptr(m_out), C.byref(llk) if want_llk else None))
+        return (HPPCAModel(s_out.value, c_out, m_out, ctx=self._ctx, row_compressed=self._row_compressed or sparse),
+                (llk.value if want_llk else None))
 
     def iterate(self, dataset: Dataset, precisions) -> "HPPCAModel":
-        """One ECM iteration: the log-likelihood cannot decrease."""
+        """One ECM iteration: the log-likelihood cannot decrease.  `dataset` may be a SparseDataset (ppca_h_sparse_em_step, DESIGN.md
+        4.30)."""
         return self._iterate(dataset, precisions, False)[0]
 
     def iterate_with_llk(self, dataset: Dataset, precisions):
@@ -2441,12 +2526,15 @@ class HPPCAModel:
 
     # -- serialisation (own npz container) ----------------------------------------------
     def dump(self) -> bytes:
-        return _npz_dump("ppca_rs_amd.HPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean)
+        return _npz_dump("ppca_rs_amd.HPPCAModel", isotropic_noise=self._base._sigma, transform=self._base._c, mean=self._base._mean,
+                         # (an unflagged model dumps the container it always dumped: absent reads as off)
+                         **({"row_compressed": True} if self._row_compressed else {}))
 
     @staticmethod
     def load(data: bytes) -> "HPPCAModel":
         return _npz_load(data, "ppca_rs_amd.HPPCAModel", "a HPPCAModel",
-                         lambda z: HPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"]))
+                         lambda z: HPPCAModel(float(z["isotropic_noise"]), z["transform"], z["mean"],
+                                              row_compressed=bool(z["row_compressed"]) if "row_compressed" in z.files else False))
 
     def __getstate__(self):
         return self.dump()
@@ -2458,10 +2546,61 @@ class HPPCAModel:
         return (self.isotropic_noise, self.transform, self.mean)
 
 
+class _SparsePrecisions:
+    """The precisions of a SparseDataset's entries on the device: a values view of the dataset (ppca_h_sparse_precisions, DESIGN.md
+    4.30) that shares its pattern, row lists, inverted index and work items.  Everything is checked on the host first -- the length
+    or the pattern, then every precision finite and > 0 -- and only then does the dataset go to the device."""
+
+    def __init__(self, sparse: SparseDataset, precisions):
+        if isinstance(precisions, SparseDataset):
+            if (precisions._d != sparse._d or not np.array_equal(precisions._indptr, sparse._indptr)
+                    or not np.array_equal(precisions._indices, sparse._indices)):
+                raise ValueError("the precisions and the dataset differ in pattern: a precision belongs to every stored entry and to "
+                                 "no other position")
+            p = precisions._values
+        else:
+            p = np.ascontiguousarray(np.asarray(precisions), dtype=np.float64)
+            if p.ndim != 1 or p.shape[0] != sparse.nnz:
+                raise ValueError(f"precisions have shape {p.shape} but the dataset stores {sparse.nnz} entries: one precision per stored "
+                                 "entry, aligned with csr()[2]")
+        if not (np.isfinite(p) & (p > 0.0)).all():
+            raise ValueError("every stored entry needs a precision that is finite and > 0 (on row-compressed data there is no masking "
+                             "precision: an entry that should not count is not stored)")
+        self._indptr, self._indices, self._d = sparse._indptr, sparse._indices, sparse._d
+        self._tiling = (sparse._block_rows, sparse._segment)
+        self._handle = None
+        h = C.c_void_p()
+        check(lib().ppca_h_sparse_precisions(ptr(p), sparse._ctx.handle, sparse._sh, C.byref(h)))
+        self._of, self._handle = sparse._sh, h  # (the library holds the pattern alive; _of names it)
+
+    def _matches(self, sparse: SparseDataset) -> bool:
+        """Whether this view was made on the device copy of `sparse` (or of a with_weights sibling made after the upload)."""
+        return sparse._handle is not None and (sparse._handle is self._of or (
+            sparse._indptr is self._indptr and sparse._indices is self._indices and (sparse._block_rows, sparse._segment) == self._tiling))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                lib().ppca_sparse_free(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+
+def _h_no_sparse_score(what: str, *datasets) -> None:
+    """Held-out scoring under known precisions is not built on row-compressed data: raised before anything touches a device."""
+    if any(isinstance(ds, SparseDataset) for ds in datasets):
+        raise TypeError(f"{what} is not available on a SparseDataset: held-out scoring under known precisions is not built on "
+                        "row-compressed data (DESIGN.md section 7); HPPCAModel.llk / llks / infer / predict / iterate* and "
+                        "HPPCATrainer.train are, and PPCAModel.heldout_score scores the two parts of SparseDataset.holdout under "
+                        "gaussian()")
+
+
 @dataclass
 class HPPCATrainer:
     """EM driver of HPPCAModel.  train returns (model, metrics): the canonical model after n_iters iterations and one TrainMetrics per
-    iteration, of the model that ENTERED it (the log-likelihood is a by-product of the iteration's sweep)."""
+    iteration, of the model that ENTERED it (the log-likelihood is a by-product of the iteration's sweep).  `dataset` may be a
+    SparseDataset with `precisions` one value per stored entry (train; init="pca" raises PPCAModel.init's ValueError)."""
 
     dataset: Dataset
     precisions: object
@@ -2470,7 +2609,8 @@ class HPPCATrainer:
               seed: Optional[int] = None, quiet: bool = True, metric: Literal["aic", "bic", "llk"] = "aic"):
         ds = self.dataset
         model = start or HPPCAModel.init(state_size, ds, seed=seed, method=init)
-        prec = model._pair(ds, self.precisions)  # (uploaded once)
+        # (uploaded once; on a SparseDataset the device view is built once)
+        prec = model._sparse_pair(ds, self.precisions) if isinstance(ds, SparseDataset) else model._pair(ds, self.precisions)
         metrics: List[TrainMetrics] = []
         for idx in range(n_iters):
             new_model, llk = model.iterate_with_llk(ds, prec)
@@ -2483,7 +2623,8 @@ class HPPCATrainer:
     def select_state_size(self, state_sizes, *, fraction: float = 0.1, seed: Optional[int] = None, n_iters: int = 10,
                           init: str = "random", folds: int = 1):
         """PPCATrainer.select_state_size with HPPCAModel fits under this trainer's precisions, which also are the held entries'
-        (the split follows the values): [(state_size, HeldOutScore, HPPCAModel)]."""
+        (the split follows the values): [(state_size, HeldOutScore, HPPCAModel)].  Not on a SparseDataset (TypeError)."""
+        _h_no_sparse_score("HPPCATrainer.select_state_size", self.dataset)
         ds = self.dataset
         prec = self.precisions
         if not isinstance(prec, Dataset):

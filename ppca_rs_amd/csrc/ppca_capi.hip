@@ -3542,6 +3542,14 @@ extern "C" int ppca_h_reconstruct(ppca_ctx *ctx, ppca_dataset *ds, ppca_dataset 
 extern "C" int ppca_h_finalize_host(int32_t d, int32_t k, double sigma, const double *transform, const double *mean, const double *stats,
                                     double *sigma_out, double *transform_out, double *mean_out) {
     if (int rc = check_h_covers(d, k)) return rc;
+    return h_finalize(d, k, sigma, transform, mean, stats, sigma_out, transform_out, mean_out);
+}
+
+// (the limit on d above is the dense sweep's; the step on row-compressed data, ppca_sparse_hetero.hip, has none and comes here)
+int ppca_host::h_finalize(int d, int k, double sigma, const double *transform, const double *mean, const double *stats, double *sigma_out,
+                          double *transform_out, double *mean_out) {
+    if (d < 1 || k < 1 || k > HETERO_MAX_K)
+        return fail(PPCA_ERR_UNSUPPORTED, "the known-precision M-step covers state sizes 1 .. %d (got k=%d, d=%d)", HETERO_MAX_K, k, d);
     if (!transform || !mean || !stats || !sigma_out || !transform_out || !mean_out) return fail(PPCA_ERR_INVALID, "null argument");
     if (int rc = check_sigma(sigma)) return rc;
     const int kp = k * (k + 1) / 2;

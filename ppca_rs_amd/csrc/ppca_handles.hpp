@@ -162,6 +162,9 @@ struct MixAux {
     int *used;
     size_t P;
 };
+// ppca_h_finalize_host behind its limit on the output size (that limit is the dense sweep's), ppca_capi.hip
+int h_finalize(int d, int k, double sigma, const double *transform, const double *mean, const double *stats, double *sigma_out,
+               double *transform_out, double *mean_out);
 int check_prior(const ppca_prior *prior);
 int em_finalize_plain(ppca_ctx *ctx, const ppca_model *model_in, const double *stats_dev, const ppca_prior *prior, ppca_model *out);
 int mix_aux(ppca_ctx *ctx, int32_t nm, MixAux &a);

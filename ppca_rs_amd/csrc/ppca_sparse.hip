@@ -694,9 +694,8 @@ int ppca_sp::sp_check_query(const SpCore &c, const int64_t *query_row_ptr, const
     return PPCA_OK;
 }
 
-extern "C" int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr,
-                                   const int32_t *query_col, double *mean_host, double *var_host) {
-    if (int rc = sp_check(ctx, sp, model)) return rc;
+int ppca_sp::sp_predict(ppca_ctx *ctx, const ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr, const int32_t *query_col,
+                        double *mean_host, double *var_host, const SpRowPass &rows_of_block) {
     const SpCore &c = *sp->core;
     int64_t nq = 0;
     if (int rc = sp_check_query(c, query_row_ptr, query_col, mean_host, var_host, &nq)) return rc;
@@ -714,7 +713,7 @@ extern "C" int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_mo
         const SpBlock &b = c.blocks[bi];
         const int64_t q0 = query_row_ptr[b.row0], q1 = query_row_ptr[b.row0 + b.rows];
         if (q1 == q0) continue;
-        rc = sp_rows_of_block(ctx, sp, b, model, nullptr, dptr<double>(st), dptr<double>(cv), nullptr, nullptr);
+        rc = rows_of_block(b, dptr<double>(st), dptr<double>(cv));
         if (rc) break;
         if (sp_launch(sparse_predict_kernel, sp_elementwise_grid(q1 - q0, ctx->n_cu), ctx->stream, dptr<const int64_t>(qp), dptr<const int32_t>(qc), q0,
                       q1, b.row0, b.rows, c.d, k, model->p(), dptr<const double>(st), dptr<const double>(cv), dptr<double>(mean),
@@ -726,4 +725,13 @@ extern "C" int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_mo
     if (!rc && hipMemcpyAsync(var_host, var->p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         rc = fail(PPCA_ERR_HIP, "download failed");
     return sp_finish(ctx, rc, "predict");  // (the uploads read the caller's buffers)
+}
+
+extern "C" int ppca_sparse_predict(ppca_ctx *ctx, ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr,
+                                   const int32_t *query_col, double *mean_host, double *var_host) {
+    if (int rc = sp_check(ctx, sp, model)) return rc;
+    const auto rows = [&](const SpBlock &b, double *states, double *covs) {
+        return sp_rows_of_block(ctx, sp, b, model, nullptr, states, covs, nullptr, nullptr);
+    };
+    return sp_predict(ctx, sp, model, query_row_ptr, query_col, mean_host, var_host, rows);
 }

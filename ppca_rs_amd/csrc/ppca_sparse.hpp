@@ -1,6 +1,6 @@
-// ppca_sparse.hpp -- what the translation units of the row-compressed data path share (SparseDataset, DESIGN.md sections 4.20 - 4.28):
+// ppca_sparse.hpp -- what the translation units of the row-compressed data path share (SparseDataset, DESIGN.md sections 4.20 - 4.30):
 // ppca_sparse.hip (container, EM passes, llk / infer / predict), ppca_sparse_mix.hip, ppca_sparse_topn.hip, ppca_sparse_heldout.hip,
-// ppca_sparse_fa.hip and ppca_sparse_robust.hip.  Internal: not installed.
+// ppca_sparse_fa.hip, ppca_sparse_robust.hip and ppca_sparse_hetero.hip.  Internal: not installed.
 //
 // Storage.  CSR on the device: row_ptr (int64, n + 1), col (int32, nnz, strictly increasing within a row), val (fp64, nnz).  Rows are
 // cut into blocks of block_rows (fixed at construction: the records of a block stay under 1 GiB at k = 16).  Per block the host builds
@@ -16,6 +16,7 @@
 // file's anonymous namespace.
 #pragma once
 #include <algorithm>
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -218,6 +219,11 @@ int sp_check_query(const SpCore &c, const int64_t *query_row_ptr, const int32_t 
 // the row pass (sparse_row_kernel<k>) over one block: outputs, all nullable, indexed by the row within the block
 int sp_rows_of_block(ppca_ctx *ctx, const ppca_sparse *sp, const SpBlock &b, const ppca_model *model, double *llks, double *states, double *covs,
                      double *rec, double *rscal);
+// ppca_sparse_predict behind its checks of (ctx, sp, model): the query's checks and upload, then per block with a query entry
+// rows_of_block(block, states, covs) -- the caller's row pass into one block's scratch -- and sparse_predict_kernel, the download, one wait
+typedef std::function<int(const SpBlock &, double *, double *)> SpRowPass;
+int sp_predict(ppca_ctx *ctx, const ppca_sparse *sp, const ppca_model *model, const int64_t *query_row_ptr, const int32_t *query_col,
+               double *mean_host, double *var_host, const SpRowPass &rows_of_block);
 // the scratch of sp_accumulate at state size k: one block's records and scalar terms, the scalars' partials, the runs' partials
 struct SpAccScratch {
     BufRef rec, rscal, spart, runpart;

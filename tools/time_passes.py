@@ -26,7 +26,8 @@ data (see sparse_heldout_legs); with `--sparse-topn N_TOP` besid
 data (see sparse_topn_legs); with `--mix NM` beside either, ONLY the legs of PPCAMix on that data (see
 sparse_mix_legs); with `--sparse-topn N_TOP` and `--mix NM` together, ONLY the legs of PPCAMix.recommend (see
 sparse_mix_topn_legs); with `--fa` beside either, ONLY the legs of FAModel on that data (see sparse_fa_legs); with
-`--robust` beside either, ONLY the legs of TPPCAModel on that data (see sparse_t_legs)."""
+`--robust` beside either, ONLY the legs of TPPCAModel on that data (see sparse_t_legs); with `--sparse-h` beside
+either, ONLY the legs of HPPCAModel on that data (see sparse_h_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -534,6 +535,58 @@ def sparse_t_legs(reps=5):
           f"against (5) = {med[4]:.3f} ms")
 
 
+def sparse_h_legs(reps=5):
+    """HPPCAModel on a SparseDataset (`--sparse-h [--reps R]` beside `--sparse DENSITY` or `--sparse-rows M`), in one
+    process, alternating, every repetition timed on its own behind a synchronise: (1) PPCAModel.llks(sp), (2) HPPCAModel.llks(sp, view),
+    (3) the construction of the precisions' view (host check, upload of nnz doubles, the fill of the index-order copy),
+    (4) PPCAModel.iterate(sp), (5) HPPCAModel.iterate(sp, view).  Precisions log-uniform in [2^-10, 2^10].  The yardstick is the
+    Gaussian model's own passes in the same process: reported are (2) / (1), (3) / (4) and (5) / (4)."""
+    _, _, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    ix, v = cols.int().cpu().numpy(), vals.cpu().numpy()
+    del cols, vals
+    sp = P.SparseDataset(indptr, ix, v, d, ctx=ctx)
+    sp._sh
+    print(f"  host: the index, row lists and work items {sp.index_build_seconds():.2f} s", flush=True)
+    model = P.PPCAModel.init(k, sp, seed=3).iterate(sp)
+    h = P.HPPCAModel.from_ppca(model, row_compressed=True)
+    pv = np.exp(np.random.default_rng(9).uniform(np.log(2.0 ** -10), np.log(2.0 ** 10), nnz))
+    view = h._sparse_pair(sp, pv)
+
+    def series(fn, r, warm):
+        for _ in range(warm):
+            fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:72s} median {med:10.3f} ms  min {ts.min():10.3f}  max {ts.max():10.3f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    legs = [("(1) PPCAModel.llks(sp)", lambda: model.llks(sp)), ("(2) HPPCAModel.llks(sp, view)", lambda: h.llks(sp, view)),
+            ("(3) the precisions' view: check, upload, index-order fill", lambda: h._sparse_pair(sp, pv)),
+            ("(4) PPCAModel.iterate(sp)", lambda: model.iterate(sp)), ("(5) HPPCAModel.iterate(sp, view)", lambda: h.iterate(sp, view))]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn in legs:
+            got.setdefault(name, []).append(series(fn, reps, 2))
+    med = [report(name, np.concatenate(got[name])) for name, _ in legs]
+    spread = [float((np.concatenate(got[name]).max() - np.concatenate(got[name]).min()) / m_) for (name, _), m_ in zip(legs, med)]
+    print(f"  (2) / (1): {med[1] / med[0]:.3f};  (3) / (4): {med[2] / med[3]:.3f};  (5) / (4): {med[4] / med[3]:.3f}  "
+          f"(run-to-run spread of (4), (5): {spread[3]:.1%}, {spread[4]:.1%})")
+
+
+if "--sparse-h" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
+    sparse_h_legs()
+    sys.exit(0)
 if "--robust" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
     sparse_t_legs()
     sys.exit(0)
