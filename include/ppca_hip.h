@@ -523,6 +523,27 @@ int ppca_sparse_from_host(ppca_ctx *ctx, int64_t n, int32_t d, const int64_t *ro
  * offsets relative to the block's first entry.  Validates like the constructor, which calls the same routine. */
 int ppca_sparse_transpose_host(int64_t n, int32_t d, const int64_t *row_ptr, const int32_t *col, const double *val, int64_t block_rows,
                                int64_t *col_ptr_out, int32_t *t_row_out, double *t_val_out);
+/* ppca_sparse_from_host for CSR arrays that already live on the device.  The three arrays and the weights (n or NULL)
+ * are borrowed the way ppca_dataset_from_device borrows x: the library never writes or frees them and the caller keeps them alive as
+ * long as the handle, or any handle made from it, lives.  The format is validated on the device by the rules above; a violation is
+ * PPCA_ERR_INVALID before anything is built, and the message names the lowest offending row whatever the grid.  The row lists, the
+ * inverted index and the work items are built on the device and equal those of ppca_sparse_from_host on the same arrays, integer for
+ * integer (t_val: the input's bits), so every pass gives the same bits on either handle.  A few integers per block and one flag per
+ * column come back to the host; nothing of size nnz does.  ppca_sparse_build_seconds: the wall time of the build, its waits included. */
+int ppca_from_device_sparse(int64_t n, int32_t d, ppca_ctx *ctx, const int64_t *row_ptr_dev, const int32_t *col_dev, const double *val_dev,
+                            const double *weights_dev, int64_t block_rows, int32_t segment, ppca_sparse **out);
+/* The index of a handle from either constructor, block by block (0 <= block < *n_blocks_out of ppca_n_blocks_sparse), every output
+ * nullable:
+ *   counts_out   (13) row0, rows, e0, nnz, nbin[3], bin_off[3], n_items, n_long, n_runs of the block
+ *   col_ptr_out  (d + 1) the block's column offsets relative to e0, recomputed from the items
+ *   t_row_out    (nnz of the block, int32) and t_val_out (fp64; a values view: the view's): the inverted index
+ *   rowlist_out  (rows, int32) the three row lists end to end
+ *   items_out    (n_items x 24 bytes: int64 start, int64 dest, int32 col, int32 len) and longs_out (n_long x 16 bytes: int64 first,
+ *                int32 col, int32 nruns): the work items of the column pass
+ * block = -1: counts_out = n, nnz, block_rows, segment, max_rows, max_runs, nonempty_rows, d, n_blocks, 0 .. (no other output). */
+int ppca_index_to_host_sparse(int64_t block, ppca_sparse *sp, int64_t *counts_out, int64_t *col_ptr_out, int32_t *t_row_out, double *t_val_out,
+                              int32_t *rowlist_out, void *items_out, void *longs_out);
+int ppca_n_blocks_sparse(int64_t *n_blocks_out, const ppca_sparse *sp);
 int ppca_sparse_free(ppca_sparse *sp);
 int64_t ppca_sparse_len(const ppca_sparse *sp);
 int32_t ppca_sparse_output_size(const ppca_sparse *sp);
@@ -610,6 +631,13 @@ int ppca_mix_topn_sparse(ppca_ctx *ctx, ppca_sparse *sp, ppca_model *const *mode
  * monotone row_ptr, else PPCA_ERR_INVALID. */
 int ppca_heldout_split_csr_host(int64_t n, const int64_t *row_ptr, const int32_t *col, double lo, double hi, uint64_t seed,
                                 int64_t row_offset, uint8_t *held_flag_out, int64_t *counts_out);
+/* The same split on the device: the entries of sp that ppca_heldout_split_csr_host flags go to *held_out, the others to
+ * *train_out, both new handles with device-owned CSR arrays (columns and value bits kept, in order), sp's block_rows, segment and
+ * weights (shared, not copied), their index built as by ppca_from_device_sparse.  A values view is split by its own values.
+ * counts_out (nullable, 2) = [entries kept, entries held].  Preconditions and codes of the host routine; free both with
+ * ppca_sparse_free, in any order with sp. */
+int ppca_heldout_split_sparse(double lo, double hi, uint64_t seed, int64_t row_offset, ppca_ctx *ctx, ppca_sparse *sp,
+                              ppca_sparse **train_out, ppca_sparse **held_out, int64_t *counts_out);
 /* ppca_heldout_score on row-compressed data: (z, Sigma) is the posterior of row i given its entries in `train`
  * (ppca_sparse_infer; an empty row: 0, I) and every entry x of `held` in that row is scored as a new reading of column j,
  *   m = mean_j + c_j^T z,  v = sigma^2 + c_j^T Sigma c_j,  e = x - m,  l = -1/2 (ln 2 pi + ln v + e^2 / v)

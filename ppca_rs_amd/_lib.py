@@ -173,6 +173,9 @@ SIGNATURES = {
     "ppca_h_em_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, c_double_p, C.c_void_p, C.c_void_p, c_double_p]),
     "ppca_sparse_from_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, c_void_pp]),
     "ppca_sparse_transpose_host": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_from_device_sparse": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, c_void_pp]),
+    "ppca_index_to_host_sparse": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppca_n_blocks_sparse": (C.c_int, [C.POINTER(C.c_int64), C.c_void_p]),
     "ppca_sparse_free": (C.c_int, [C.c_void_p]),
     "ppca_sparse_len": (C.c_int64, [C.c_void_p]),
     "ppca_sparse_output_size": (C.c_int32, [C.c_void_p]),
@@ -194,6 +197,7 @@ SIGNATURES = {
     "ppca_mix_sparse_predict": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppca_mix_topn_sparse": (C.c_int, [C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ppca_heldout_split_csr_host": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ppca_heldout_split_sparse": (C.c_int, [C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, c_void_pp, c_void_pp, C.c_void_p]),
     "ppca_heldout_score_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppca_scale_columns_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, C.c_void_p, C.c_void_p]),
     "ppca_fa_sparse_em_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p]),

@@ -431,7 +431,11 @@ class SparseDataset:
     increasing within a row, in [0, n_columns)), values (nnz, finite).  Anything else raises ValueError before the library is touched.
     block_rows / segment: the two tiling lengths of the passes (None: the library's defaults; tests put the seams at small sizes).
     The entries go to the device, with the inverted index the statistics pass reads, on first use.
-    `holdout` / `holdout_range` / `kfold` split the entries on the host exactly as Dataset's split the same matrix, and
+    `SparseDataset.from_device(indptr_ptr, indices_ptr, values_ptr, n, n_columns)` borrows CSR arrays that already live on the device
+    and validates them and builds the index there: such a dataset holds no host arrays (csr() and its like fetch them
+    on first use), every method that takes a SparseDataset takes it with the same bits, and its hold-out splits run on the device.
+    `holdout` / `holdout_range` / `kfold` split the entries (on the host, or with on_device=True on the device) exactly as Dataset's
+    split the same matrix, and
     PPCAModel.heldout_score takes the two parts.  PPCAMix takes one too: llk / llks / infer_cluster / iterate* /
     predict and PPCAMixTrainer.  So does FAModel, one noise level per column: llk / llks / infer / iterate* / predict /
     heldout_score and FATrainer.  So does TPPCAModel, the robust model: llk / llks / row_weights / mahalanobis / infer /
@@ -478,7 +482,8 @@ class SparseDataset:
                 raise ValueError(f"{name} must be positive")
         for a in (ip, ix, v):
             a.setflags(write=False)
-        self._indptr, self._indices, self._vals, self._d, self._w = ip, ix, v, d, w
+        self._ip, self._ix, self._vals, self._d, self._wts = ip, ix, v, d, w
+        self._on_device = False
         self._block_rows, self._segment = int(block_rows or 0), int(segment or 0)
         self._ctx_arg = ctx
         self._handle = None
@@ -509,6 +514,86 @@ class SparseDataset:
         indptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))]).astype(np.int64)
         return cls(indptr, c[order], v[order], d, weights, **kw)
 
+    @classmethod
+    def from_device(cls, indptr_ptr: int, indices_ptr: int, values_ptr: int, n: int, n_columns: int, weights_ptr: Optional[int] = None, *,
+                    ctx=None, keepalive=None, block_rows: Optional[int] = None, segment: Optional[int] = None) -> "SparseDataset":
+        """Borrow CSR arrays that live on the device (e.g. three torch tensors' data_ptr(): indptr int64 (n + 1), indices int32 and
+        values float64 (nnz each), weights float64 (n) or None); `keepalive` is held, and handed on to every dataset made from this
+        one.  The format is validated and the index built on the device: a violation raises PPCAError naming the lowest
+        offending row.  The dataset holds a handle and no host arrays: csr(), to_dense(), with_values and the host-side split fetch
+        them on first use; its hold-out splits run on the device."""
+        n, d = int(n), int(n_columns)
+        if not indptr_ptr:
+            raise ValueError("indptr_ptr is null")
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if d < 1 or d >= 2 ** 31:
+            raise ValueError("n_columns must lie in [1, 2^31)")
+        for name, val in (("block_rows", block_rows), ("segment", segment)):
+            if val is not None and int(val) < 1:
+                raise ValueError(f"{name} must be positive")
+        c = _ctx(ctx)
+        h = C.c_void_p()
+        check(lib().ppca_from_device_sparse(n, d, c.handle, C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr) if indices_ptr else None,
+                                            C.c_void_p(values_ptr) if values_ptr else None, C.c_void_p(weights_ptr) if weights_ptr else None,
+                                            int(block_rows or 0), int(segment or 0), C.byref(h)))
+        return cls._device_born(h, c, d, int(block_rows or 0), int(segment or 0), weights=bool(weights_ptr), keepalive=keepalive)
+
+    @classmethod
+    def _device_born(cls, handle, ctx, d: int, block_rows: int, segment: int, *, weights, keepalive) -> "SparseDataset":
+        """A dataset around a handle the library built on the device.  weights: False (all ones), True (on the device: fetched on
+        first use) or the host copy."""
+        out = cls.__new__(cls)
+        out._ip = out._ix = out._vals = None
+        out._wts = None if isinstance(weights, bool) else weights
+        out._w_on_device = weights is True
+        out._d, out._block_rows, out._segment = d, block_rows, segment
+        out._ctx_arg, out._handle, out._on_device, out._keepalive = ctx, handle, True, keepalive
+        return out
+
+    def _fetch(self) -> None:
+        """The pattern and the weights of a device-born dataset, to the host (once)."""
+        if self._ip is None:
+            n, nnz = int(lib().ppca_sparse_len(self._handle)), int(lib().ppca_sparse_nnz(self._handle))
+            ip, ix = np.empty(n + 1, dtype=np.int64), np.empty(nnz, dtype=np.int32)
+            check(lib().ppca_sparse_to_host(self._handle, ptr(ip), ptr(ix), None, None))
+            ip.setflags(write=False)
+            ix.setflags(write=False)
+            self._ip, self._ix = ip, ix
+        if getattr(self, "_w_on_device", False):
+            w = np.empty(len(self))
+            check(lib().ppca_sparse_to_host(self._handle, None, None, None, ptr(w)))
+            self._wts, self._w_on_device = w, False
+
+    # the host arrays: a device-born dataset downloads them on first use
+    @property
+    def _indptr(self) -> np.ndarray:
+        self._fetch()
+        return self._ip
+
+    @_indptr.setter
+    def _indptr(self, a):
+        self._ip = a
+
+    @property
+    def _indices(self) -> np.ndarray:
+        self._fetch()
+        return self._ix
+
+    @_indices.setter
+    def _indices(self, a):
+        self._ix = a
+
+    @property
+    def _w(self) -> Optional[np.ndarray]:
+        if getattr(self, "_w_on_device", False):
+            self._fetch()
+        return self._wts
+
+    @_w.setter
+    def _w(self, w):
+        self._wts, self._w_on_device = w, False
+
     # -- the device handle ----------------------------------------------------
     @property
     def _ctx(self) -> _lib.Context:
@@ -529,7 +614,7 @@ class SparseDataset:
     def _values(self) -> np.ndarray:
         """The values on the host.  A values view (`_scale_columns`) is made on the device and fetches them on first use only."""
         if self._vals is None:
-            v = np.empty(self._indices.size)
+            v = np.empty(self.nnz)
             check(lib().ppca_sparse_to_host(self._handle, None, None, ptr(v), None))
             v.setflags(write=False)
             self._vals = v
@@ -558,14 +643,14 @@ class SparseDataset:
 
     # -- accessors ------------------------------------------------------------
     def __len__(self) -> int:
-        return int(self._indptr.size - 1)
+        return int(self._ip.size - 1) if self._ip is not None else int(lib().ppca_sparse_len(self._handle))
 
     def output_size(self) -> Optional[int]:
         return self._d if len(self) > 0 else None
 
     @property
     def nnz(self) -> int:
-        return int(self._indices.size)
+        return int(self._ix.size) if self._ix is not None else int(lib().ppca_sparse_nnz(self._handle))
 
     def csr(self):
         """(indptr int64, indices int32, values float64): copies."""
@@ -598,11 +683,12 @@ class SparseDataset:
             raise ValueError(f"values must be 1-D of length nnz = {self.nnz}; got shape {v.shape}")
         if not np.isfinite(v).all():
             raise ValueError("values must be finite (an entry that is missing is simply not stored)")
+        v = v.copy()
+        v.setflags(write=False)
+        self._fetch()  # (the new dataset has no handle to fetch its pattern through)
         out = SparseDataset.__new__(SparseDataset)
         out.__dict__.update(self.__dict__)
         out.__dict__.pop("holdout_counts", None)
-        v = v.copy()
-        v.setflags(write=False)
         out._vals, out._handle = v, None
         return out
 
@@ -654,6 +740,7 @@ class SparseDataset:
     def _select(self, keep: np.ndarray) -> "SparseDataset":
         """The entries flagged in `keep` (bool, nnz) as a SparseDataset with this one's weights, n_columns, ctx and tiling; values keep
         their bits.  No device work: the part uploads on first use."""
+        self._fetch()  # (a device-born dataset: its pattern and weights, before the part is cut loose from the handle)
         out = SparseDataset.__new__(SparseDataset)
         out.__dict__.update(self.__dict__)
         out._handle = None
@@ -663,12 +750,22 @@ class SparseDataset:
             a.setflags(write=False)
         return out
 
-    def _split(self, lo: float, hi: float, seed: Optional[int], row_offset: int):
-        """The call of ppca_heldout_split_csr_host (host code) and the two parts."""
+    def _split(self, lo: float, hi: float, seed: Optional[int], row_offset: int, on_device: Optional[bool] = None):
+        """The call of ppca_heldout_split_csr_host (host code) and the two parts; on the device (on_device, or None on a device-born
+        dataset or a part of one) the call of ppca_heldout_split_sparse, whose parts are device-born."""
         if row_offset < 0:
             raise ValueError("row_offset must be >= 0")
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1)[0])
+        if getattr(self, "_on_device", False) if on_device is None else on_device:
+            th, hh, counts = C.c_void_p(), C.c_void_p(), np.zeros(2, dtype=np.int64)
+            check(lib().ppca_heldout_split_sparse(float(lo), float(hi), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), self._ctx.handle,
+                                                  self._sh, C.byref(th), C.byref(hh), ptr(counts)))
+            weights = True if getattr(self, "_w_on_device", False) else (self._wts if self._wts is not None else False)
+            parts = [SparseDataset._device_born(h, self._ctx, self._d, self._block_rows, self._segment, weights=weights,
+                                                keepalive=getattr(self, "_keepalive", None)) for h in (th, hh)]
+            parts[0].holdout_counts = parts[1].holdout_counts = (int(counts[0]), int(counts[1]))
+            return parts[0], parts[1]
         flags, counts = np.zeros(self.nnz, dtype=np.uint8), np.zeros(2, dtype=np.int64)
         check(lib().ppca_heldout_split_csr_host(len(self), ptr(self._indptr), ptr(self._indices), float(lo), float(hi),
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), ptr(flags), ptr(counts)))
@@ -677,34 +774,37 @@ class SparseDataset:
         train.holdout_counts = heldp.holdout_counts = (int(counts[0]), int(counts[1]))
         return train, heldp
 
-    def holdout(self, fraction: float, seed: Optional[int] = None, *, row_offset: int = 0):
+    def holdout(self, fraction: float, seed: Optional[int] = None, *, row_offset: int = 0, on_device: Optional[bool] = None):
         """(train, held): Dataset.holdout on row-compressed data.  Every entry is held with probability `fraction`, decided by the
         same word of the counter-based generator, keyed by (seed, row_offset + row, column): SparseDataset.from_dense(x).holdout(f, s)
         holds exactly the entries Dataset(x).holdout(f, s) holds.  Both parts are SparseDatasets with this one's weights, n_columns
         and tiling; the split is host work and touches no device.  seed=None draws a fresh seed.
-        train.holdout_counts = held.holdout_counts = (entries kept, entries held)."""
+        train.holdout_counts = held.holdout_counts = (entries kept, entries held).
+        on_device: None = on the device for a device-born dataset (`from_device`) or a part of one, on the host otherwise; True forces
+        the device split (a host-born dataset uploads first), whose parts are device-born: the same entries, the same value bits."""
         if not 0.0 <= float(fraction) <= 1.0:  # (NaN fails both comparisons)
             raise ValueError("fraction must lie in [0, 1]")
-        return self._split(0.0, fraction, seed, row_offset)
+        return self._split(0.0, fraction, seed, row_offset, on_device)
 
-    def holdout_range(self, lo: float, hi: float, seed: Optional[int] = None, *, row_offset: int = 0):
+    def holdout_range(self, lo: float, hi: float, seed: Optional[int] = None, *, row_offset: int = 0, on_device: Optional[bool] = None):
         """`holdout` with the held entries those whose uniform u lies in [lo, hi) (Dataset.holdout_range).  Requires 0 <= lo <= hi <= 1."""
         if not 0.0 <= float(lo) <= float(hi) <= 1.0:  # (NaN fails the comparisons)
             raise ValueError("the range must satisfy 0 <= lo <= hi <= 1")
-        return self._split(lo, hi, seed, row_offset)
+        return self._split(lo, hi, seed, row_offset, on_device)
 
     fold_edges = staticmethod(Dataset.fold_edges)
 
-    def kfold(self, n_folds: int, seed: Optional[int] = None, *, row_offset: int = 0):
+    def kfold(self, n_folds: int, seed: Optional[int] = None, *, row_offset: int = 0, on_device: Optional[bool] = None):
         """The n_folds (train, held) pairs of entry-wise K-fold cross-validation (Dataset.kfold): every entry is held in exactly one
-        fold.  seed=None draws one fresh seed for all of them."""
+        fold.  seed=None draws one fresh seed for all of them.  on_device: as `holdout`."""
         edges = Dataset.fold_edges(n_folds)
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1)[0])
-        return [self.holdout_range(lo, hi, seed, row_offset=row_offset) for lo, hi in zip(edges, edges[1:])]
+        return [self.holdout_range(lo, hi, seed, row_offset=row_offset, on_device=on_device) for lo, hi in zip(edges, edges[1:])]
 
     def index_build_seconds(self) -> float:
-        """Host time the constructor of the device copy spent on the inverted index, the row lists and the work items."""
+        """Time the constructor of the device copy spent on the inverted index, the row lists and the work items: host time for a
+        host-born dataset, the wall time of the device build (its waits included) for a device-born one."""
         return float(lib().ppca_sparse_build_seconds(self._sh))
 
     def _dense(self) -> np.ndarray:

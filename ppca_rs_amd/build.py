@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libppca_hip.so")
-SOURCES = ["ppca_kernels.hip", "ppca_pass.hip", "ppca_mix.hip", "ppca_util.hip", "ppca_em9.hip", "ppca_em16.hip", "ppca_llk.hip", "ppca_generic.hip", "ppca_solve4.hip", "ppca_sample.hip", "ppca_loo.hip", "ppca_heldout.hip", "ppca_scale.hip", "ppca_kmeans.hip", "ppca_moments.hip", "ppca_robust.hip", "ppca_hetero.hip", "ppca_sparse.hip", "ppca_sparse_mix.hip", "ppca_sparse_topn.hip", "ppca_sparse_heldout.hip", "ppca_sparse_fa.hip", "ppca_sparse_robust.hip", "ppca_sparse_hetero.hip", "ppca_capi.hip", "ppca_comm.hip"]
+SOURCES = ["ppca_kernels.hip", "ppca_pass.hip", "ppca_mix.hip", "ppca_util.hip", "ppca_em9.hip", "ppca_em16.hip", "ppca_llk.hip", "ppca_generic.hip", "ppca_solve4.hip", "ppca_sample.hip", "ppca_loo.hip", "ppca_heldout.hip", "ppca_scale.hip", "ppca_kmeans.hip", "ppca_moments.hip", "ppca_robust.hip", "ppca_hetero.hip", "ppca_sparse.hip", "ppca_sparse_mix.hip", "ppca_sparse_topn.hip", "ppca_sparse_heldout.hip", "ppca_sparse_fa.hip", "ppca_sparse_robust.hip", "ppca_sparse_hetero.hip", "ppca_sparse_build.hip", "ppca_capi.hip", "ppca_comm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]  # (tools/devbuild.py compiles with the same line)
 DEPS = SOURCES + ["ppca_small.hpp", "ppca_internal.hpp", "ppca_solve.hpp", "ppca_handles.hpp", "ppca_device.hpp", "ppca_sweep.hpp", "ppca_sparse.hpp", os.path.join("..", "..", "include", "ppca_hip.h")]
 

@@ -1,9 +1,10 @@
-// ppca_sparse.hpp -- what the translation units of the row-compressed data path share (SparseDataset, DESIGN.md sections 4.20 - 4.30):
+// ppca_sparse.hpp -- what the translation units of the row-compressed data path share (SparseDataset, DESIGN.md sections 4.20 - 4.31):
 // ppca_sparse.hip (container, EM passes, llk / infer / predict), ppca_sparse_mix.hip, ppca_sparse_topn.hip, ppca_sparse_heldout.hip,
-// ppca_sparse_fa.hip, ppca_sparse_robust.hip and ppca_sparse_hetero.hip.  Internal: not installed.
+// ppca_sparse_fa.hip, ppca_sparse_robust.hip, ppca_sparse_hetero.hip and ppca_sparse_build.hip (the same container built on the device
+// from CSR arrays that live there, and the split of such a handle).  Internal: not installed.
 //
 // Storage.  CSR on the device: row_ptr (int64, n + 1), col (int32, nnz, strictly increasing within a row), val (fp64, nnz).  Rows are
-// cut into blocks of block_rows (fixed at construction: the records of a block stay under 1 GiB at k = 16).  Per block the host builds
+// cut into blocks of block_rows (fixed at construction: the records of a block stay under 1 GiB at k = 16).  Per block the constructor builds
 //   - three row lists by row length m: m <= 16, m <= 64, longer (the bins of the row pass);
 //   - the inverted index in CSC order (per column, the block's entries in ascending row): t_row (int32, row within the block) and
 //     t_val, by a counting sort that is stable in row order (ppca_sparse_transpose_host);

@@ -27,7 +27,8 @@ data (see sparse_topn_legs); with `--mix NM` beside either, ONLY
 sparse_mix_legs); with `--sparse-topn N_TOP` and `--mix NM` together, ONLY the legs of PPCAMix.recommend (see
 sparse_mix_topn_legs); with `--fa` beside either, ONLY the legs of FAModel on that data (see sparse_fa_legs); with
 `--robust` beside either, ONLY the legs of TPPCAModel on that data (see sparse_t_legs); with `--sparse-h` beside
-either, ONLY the legs of HPPCAModel on that data (see sparse_h_legs)."""
+either, ONLY the legs of HPPCAModel on that data (see sparse_h_legs); with `--sparse-build` beside either, ONLY the
+legs of the device-side build and split against the host's (see sparse_build_legs)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -584,6 +585,78 @@ def sparse_h_legs(reps=5):
           f"(run-to-run spread of (4), (5): {spread[3]:.1%}, {spread[4]:.1%})")
 
 
+def sparse_build_legs(reps=2):
+    """The device-side build of SparseDataset (`--sparse-build [--reps R]` beside `--sparse DENSITY` or
+    `--sparse-rows M`), in one process, alternating, every repetition timed on its own behind a synchronise, host path against device
+    path: (1) ppca_sparse_from_host (validation, index, row lists, work items, upload of five arrays) from host arrays, (2)
+    SparseDataset.from_device from the same arrays resident on the device; (3) the host holdout(0.1) and the device copies of both
+    parts, (4) the device split of the device-born dataset; (5), (6) PPCATrainer.select_state_size([K], folds=5, n_iters=5) on the
+    host-born and on the device-born dataset.  Reported: the medians and (2) / (1), (4) / (3), (6) / (5)."""
+    torch, dev, _, _, cols, vals, _, indptr, nnz = sparse_data()
+    if "--reps" in sys.argv:
+        reps = int(sys.argv[sys.argv.index("--reps") + 1])
+    ip_d, ix_d, v_d = torch.from_numpy(indptr).to(dev), cols.int().contiguous(), vals.contiguous()
+    ix, v = ix_d.cpu().numpy(), v_d.cpu().numpy()
+    del cols, vals
+    torch.cuda.synchronize()
+    host = P.SparseDataset(indptr, ix, v, d, ctx=ctx)
+
+    def host_build():
+        s = P.SparseDataset.__new__(P.SparseDataset)  # (the same arrays, no second pass of the Python checks)
+        s.__dict__.update(host.__dict__)
+        s._handle = None
+        s._sh
+        return s
+
+    def dev_build():
+        return P.SparseDataset.from_device(ip_d.data_ptr(), ix_d.data_ptr(), v_d.data_ptr(), n, d, ctx=ctx, keepalive=(ip_d, ix_d, v_d))
+
+    host._sh
+    born = dev_build()
+    print(f"  index, row lists and work items: host {host.index_build_seconds():.3f} s (without validation and upload), device "
+          f"{born.index_build_seconds():.3f} s (with validation and waits)", flush=True)
+
+    def host_split():
+        t, h = host.holdout(0.1, 5)
+        t._sh, h._sh
+
+    def select(sp):
+        return P.PPCATrainer(sp).select_state_size([k], seed=7, folds=5, n_iters=5)
+
+    def series(fn, r):
+        ctx.synchronize()
+        ts = []
+        for _ in range(r):
+            t0 = time.perf_counter()
+            fn()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return np.array(ts)
+
+    def report(name, ts):
+        med = float(np.median(ts))
+        print(f"{name:72s} median {med:10.2f} ms  min {ts.min():10.2f}  max {ts.max():10.2f}  ({ts.size} repetitions)", flush=True)
+        return med
+
+    a, b = select(host), select(born)  # (also the warm-up: code objects, the block cache)
+    print(f"  select_state_size mean_llk: host-born {a[0][1].mean_llk!r}, device-born {b[0][1].mean_llk!r}", flush=True)
+    legs = [("(1) host build and upload (ppca_sparse_from_host)", host_build, reps), ("(2) device build (SparseDataset.from_device)", dev_build, reps),
+            ("(3) host holdout(0.1) and the device copies of both parts", host_split, reps),
+            ("(4) device split (holdout(0.1) of the device-born dataset)", lambda: born.holdout(0.1, 5), reps),
+            (f"(5) select_state_size([{k}], folds=5, n_iters=5), host-born", lambda: select(host), 1),
+            (f"(6) select_state_size([{k}], folds=5, n_iters=5), device-born", lambda: select(born), 1)]
+    got = {}
+    for _ in range(2):  # the legs alternate, so that all see the same machine
+        for name, fn, r in legs:
+            got.setdefault(name, []).append(series(fn, r))
+    med = [report(name, np.concatenate(got[name])) for name, _, _ in legs]
+    print(f"  nnz = {nnz}: (2) / (1): {med[1] / med[0]:.3f};  (4) / (3): {med[3] / med[2]:.3f};  (6) / (5): {med[5] / med[4]:.3f}  "
+          "(below 1: the device path is faster)")
+
+
+if "--sparse-build" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
+    sparse_build_legs()
+    sys.exit(0)
 if "--sparse-h" in sys.argv and ("--sparse" in sys.argv or "--sparse-rows" in sys.argv):
     sparse_h_legs()
     sys.exit(0)
